@@ -9,7 +9,9 @@ GPU: 5 discriminator updates + 1 generator update (hinge loss, 2 x Adam), G [256
 
 Prints ONE JSON line (rank 0) with the throughput, a `roofline` object for the dominant kernel
 (per-launch HIP-event timing of an instrumented pass of the same step) and a `cpu_baseline` object
-(the CPU oracle timed on this host's cores, N=1 only).
+(the CPU oracle timed on this host's cores, N=1 only).  `--dump-outputs DIR` also writes what the last timed
+step computed (its losses and the state_dict it left in the model) as DIR/<name>.npy: the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -192,6 +194,40 @@ def log(msg):
     print(f'[bench {time.strftime("%H:%M:%S")}] {msg}', file=sys.stderr, flush=True)
 
 
+DUMP_BUDGET = 64_000_000        # bytes, all files of --dump-outputs together (.npy headers included)
+
+
+def step_outputs(losses, model):
+    """What the timed train step hands its caller after its last iteration, as host numpy arrays: the loss(es) it
+    returns and the trained state it leaves in the model (parameters and buffers, state_dict keys as names)."""
+    import numpy as np
+    out = {name: np.asarray(t.detach().float().cpu().numpy()) for name, t in losses.items()}
+    for k, v in model.state_dict().items():
+        v = v.detach().cpu()
+        out['state.' + k] = v.double().numpy() if v.dtype in (torch.float64, torch.int64) else v.float().numpy()
+    return out
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET, seed=0):
+    """--dump-outputs: every array as DIR/<name>.npy (float32, or float64 where the source is float64 / int64).  If the
+    arrays exceed `budget` bytes together, the smallest are kept whole and each remaining one gets an equal share of
+    what is left: a fixed sample of its flattened elements (PCG64(seed) positions, ascending), the same on every run."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    names = sorted(arrays, key=lambda n: (arrays[n].nbytes, n))
+    left, sampled = budget - 256 * len(names), []          # (.npy headers: 128 bytes each)
+    for i, name in enumerate(names):
+        x = arrays[name]
+        share = left // (len(names) - i)
+        if x.nbytes > share:
+            idx = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(x.size, share // x.itemsize, replace=False))
+            x = x.reshape(-1)[idx]
+            sampled.append(name)
+        np.save(os.path.join(dirname, name + '.npy'), x)
+        left -= x.nbytes
+    log(f'dumped {len(names)} arrays to {dirname}' + (f'; sampled: {sampled}' if sampled else ''))
+
+
 def bench_mcglow(a, dev, dtype, world, rank, group):
     """Secondary workload (BASELINE configs[3]): MCGlow train step (train_glow.py:108-121)
     on Omniglot as the reference runs it ([1,32,32], 1623 modes) or CIFAR-10 ([3,32,32], 10 modes); hidden 512,
@@ -249,6 +285,8 @@ def bench_mcglow(a, dev, dtype, world, rank, group):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt)
     value = a.batch * world * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, step_outputs({'loss': loss}, model))
     roofline = None
     if not a.no_roofline and rank == 0:
         roofline = profile_alone(tr, lambda: tr._eager(img, lab, torch.rand_like(img)), PEAK_TFLOPS[a.dtype])
@@ -311,6 +349,8 @@ def bench_mcvae(a, dev, dtype, world, rank, group):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt)
     value = a.batch * world * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, step_outputs({'loss': loss}, model))
     roofline = None
     if not a.no_roofline and rank == 0:
         eps = torch.randn(a.batch, model.latent_size, device=dev)
@@ -374,6 +414,8 @@ def bench_mcpixelcnn(a, dev, dtype, world, rank, group):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt)
     value = a.batch * world * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, step_outputs({'loss': loss}, model))
     roofline = None
     if not a.no_roofline and rank == 0:
         roofline = profile_alone(tr, lambda: tr._eager(codes, lab), PEAK_TFLOPS[a.dtype])
@@ -422,7 +464,12 @@ def main():
                          'inside the timed region')
     ap.add_argument('--grad-bf16', action='store_true', help='N > 1: gradient buckets cross the links as bf16 (off: fp32, as the reference sums them)')
     ap.add_argument('--roofline-passes', type=int, default=5, help='instrumented eager iterations the roofline object averages')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned (losses) and left in the model (state_dict) '
+                         'as DIR/<name>.npy, at most 64 MB in all (rank 0)')
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -535,6 +582,8 @@ def main():
     value = a.batch * world * a.steps / dt
     log(f'timed region done: {value:.1f} images/s')
     losses = (float(dl), float(gl))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, step_outputs({'d_loss': dl, 'g_loss': gl}, model))
     # the same loop for >= 9 s more: sustained clocks, and long enough for an outside sampler to see the GPU busy
     sustained = None
     if a.sustain_steps > 0:

@@ -48,3 +48,25 @@ def test_bench_default_path_replays_graphs(workload):
     assert out['n_gpus'] == 1 and out['value'] > 0 and out['mask_compaction'] is True
     rf = out['roofline']
     assert rf['unit'] in ('TFLOP/s', 'GB/s') and 0 < rf['frac'] < 1 and rf['bound'] in ('mfma', 'hbm')
+
+
+def test_bench_dump_outputs_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the losses of the last timed step (the JSON line's last_losses) and the state_dict it left in the
+    model, as .npy files; the same arguments give the same files."""
+    import numpy as np
+    outs = []
+    for d in ('a', 'b'):
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--no-cpu-baseline',
+               '--sustain-steps', '0', '--no-roofline', '--dump-outputs', str(tmp_path / d)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        outs.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1]))
+    assert outs[0]['steps'] == 2
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert 'state.generator.linear.module.weight.npy' in files and sorted(os.listdir(tmp_path / 'b')) == files
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 64_000_000
+    got = (float(np.load(tmp_path / 'a' / 'd_loss.npy')), float(np.load(tmp_path / 'a' / 'g_loss.npy')))
+    assert got == tuple(outs[0]['last_losses'])
+    for f in files:
+        x = np.load(tmp_path / 'a' / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, np.load(tmp_path / 'b' / f)), f

@@ -275,3 +275,27 @@ def test_tuning_switches_need_opt_in():
     r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, env=dict(env, MCGEN_TUNING='1'), timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     assert r.stdout.split('\n')[-2] == "False False 7 [('MCGEN_GK', '0'), ('MCGEN_PAIR_D', '0'), ('MCGEN_WGRAD_MAX_SPLITS', '7')]", r.stdout
+
+
+def test_bench_dump_outputs_budget_and_sampling(tmp_path):
+    """bench.py --dump-outputs: one float32 / float64 .npy per array, at most 64 MB together; small arrays are kept whole,
+    oversized ones become a fixed, ascending sample of their elements -- the same files on every call."""
+    import bench
+    bn = torch.nn.BatchNorm1d(4)
+    arrays = bench.step_outputs({'loss': torch.tensor(1.5)}, bn)
+    assert arrays['state.num_batches_tracked'].dtype == np.float64 and arrays['state.weight'].dtype == np.float32
+    arrays['ramp'] = np.arange(12_000_000, dtype=np.float64)
+    arrays['noise'] = np.random.Generator(np.random.PCG64(3)).random((4, 5_000_000), dtype=np.float32)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == sorted(k + '.npy' for k in arrays)
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 64_000_000
+    for f in files:
+        x, y = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    for k in ('loss', 'state.weight', 'state.running_var', 'state.num_batches_tracked'):
+        assert np.array_equal(np.load(tmp_path / 'a' / (k + '.npy')), arrays[k]), k
+    ramp = np.load(tmp_path / 'a' / 'ramp.npy')
+    assert 1_000_000 < ramp.size < 12_000_000 and np.all(np.diff(ramp) > 0) and ramp[-1] < 12_000_000
+    assert 1_000_000 < np.load(tmp_path / 'a' / 'noise.npy').size < 20_000_000
