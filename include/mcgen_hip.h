@@ -608,6 +608,31 @@ int mcgen_cross_entropy(const void* logits, const int64_t* target, float* loss_r
  * x = |e_c|^2 - 2 <f_p, e_c> comes from one fused 1x1 convolution over the codebook */
 int mcgen_argmin_channels(const void* x, int64_t* idx, int dtype, int64_t pixels, int C, int Cp, void* stream);
 
+/* ---- VQ-VAE training (csrc/vq_ops.hip) ----------------------------------------------------------------------------
+ * The training step of VectorQuantization.forward (modules.py:18-43) after the nearest-code search (the fused 1x1
+ * convolution over -2 E^T with bias |E|^2, then mcgen_argmin_channels).  f = fp32 features [pixels, Fp] (D used),
+ * idx = the chosen codes, E = embedding [D, K] BEFORE this step's update.  Deterministic (no float atomics).
+ * mcgen_vq_chunks: the number of statistics slabs for `pixels` (chunks of fixed size). */
+int mcgen_vq_chunks(int64_t pixels);
+/* q[p, :D] = E[:, idx_p] (compute dtype, pitch D), g (optional) = coef * (f - q): the commitment gradient term
+ * (coef = vq_commit * 2 / (pixels * D)); dpart[chunk] = partial sums of (q - f)^2.  train: per-chunk one-hot GEMM
+ * slabs slab[chunk][D][K] = sum of f over the chunk's pixels of code k, cslab[chunk][K] = their counts.
+ * D a multiple of 8 up to 64, K a multiple of 64. */
+int mcgen_vq_stats(const float* feat, const int64_t* idx, const float* embedding, void* q, void* g, float* slab,
+                   float* cslab, float* dpart, float coef, int dtype, int64_t pixels, int D, int Fp, int K, int train,
+                   void* stream);
+/* diff = sum(dpart) / (pixels * D) (device scalar).  train: count_k (optional output) = slab sums in chunk order,
+ * cluster_size <- decay * cluster_size + (1 - decay) * count, n = sum cluster_size,
+ * cs_scratch = (cluster_size + eps) / (n + K eps) * n, embedding_mean <- decay * embedding_mean + (1 - decay) * sum,
+ * embedding = embedding_mean / cs (in place in the module's buffers) */
+int mcgen_vq_update(const float* slab, const float* cslab, const float* dpart, int64_t pixels, int D, int K, float decay,
+                    float one_m_decay, float eps, float* cluster_size, float* embedding_mean, float* embedding,
+                    float* counts, float* cs_scratch, float* diff, int train, void* stream);
+/* VQ-VAE reconstruction term (vqvae.py:97-104): decoded = tanh(x), partials[b] = block sums of (decoded - target)^2,
+ * dx (optional) = gscale * (decoded - target) * (1 - decoded^2); target fp32 in x's NHWC pitch (Cp a multiple of 8) */
+int mcgen_mse_tanh(const void* x, const float* target, void* decoded, void* dx, float* partials, int blocks, float gscale,
+                   int dtype, int64_t pixels, int C, int Cp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,10 @@ SYMBOLS = {
     'mcgen_onehot_rep': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     'mcgen_adam': (_i, [_vp, _vp, _vp, _vp, _i64, _f, _vp, _f, _f, _f, _f, _vp, _vp]),
     'mcgen_sn_fix_pair_adam': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _f, _f, _f, _f, _vp, _i, _vp]),
+    'mcgen_vq_chunks': (_i, [_i64]),
+    'mcgen_vq_stats': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i64, _i, _i, _i, _i, _vp]),
+    'mcgen_vq_update': (_i, [_vp, _vp, _vp, _i64, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    'mcgen_mse_tanh': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _i, _i64, _i, _i, _vp]),
 }
 
 _lib = None

@@ -2,7 +2,8 @@
 (images -> quantised features, commitment MSE, code map) is the step in front of every MCPixelCNN iteration
 (train_pixelcnn.py:111-113) and ``decode_code`` turns sampled code maps back into images (generate.py).
 The auto-encoder is frozen there (``ae.train(False)``): BatchNorm uses running statistics and the codebook is fixed.
-Training the VQ-VAE itself (EMA codebook update, straight-through gradient) is not built."""
+Training the VQ-VAE itself (train_vqvae.py) goes through ``forward`` and ``trainer.VQVAETrainer`` on ``vqvae_engine.py``:
+straight-through gradient, MSE + commitment loss, and the EMA codebook update of the quantiser's buffers."""
 from __future__ import annotations
 
 import torch
@@ -13,7 +14,32 @@ from .. import ops
 from ..config import cfg
 from ..modules import VectorQuantization
 from ..ops import Seg, pad8
+from ..vqvae_engine import VQVAEEngine
 from .utils import init_param
+
+
+class _VQVAEFn(torch.autograd.Function):
+    """One autograd node for the whole model: only the loss carries gradient (train_vqvae.py:106-108)."""
+
+    @staticmethod
+    def forward(ctx, engine, img, holder, *params):
+        tape = []
+        out = engine.forward(img, True, tape, want_grad=True)
+        holder.update(out)
+        ctx.engine, ctx.tape, ctx.params = engine, tape, params
+        return out['loss']
+
+    @staticmethod
+    def backward(ctx, gloss):
+        eng = ctx.engine
+        sink = {}
+        eng._gsink = sink
+        try:
+            eng.backward(ctx.tape)
+        finally:
+            eng._gsink = None
+        ctx.tape = None
+        return (None, None, None) + tuple(sink[id(p)] * gloss if id(p) in sink else None for p in ctx.params)
 
 
 class ResBlock(nn.Module):
@@ -83,7 +109,16 @@ class VQVAE(nn.Module):
 
     def _frozen(self):
         if self.training:
-            raise NotImplementedError('VQVAE: only the frozen (eval-mode) encode / decode_code paths are built')
+            raise NotImplementedError('VQVAE.encode / decode_code are the frozen (eval-mode) paths: training runs through '
+                                      'VQVAE.forward / trainer.VQVAETrainer')
+
+    def _engine(self):
+        eng = self.__dict__.get('_eng')
+        dt = self._dt()
+        if eng is None or eng.dtype != dt:
+            eng = VQVAEEngine(self, dt)
+            self.__dict__['_eng'] = eng
+        return eng
 
     # ---- fused building blocks (eval-mode BatchNorm folded into prologues) -------------------------------------
     def _res(self, blk, x):
@@ -162,7 +197,19 @@ class VQVAE(nn.Module):
             return torch.tanh(ops.to_nchw(x, self.data_shape[0]))
 
     def forward(self, input):
-        raise NotImplementedError('VQVAE.forward (auto-encoder training) is not on the MultimodalController hot path')
+        """{'img' in (-1, 1)} -> {'loss', 'code' [N, W, H], 'img'} (vqvae.py:97-104).  Training mode updates the BatchNorm
+        running statistics and the quantiser's EMA buffers, with or without grad; with grad enabled the loss carries the
+        straight-through gradient of every parameter (``loss.backward()``)."""
+        eng = self._engine()
+        img = input['img']
+        if torch.is_grad_enabled() and self.training:
+            holder = {}
+            params = [p for p in self.parameters() if p.requires_grad]
+            loss = _VQVAEFn.apply(eng, img, holder, *params)
+            return {'loss': loss, 'code': holder['code'], 'img': holder['img']}
+        with torch.no_grad():
+            out = eng.forward(img, self.training)
+        return {'loss': out['loss'], 'code': out['code'], 'img': out['img']}
 
 
 def vqvae():

@@ -92,9 +92,10 @@ class Wrapper(nn.Module):
 
 class VectorQuantization(nn.Module):
     """modules.py:6-46 -- the EMA codebook of the VQ-VAE.  Buffers as in the reference (``embedding`` [D, K],
-    ``cluster_size`` [K], ``embedding_mean`` [D, K]).  The HIP path implements the inference side (nearest code +
-    gather), which is what runs in front of MCPixelCNN (train_pixelcnn.py:111-113); the EMA update of a VQ-VAE
-    training run is not built."""
+    ``cluster_size`` [K], ``embedding_mean`` [D, K]).  ``nearest`` is the inference side (frozen codebook), which is
+    what runs in front of MCPixelCNN (train_pixelcnn.py:111-113).  The training step -- straight-through gradient and
+    the EMA update of these buffers (deterministic, in place) -- runs inside ``VQVAE.forward`` / ``VQVAETrainer``
+    (vqvae_engine.py, ops.vq_step)."""
 
     def __init__(self, embedding_size, num_embedding, decay=0.99, eps=1e-5):
         super().__init__()
@@ -111,7 +112,12 @@ class VectorQuantization(nn.Module):
         """[N, H, W, D] fp32 features -> int64 code indices [N, H, W]: argmin_k |f - e_k|^2 = argmin_k (|e_k|^2 - 2 f.e_k),
         one fused 1x1 convolution over the codebook + the arg-min kernel."""
         if self.training:
-            raise NotImplementedError('VectorQuantization: only the inference path (frozen codebook) is built')
+            raise NotImplementedError('VectorQuantization.nearest is the frozen-codebook path: training runs through '
+                                      'VQVAE.forward / trainer.VQVAETrainer')
+        return self._nearest(feat_nhwc)
+
+    def _nearest(self, feat_nhwc: torch.Tensor) -> torch.Tensor:
+        """`nearest` without the mode check: the training step searches the codebook before updating it."""
         e = self.embedding                                                   # [D, K]
         w = (-2.0 * e.t()).contiguous().reshape(self.num_embedding, self.embedding_size, 1, 1)
         dist, _ = ops.conv_fused([ops.Seg(feat_nhwc, ksize=1)], ops.prep_weight(w, feat_nhwc.dtype), self.num_embedding,

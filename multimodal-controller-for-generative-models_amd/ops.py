@@ -1607,6 +1607,54 @@ def argmin_channels(x: Tensor, c: int) -> Tensor:
     return idx
 
 
+def vq_step(feat: Tensor, idx: Tensor, embedding: Tensor, d: int, dtype: torch.dtype, coef: float = 0.0,
+            want_grad: bool = False, train: bool = False, cluster_size: Optional[Tensor] = None,
+            embedding_mean: Optional[Tensor] = None, decay: float = 0.99, eps: float = 1e-5, want_counts: bool = False):
+    """The training step of VectorQuantization.forward (modules.py:18-43) after the nearest-code search.
+    `feat` fp32 [..., Fp] (first d channels), `idx` int64 [...] the chosen codes, `embedding` [D, K] fp32.
+    -> (q [..., d] in `dtype` = E[:, idx] gathered BEFORE the update, g = coef * (f - q) or None, diff = mean((q - f)^2)
+    as a device scalar, counts [K] fp32 or None).  train: the EMA update of cluster_size / embedding_mean / embedding,
+    in place, deterministic (mcgen_vq_stats + mcgen_vq_update)."""
+    pixels = idx.numel()
+    k = embedding.shape[1]
+    if feat.dtype != torch.float32 or feat.numel() != pixels * feat.shape[-1] or idx.dtype != torch.int64:
+        raise _lib.McgenError('vq_step: fp32 features with one int64 code per pixel expected')
+    lib = _lib.load()
+    chunks = lib.mcgen_vq_chunks(pixels)
+    dev = feat.device
+    q = torch.empty((*idx.shape, d), dtype=dtype, device=dev)
+    g = torch.empty_like(q) if want_grad else None
+    dpart = torch.empty(chunks, dtype=torch.float32, device=dev)
+    slab = torch.empty((chunks, d, k), dtype=torch.float32, device=dev) if train else None
+    cslab = torch.empty((chunks, k), dtype=torch.float32, device=dev) if train else None
+    idx = idx.contiguous()
+    check(lib.mcgen_vq_stats(_f32(feat), idx.data_ptr(), _f32(embedding), _p(q), _p(g), _f32(slab), _f32(cslab), _f32(dpart),
+                             float(coef), _dt(dtype), pixels, d, feat.shape[-1], k, int(train), _stream()), 'vq_stats')
+    diff = torch.empty((), dtype=torch.float32, device=dev)
+    counts = torch.empty(k, dtype=torch.float32, device=dev) if (train and want_counts) else None
+    cs = torch.empty(k, dtype=torch.float32, device=dev) if train else None
+    check(lib.mcgen_vq_update(_f32(slab), _f32(cslab), _f32(dpart), pixels, d, k, float(decay), float(1.0 - decay), float(eps),
+                              _f32(cluster_size) if train else None, _f32(embedding_mean) if train else None,
+                              _f32(embedding) if train else None, _f32(counts), _f32(cs), _f32(diff), int(train), _stream()),
+          'vq_update')
+    return q, g, diff, counts
+
+
+def mse_tanh(x: Tensor, target: Tensor, c: int, gscale: float, want_grad: bool):
+    """-> (decoded = tanh(x), sum of (decoded - target)^2 as a device scalar, dx = gscale * (decoded - target) *
+    (1 - decoded^2) or None).  `target` fp32 in x's NHWC shape."""
+    pixels = x.numel() // x.shape[-1]
+    if target.shape != x.shape or target.dtype != torch.float32:
+        raise _lib.McgenError('mse_tanh: target must be fp32 in x\'s NHWC shape')
+    blocks = max(1, min(1024, (x.numel() // 8 + 255) // 256))
+    part = torch.empty(blocks, dtype=torch.float32, device=x.device)
+    dec = torch.empty_like(x)
+    dx = torch.empty_like(x) if want_grad else None
+    check(_lib.load().mcgen_mse_tanh(_p(x), _f32(target), _p(dec), _p(dx), _f32(part), blocks, float(gscale), _dt(x.dtype), pixels,
+                                     c, x.shape[-1], _stream()), 'mse_tanh')
+    return dec, part.double().sum().float(), dx
+
+
 def prep_weight_ex(w: Tensor, dtype: torch.dtype, ksize: Optional[int] = None, *, kh0: int = 0, kw0: int = 0,
                    transpose: bool = False, row_scale: Optional[Tensor] = None, col_scale: Optional[Tensor] = None,
                    rows_img: Optional[int] = None, k_img: Optional[int] = None, wscale: float = 1.0) -> Tensor:

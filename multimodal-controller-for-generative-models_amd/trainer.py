@@ -780,3 +780,32 @@ class VAETrainer(_FlatTrainer):
         if eps is None:
             eps = torch.randn(img.shape[0], self.model.latent_size, device=img.device)
         return self._eager(img, label, eps)
+
+
+class VQVAETrainer(_FlatTrainer):
+    """train_vqvae.py:99-112 on the HIP path: zero_grad, forward (the quantiser's EMA buffers move as in the reference),
+    backward, clip_grad_norm_(1), Adam(lr 3e-4).  No per-step random input.  The capture warm-up restores the whole
+    state_dict, the codebook buffers (embedding, cluster_size, embedding_mean) included, so capturing does not advance
+    training.  A batch of another size than the captured one (the loader's short final batch) runs the eager step."""
+
+    def __init__(self, model, *a, world_size=1, **k):
+        if world_size > 1:
+            raise ValueError('VQVAETrainer: multi-GPU VQ-VAE training is not supported (per-rank EMA statistics would '
+                             'drift the codebooks apart); run with world_size 1')
+        super().__init__(model, *a, world_size=world_size, **k)
+
+    def _compute(self, img):
+        eng = self.model._engine()
+        self.gflat.zero_()
+        tape = []
+        out = eng.forward(img, True, tape, want_grad=True)
+        eng.backward(tape)
+        return out['loss']
+
+    def capture(self, img, warmup: int = 1):
+        self._capture((img.clone(),), warmup)
+
+    def train_iteration(self, img):
+        if self._graphs and tuple(img.shape) == tuple(self.statics[0].shape):
+            return self._replay(img)
+        return self._eager(img)

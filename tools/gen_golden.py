@@ -685,6 +685,122 @@ def fx_classifier():
 FIXTURES.update(mcgan_full_b128=fx_mcgan_full_b128, mcgan_coil_full=fx_mcgan_coil_full, mcglow_full=fx_mcglow_full,
                 mcpixelcnn_full=fx_mcpixelcnn_full, classifier=fx_classifier)
 
+def _vqvae_steps(model, img, steps, arrays, clip=1.0, lr=3e-4):
+    """train_vqvae.py:99-112 loop body (zero_grad, forward, backward, clip_grad_norm_(1), Adam(lr 3e-4).step()).
+    Step 0 also records the quantiser's input / codebook before its update and the MSE / VQ parts of the loss, every
+    parameter's gradient before clipping and every buffer after the step."""
+    opt = torch.optim.Adam(model.parameters(), lr=lr)
+    seen = {}
+
+    def pre(mod, inp):
+        seen['x'] = inp[0].detach().clone(); seen['emb'] = mod.embedding.clone()
+
+    def post(mod, inp, out):
+        seen['diff'] = out[1].detach().clone()
+    h1 = model.quantizer.register_forward_pre_hook(pre)
+    h2 = model.quantizer.register_forward_hook(post)
+    losses, first = [], None
+    for s in range(steps):
+        opt.zero_grad()
+        out = model({'img': img.clone()})
+        out['loss'].backward()
+        if s == 0:
+            first = dict(out, x=seen['x'], emb=seen['emb'], diff=seen['diff'],
+                         grads={k: p.grad.detach().clone() for k, p in model.named_parameters()})
+        torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
+        opt.step()
+        if s == 0:
+            first['buffers'] = {k: b.detach().clone() for k, b in model.named_buffers()}
+        losses.append(out['loss'].item())
+    h1.remove(); h2.remove()
+    arrays['losses'] = np.array(losses, dtype=np.float64)
+    return first
+
+
+def _vq_margin(x, emb):
+    d = emb.shape[0]
+    flat = x.transpose(1, -1).contiguous().view(-1, d)
+    dist = flat.pow(2).sum(1, keepdim=True) - 2 * flat @ emb + emb.pow(2).sum(0, keepdim=True)
+    top2 = dist.topk(2, dim=1, largest=False).values
+    return (top2[:, 1] - top2[:, 0]).view(*x.transpose(1, -1).shape[:-1])
+
+
+def _set_vqvae_cfg(hidden, d, k):
+    cfg['model_name'] = 'vqvae'; cfg['device'] = 'cpu'; cfg['data_shape'] = [3, 32, 32]
+    cfg['vqvae'] = {'hidden_size': list(hidden), 'num_res_block': 2, 'embedding_size': d, 'num_embedding': k, 'vq_commit': 0.25}
+
+
+def fx_vqvae_train_small():
+    """VQ-VAE training (train_vqvae.py:99-112), reduced: hidden [16, 16], 2 res blocks, D 8, K 64, B 8.  The codebook
+    (embedding = embedding_mean) is spread over the initial training-mode encoder outputs so that many codes are hit.
+    Step 0 in detail (loss parts, code map + arg-min margin, decoded image, gradients before clipping, buffers after),
+    the losses of 3 loop-body steps, the final state and an eval-mode forward on it."""
+    import models
+    _set_vqvae_cfg([16, 16], 8, 64)
+    torch.manual_seed(0)
+    model = models.vqvae(); model.train(True)
+    img, _ = gu.synthetic_batch(8, 10, seed=71)
+    with torch.no_grad():
+        keep = {k: v.clone() for k, v in model.state_dict().items()}
+        flat0 = model.encoder(img).transpose(1, -1).contiguous().view(-1, 8)
+        model.load_state_dict(keep)                     # (undo the BN running-statistics update of that probe)
+        gsel = torch.Generator().manual_seed(72)
+        emb = (flat0[::8] + 0.02 * torch.randn(64, 8, generator=gsel)).t().contiguous()
+        model.quantizer.embedding.copy_(emb); model.quantizer.embedding_mean.copy_(emb)
+    arrays = np_state(model.state_dict(), 'sd/')
+    arrays['img'] = img.numpy()
+    first = _vqvae_steps(model, img, 3, arrays)
+    arrays['loss0'] = np.array(first['loss'].item())
+    arrays['mse0'] = np.array(F.mse_loss(first['img'], img).item())
+    arrays['vq0'] = np.array(first['diff'].item())
+    arrays['code0'] = first['code'].numpy()
+    arrays['dist_margin0'] = _vq_margin(first['x'], first['emb']).numpy()
+    arrays['img0'] = first['img'].detach().numpy()
+    for k, g in first['grads'].items():
+        arrays['grad0/' + k] = g.numpy()
+    for k, b in first['buffers'].items():
+        arrays['buf1/' + k] = b.numpy()
+    arrays.update(np_state(model.state_dict(), 'sd_final/'))
+    model.train(False)
+    with torch.no_grad():
+        out = model({'img': img.clone()})
+    arrays['eval_loss'] = np.array(out['loss'].item())
+    arrays['eval_code'] = out['code'].numpy()
+    save('vqvae_train_small.npz', **arrays)
+
+
+def fx_vqvae_train_full():
+    """The shipped VQ-VAE (hidden [128, 128], D 64, K 512) at B = 128, 2 loop-body steps.  Weights: procedural stand-ins
+    (gu.procedural_state_generic, seed 7301) with the quantiser's reference initialisation (embedding = embedding_mean
+    ~ N(0, 1), stored; cluster_size 0), under which most pixels of the first step pick one code.  Recorded: the losses,
+    the step-0 code histogram, per-parameter gradient norms before clipping, a strided slice of the decoded image and
+    cluster_size / embedding after step 0."""
+    import models
+    _set_vqvae_cfg([128, 128], 64, 512)
+    torch.manual_seed(0)
+    model = models.vqvae(); model.train(True)
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    sd = gu.procedural_state_generic(shapes, seed=7301)
+    emb = torch.randn(64, 512, generator=torch.Generator().manual_seed(7302))
+    sd['quantizer.embedding'] = emb.clone(); sd['quantizer.embedding_mean'] = emb.clone()
+    sd['quantizer.cluster_size'] = torch.zeros(512)
+    model.load_state_dict(sd)
+    arrays = {'q_embedding': emb.numpy()}
+    img, _ = gu.synthetic_batch(128, 10, seed=73)
+    first = _vqvae_steps(model, img, 2, arrays)
+    arrays['hist0'] = torch.bincount(first['code'].flatten(), minlength=512).numpy()
+    names = sorted(first['grads'])
+    arrays['grad_names'] = np.array(names)
+    arrays['grad_norms'] = np.array([first['grads'][k].double().norm().item() for k in names])
+    arrays['img0_sample'] = first['img'].detach().numpy()[:4, :, ::4, ::4].copy()
+    arrays['cluster_size1'] = first['buffers']['quantizer.cluster_size'].numpy()
+    arrays['embedding1'] = first['buffers']['quantizer.embedding'].numpy()
+    arrays['vq0'] = np.array(first['diff'].item())
+    save('vqvae_train_full_digest.npz', **arrays)
+
+
+FIXTURES.update(vqvae_train_small=fx_vqvae_train_small, vqvae_train_full=fx_vqvae_train_full)
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--only', default=None)
