@@ -142,6 +142,7 @@ class FusedSchedule:
 class Driver:
     """One of train_vae.py / train_glow.py / train_pixelcnn.py.  Subclasses set `trainer_cls` and override the hooks."""
     trainer_cls = None
+    pivot_max = False                                     # train_classifier.py:29-30,90-91: Accuracy is maximised
 
     def __init__(self, extra):
         self.extra = extra
@@ -284,7 +285,8 @@ class Driver:
                 save_result = {'cfg': dict(cfg), 'epoch': epoch + 1, 'model_dict': {k: v.detach().cpu() for k, v in model.state_dict().items()},
                                'optimizer_dict': optimizer.state_dict(), 'scheduler_dict': scheduler.state_dict(), 'logger': logger}
                 save(save_result, './output/model/{}_checkpoint.pt'.format(cfg['model_tag']))
-                if cfg['pivot'] > logger.mean[pivot]:
+                better = logger.mean[pivot] > cfg['pivot'] if self.pivot_max else cfg['pivot'] > logger.mean[pivot]
+                if better:
                     cfg['pivot'] = logger.mean[pivot]
                     shutil.copy('./output/model/{}_checkpoint.pt'.format(cfg['model_tag']),
                                 './output/model/{}_best.pt'.format(cfg['model_tag']))

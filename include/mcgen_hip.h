@@ -633,6 +633,22 @@ int mcgen_vq_update(const float* slab, const float* cslab, const float* dpart, i
 int mcgen_mse_tanh(const void* x, const float* target, void* decoded, void* dx, float* partials, int blocks, float gscale,
                    int dtype, int64_t pixels, int C, int Cp, void* stream);
 
+/* ---- classifier training (csrc/classifier_ops.hip) ------------------------------------------------------------------
+ * Backward of y = MaxPool2d(2)(relu(BN_train(x))) (models/classifier.py, one block tail) without an index tensor:
+ * gp = dL/dy [N, Ho, Wo, C], x = the pre-BatchNorm input [N, 2Ho, 2Wo, C] (NHWC, C a multiple of 8), sc / sh the batch
+ * affine of the forward (sc = gamma * rstd, sh = beta - mean * sc), mean / rstd the batch statistics.  Each window's
+ * argmax is recomputed from relu(fma(x, sc, sh)) in fp32 as mcgen_affine_relu_maxpool2 computes it: the FIRST strict
+ * maximum in row-major order takes gp, and only when that maximum is > 0 (dz = 0 elsewhere).
+ * mcgen_maxpool2_bn_bwd_stats: partials[b][0][c] = sum dz, partials[b][1][c] = sum dz * x_hat over block b's windows
+ * (C/8 must divide 256; reduce with mcgen_bn_bwd_finalize). */
+int mcgen_maxpool2_bn_bwd_stats(const void* gp, const void* x, const float* scale, const float* shift, const float* mean,
+                                const float* rstd, float* partials, int blocks, int dtype, int N, int Ho, int Wo, int C,
+                                void* stream);
+/* dx [N, 2Ho, 2Wo, C] = sc * (dz - sums[0] / M - x_hat * sums[1] / M), M = N * 4 * Ho * Wo, sums = [2, C] */
+int mcgen_maxpool2_bn_bwd_apply(const void* gp, const void* x, const float* scale, const float* shift, const float* mean,
+                                const float* rstd, const float* sums, void* dx, int dtype, int N, int Ho, int Wo, int C,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,6 +223,8 @@ SYMBOLS = {
     'mcgen_vq_stats': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i64, _i, _i, _i, _i, _vp]),
     'mcgen_vq_update': (_i, [_vp, _vp, _vp, _i64, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     'mcgen_mse_tanh': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _i, _i64, _i, _i, _vp]),
+    'mcgen_maxpool2_bn_bwd_stats': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'mcgen_maxpool2_bn_bwd_apply': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
 
 _lib = None

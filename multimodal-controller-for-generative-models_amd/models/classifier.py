@@ -6,8 +6,11 @@ Same class / factory name, constructor arguments and child order as the referenc
 it (`model.train(False)`, metrics.py:55,95): the three `Conv -> BatchNorm -> ReLU -> MaxPool2d(2)` stages are one fused
 3x3 convolution each plus `mcgen_affine_relu_maxpool2` (eval-mode BatchNorm folded into an affine), the fourth stage's
 BatchNorm + ReLU ride in one elementwise launch, and the Linear head is a 1x1 launch over the NHWC-flattened map with
-its weight columns permuted from the reference's (c, h, w) flattening.  Training the classifier is the reference's
-`train_classifier.py` and not part of this path: a training-mode forward raises.
+its weight columns permuted from the reference's (c, h, w) flattening.
+
+Training (train_classifier.py:104-113) runs through `forward` in training mode on classifier_engine.py: batch statistics,
+the hand-derived backward behind an autograd bridge when grad is enabled (so the reference loop with torch.optim.Adam
+runs), and trainer.ClassifierTrainer for the fused, graph-replayed step.  `feature()` stays evaluation-only.
 """
 from __future__ import annotations
 
@@ -18,6 +21,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from .._lib import McgenError
+from ..classifier_engine import ClassifierEngine
 from ..config import cfg
 from ..ops import Seg
 from .utils import init_param
@@ -26,6 +30,31 @@ from .utils import init_param
 def loss(input, output):
     """classifier.py:9-11."""
     return F.cross_entropy(output['label'], input['label'], reduction='mean')
+
+
+class _ClassifierFn(torch.autograd.Function):
+    """One autograd node for the whole model: only the loss carries gradient (train_classifier.py:108-109)."""
+
+    @staticmethod
+    def forward(ctx, engine, img, label, holder, *params):
+        tape = []
+        loss, logits = engine.forward(img, label, True, tape, want_grad=True)
+        holder['label'] = logits
+        ctx.engine, ctx.tape = engine, tape
+        ctx.params = params
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        eng = ctx.engine
+        sink = {}
+        eng._gsink = sink
+        try:
+            eng.backward(ctx.tape)
+        finally:
+            eng._gsink = None
+        ctx.tape = None
+        return (None, None, None, None) + tuple(sink[id(p)] * gloss if id(p) in sink else None for p in ctx.params)
 
 
 class Classifier(nn.Module):
@@ -49,11 +78,19 @@ class Classifier(nn.Module):
     def _dt(self):
         return self.__dict__.get('_cdt') or {'float32': torch.float32, 'bfloat16': torch.bfloat16}[cfg.get('compute_dtype', 'float32')]
 
+    def _engine(self):
+        eng = self.__dict__.get('_eng')
+        dt = self._dt()
+        if eng is None or eng.dtype != dt:
+            eng = ClassifierEngine(self, dt)
+            self.__dict__['_eng'] = eng
+        return eng
+
     def _encode(self, x: torch.Tensor) -> torch.Tensor:
         """-> NHWC map of the last stage after BatchNorm + ReLU, [N, h, w, pad8(C)]."""
         if self.training:
-            raise McgenError('Classifier: the fused path is the evaluation-mode feature network of IS / FID (metrics.py:55,95); '
-                             'training it is train_classifier.py in the reference')
+            raise McgenError('Classifier.feature is the evaluation-mode feature network of IS / FID (metrics.py:55,95); '
+                             'training runs through Classifier.forward / trainer.ClassifierTrainer')
         dt = self._dt()
         stages = [m for m in self.blocks if isinstance(m, nn.Conv2d)]
         bns = [m for m in self.blocks if isinstance(m, nn.BatchNorm2d)]
@@ -78,6 +115,18 @@ class Classifier(nn.Module):
         return ops.to_nchw(y, c).reshape(y.shape[0], -1)
 
     def forward(self, input):
+        """{'img', 'label'} -> {'label': logits, 'loss'}.  Training mode runs on batch statistics and updates the BatchNorm
+        running statistics; with grad enabled the loss carries the gradient of every parameter (``loss.backward()``)."""
+        if self.training:
+            eng = self._engine()
+            if torch.is_grad_enabled():
+                holder = {}
+                params = [p for p in self.parameters() if p.requires_grad]
+                ce = _ClassifierFn.apply(eng, input['img'], input['label'], holder, *params)
+                return {'label': holder['label'], 'loss': ce}
+            with torch.no_grad():
+                ce, logits = eng.forward(input['img'], input['label'], True)
+            return {'label': logits, 'loss': ce}
         y = self._encode(input['img'])                        # [N, h, w, Cp]
         n, h, w, cp = y.shape
         c = self.encoded_shape[0]

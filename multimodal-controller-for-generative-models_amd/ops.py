@@ -1573,6 +1573,26 @@ def code_bn_bwd(g: Tensor, code: Optional[Tensor], x: Tensor, scale, mean, rstd,
     return dx
 
 
+def maxpool2_bn_bwd(gp: Tensor, x: Tensor, scale, shift, mean, rstd, dgamma: Tensor, dbeta: Tensor) -> Tensor:
+    """Backward of y = MaxPool2d(2)(relu(x * scale + shift)) through training-mode BatchNorm (the classifier's block tail,
+    forward mcgen_affine_relu_maxpool2 with the batch affine) w.r.t. x [N, 2Ho, 2Wo, C]; fills dgamma / dbeta.  The
+    window argmax is recomputed from x (first strict maximum, ReLU gate), so no index tensor and no full-size dz."""
+    n, h, w, c = x.shape
+    ho, wo = h // 2, w // 2
+    if h % 2 or w % 2 or tuple(gp.shape) != (n, ho, wo, c) or gp.dtype != x.dtype:
+        raise _lib.McgenError(f'maxpool2_bn_bwd: gp must be {(n, ho, wo, c)} {x.dtype}, got {tuple(gp.shape)} {gp.dtype}')
+    blocks = max(1, min(256, (n * ho * wo) // 16))
+    part = torch.empty((blocks, 2, c), dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    check(lib.mcgen_maxpool2_bn_bwd_stats(_p(gp), _p(x), _f32(scale), _f32(shift), _f32(mean), _f32(rstd), _f32(part), blocks,
+                                          _dt(x.dtype), n, ho, wo, c, _stream()), 'maxpool2_bn_bwd_stats')
+    sums = _bwd_sums(part, c, dgamma, dbeta)
+    dx = torch.empty_like(x)
+    check(lib.mcgen_maxpool2_bn_bwd_apply(_p(gp), _p(x), _f32(scale), _f32(shift), _f32(mean), _f32(rstd), _f32(sums), _p(dx),
+                                          _dt(x.dtype), n, ho, wo, c, _stream()), 'maxpool2_bn_bwd_apply')
+    return dx
+
+
 def bce_logits(logits: Tensor, target: Tensor, c: int, gscale: float, want_grad: bool):
     """-> (recon = sigmoid(logits), sum of BCE(recon, target) as a device scalar, dlogits or None)."""
     pixels = logits.numel() // logits.shape[-1]

@@ -809,3 +809,37 @@ class VQVAETrainer(_FlatTrainer):
         if self._graphs and tuple(img.shape) == tuple(self.statics[0].shape):
             return self._replay(img)
         return self._eager(img)
+
+
+class ClassifierTrainer(_FlatTrainer):
+    """train_classifier.py:104-113 on the HIP path: zero_grad, forward in training mode (the BatchNorm running statistics
+    move as in the reference), backward, clip_grad_norm_(1), Adam (lr 1e-2 in the driver).  No per-step random input.
+    The learning rate lives in device memory (FusedAdam), so a MultiStepLR step (`set_lr`) needs no re-capture.  The
+    capture warm-up restores the whole state_dict, the BatchNorm buffers included, so capturing does not advance
+    training.  A batch of another size than the captured one (the loader's short final batch) runs the eager step."""
+
+    def __init__(self, model, *a, world_size=1, **k):
+        if world_size > 1:
+            raise ValueError('ClassifierTrainer: multi-GPU classifier training is not supported (the reference wraps it in '
+                             'nn.DataParallel; the datasets are small); run with world_size 1')
+        super().__init__(model, *a, world_size=world_size, **k)
+        self.logits = None
+
+    def _compute(self, img, label):
+        eng = self.model._engine()
+        self.gflat.zero_()
+        tape = []
+        loss, self.logits = eng.forward(img, label, True, tape, want_grad=True)
+        eng.backward(tape)
+        return loss
+
+    def set_lr(self, lr: float):
+        self.opt.set_lr(lr)
+
+    def capture(self, img, label, warmup: int = 1):
+        self._capture((img.clone(), label.clone()), warmup)
+
+    def train_iteration(self, img, label):
+        if self._graphs and tuple(img.shape) == tuple(self.statics[0].shape):
+            return self._replay(img, label)
+        return self._eager(img, label)

@@ -801,6 +801,125 @@ def fx_vqvae_train_full():
 
 FIXTURES.update(vqvae_train_small=fx_vqvae_train_small, vqvae_train_full=fx_vqvae_train_full)
 
+
+def _set_classifier_cfg(shape, classes):
+    cfg['model_name'] = 'classifier'; cfg['device'] = 'cpu'; cfg['classes_size'] = classes; cfg['data_shape'] = list(shape)
+    cfg['classifier'] = {'hidden_size': [8, 16, 32, 64]}
+
+
+def _classifier_steps(model, img, label, steps, lr=1e-2, clip=1.0):
+    """train_classifier.py:104-113 loop body: zero_grad, training-mode forward, backward, clip_grad_norm_(1), Adam(lr 1e-2,
+    weight_decay 0).step().  -> (losses, logits per step, step-1 gradients before clipping)."""
+    opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=0)
+    model.train(True)
+    losses, logits, grads = [], [], None
+    for s in range(steps):
+        opt.zero_grad()
+        out = model({'img': img.clone(), 'label': label.clone()})
+        out['loss'].backward()
+        if s == 0:
+            grads = {k: p.grad.detach().clone() for k, p in model.named_parameters()}
+        torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
+        opt.step()
+        losses.append(out['loss'].item()); logits.append(out['label'].detach().clone())
+    return losses, logits, grads
+
+
+def _classifier_margin(model, img):
+    """Smallest distance, relative to the per-channel spread, between the two largest ReLU outputs of a max-pool window
+    (the larger one > 0) and of any BatchNorm output from 0, over the fp64 training-mode forward of `img`.  A near-tie
+    or a near-zero there makes the gradient's routing depend on rounding, so the fixtures pick inputs that keep a margin."""
+    convs = [m for m in model.blocks if isinstance(m, torch.nn.Conv2d)]
+    bns = [m for m in model.blocks if isinstance(m, torch.nn.BatchNorm2d)]
+    x, margin = img.double(), float('inf')
+    with torch.no_grad():
+        for i, (conv, bn) in enumerate(zip(convs, bns)):
+            x = F.conv2d(x, conv.weight.double(), conv.bias.double(), padding=1)
+            z = F.batch_norm(x, None, None, bn.weight.double(), bn.bias.double(), training=True, eps=bn.eps)
+            spread = z.std((0, 2, 3), keepdim=True)
+            margin = min(margin, float((z.abs() / spread).min()))
+            x = F.relu(z)
+            if i + 1 < len(convs):
+                n, c, h, w = x.shape
+                win = (x / spread).view(n, c, h // 2, 2, w // 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(n, c, h // 2, w // 2, 4)
+                top = win.topk(2, -1).values
+                live = top[..., 0] > 0
+                if live.any():
+                    margin = min(margin, float((top[..., 0] - top[..., 1])[live].min()))
+                x = F.max_pool2d(x, 2)
+    return margin
+
+
+def _classifier_inputs(model, n, shape, classes, seed, need):
+    """The first input seed from `seed` on whose batch keeps _classifier_margin >= need."""
+    for s in range(seed, seed + 1000):
+        img, label = gu.synthetic_batch(n, classes, seed=s, shape=tuple(shape))
+        if _classifier_margin(model, img) >= need:
+            return s, img, label
+    raise RuntimeError('no input seed with the requested margin')
+
+
+CLASSIFIER_SMALL = (('coil100', [3, 32, 32], 100, 7411), ('gray', [1, 32, 32], 16, 7412))
+
+
+def fx_classifier_train_small():
+    """Classifier training (train_classifier.py:104-113) at B = 16 for 3 steps on both data shapes: COIL100 [3,32,32] with
+    100 classes and Omniglot's [1,32,32] (16 of its 1623 classes keep the file small; the 1623-class head is in the digest).
+    The initial weights (gu.procedural_state_generic, seed 7411 / 7412) and the inputs (gu.synthetic_batch: for the training
+    batch the first seed from seed + 100 on that keeps a routing margin of 3e-6, stored as input_seed; seed + 200 for the
+    feature batch) are regenerated by the tests, so only results are stored: per-step
+    loss and logits, step-1 gradients, the state after step 3 (BatchNorm buffers included; of the head weight every
+    fourth row) and an eval-mode feature() of the feature batch on it."""
+    import models
+    arrays = {}
+    for tag, shape, classes, seed in CLASSIFIER_SMALL:
+        _set_classifier_cfg(shape, classes)
+        torch.manual_seed(0)
+        model = models.classifier()
+        shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+        model.load_state_dict(gu.procedural_state_generic(shapes, seed=seed))
+        iseed, img, label = _classifier_inputs(model, 16, shape, classes, seed + 100, 3e-6)
+        feat_img, _ = gu.synthetic_batch(12, classes, seed=seed + 200, shape=tuple(shape))
+        losses, logits, grads = _classifier_steps(model, img, label, 3)
+        arrays[f'{tag}/input_seed'] = np.array(iseed)
+        arrays[f'{tag}/losses'] = np.array(losses, dtype=np.float64)
+        arrays[f'{tag}/logits'] = torch.stack(logits).numpy()
+        for k, g in grads.items():
+            arrays[f'{tag}/grad1/{k}'] = g.numpy()
+        arrays.update(np_state(model.state_dict(), f'{tag}/sd_final/'))
+        arrays[f'{tag}/sd_final/classifier.weight'] = arrays[f'{tag}/sd_final/classifier.weight'][::4].copy()     # (size)
+        model.train(False)
+        with torch.no_grad():
+            arrays[f'{tag}/feature'] = model.feature({'img': feat_img}).numpy()
+    save('classifier_train_small.npz', **arrays)
+
+
+def fx_classifier_train_full():
+    """B = 128, both data shapes with their full class counts (COIL100 100, Omniglot 1623).  Weights: procedural stand-ins
+    (gu.procedural_state_generic, seed 7401 / 7402); inputs gu.synthetic_batch from seed 83 / 84 on, the first with a
+    routing margin of 2e-6 (_classifier_margin; stored as input_seed).  Recorded: per-parameter
+    norms and sums of the step-1 gradients (before clipping) and the losses of 2 loop-body steps."""
+    import models
+    arrays = {}
+    for tag, shape, classes, seed in (('coil100', [3, 32, 32], 100, 7401), ('omniglot', [1, 32, 32], 1623, 7402)):
+        _set_classifier_cfg(shape, classes)
+        torch.manual_seed(0)
+        model = models.classifier()
+        shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+        model.load_state_dict(gu.procedural_state_generic(shapes, seed=seed))
+        iseed, img, label = _classifier_inputs(model, 128, shape, classes, seed - 7318, 2e-6)
+        losses, _, grads = _classifier_steps(model, img, label, 2)
+        arrays[f'{tag}/input_seed'] = np.array(iseed)
+        names = sorted(grads)
+        arrays[f'{tag}/grad_names'] = np.array(names)
+        arrays[f'{tag}/grad_norms'] = np.array([grads[k].double().norm().item() for k in names])
+        arrays[f'{tag}/grad_sums'] = np.array([grads[k].double().sum().item() for k in names])
+        arrays[f'{tag}/losses'] = np.array(losses, dtype=np.float64)
+    save('classifier_train_full_digest.npz', **arrays)
+
+
+FIXTURES.update(classifier_train_small=fx_classifier_train_small, classifier_train_full=fx_classifier_train_full)
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--only', default=None)
