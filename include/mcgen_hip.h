@@ -649,6 +649,24 @@ int mcgen_maxpool2_bn_bwd_apply(const void* gp, const void* x, const float* scal
                                 const float* rstd, const float* sums, void* dx, int dtype, int N, int Ho, int Wo, int C,
                                 void* stream);
 
+/* ---- MCPixelCNN incremental sampling (csrc/pixelcnn_sample.hip) ----------------------------------------------------
+ * Eval-mode ancestral sampling of MCGatedPixelCNN (models/mcpixelcnn.py:47-61, 85-112) that computes every pixel of every
+ * layer once.  Per call: for each row i, mcgen_px_sample_row(i) (vertical stacks, gate_v, vert_to_horiz of row i), then
+ * mcgen_px_sample_col(i, j) for j = 0 .. W-1 (horizontal path, head, fp32 softmax and the draw, written into codes).
+ * emb [Kq][C] and the weight pack `w` (mcgen_px_sample_weight_elems elements) are in the compute dtype, `p` (fp32) holds
+ * biases and eval BatchNorm affines, `mc` the MultimodalController rows [L][3][N][C] + [N][Hd]; the layout is spelled out
+ * in the source.  Workspace: ov [L][N][2][W][C] (compute dtype), v2h [L][N][W][2C] fp32, xh [L][N][W][C] (compute
+ * dtype).  uniform [H*W][N]: the draw is the smallest k with sum_{m<=k} e_m > u * sum_m e_m, e_m = exp(logit_m - max)
+ * (greedy: the first argmax).  logits (optional) [N][H][W][Kq] fp32.  C and Hd multiples of 8. */
+typedef struct {
+    int64_t* codes; const void* emb; const void* w; const float* p; const float* mc;
+    void* ov; float* v2h; void* xh; const float* uniform; float* logits;
+    int32_t N, H, W, C, L, Kq, Hd, greedy;
+} mcgen_px_sample_t;
+int64_t mcgen_px_sample_weight_elems(int C, int L, int Hd, int Kq);
+int mcgen_px_sample_row(const mcgen_px_sample_t* p, int i, int dtype, void* stream);
+int mcgen_px_sample_col(const mcgen_px_sample_t* p, int i, int j, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

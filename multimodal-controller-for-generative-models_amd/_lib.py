@@ -75,6 +75,13 @@ class Gated(C.Structure):                                  # mcgen_gated_t
                 ('N', C.c_int32), ('HW', C.c_int32), ('C', C.c_int32), ('_pad', C.c_int32)]
 
 
+class PxSample(C.Structure):                               # mcgen_px_sample_t
+    _fields_ = [('codes', C.c_void_p), ('emb', C.c_void_p), ('w', C.c_void_p), ('p', C.c_void_p), ('mc', C.c_void_p),
+                ('ov', C.c_void_p), ('v2h', C.c_void_p), ('xh', C.c_void_p), ('uniform', C.c_void_p), ('logits', C.c_void_p),
+                ('N', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('C', C.c_int32), ('L', C.c_int32), ('Kq', C.c_int32),
+                ('Hd', C.c_int32), ('greedy', C.c_int32)]
+
+
 class Code(C.Structure):
     _fields_ = [('codebook', C.c_void_p), ('out_off', C.c_int64), ('M', C.c_int32), ('C', C.c_int32),
                 ('scale_idx', C.c_int32), ('_pad', C.c_int32)]
@@ -225,6 +232,9 @@ SYMBOLS = {
     'mcgen_mse_tanh': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _i, _i64, _i, _i, _vp]),
     'mcgen_maxpool2_bn_bwd_stats': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'mcgen_maxpool2_bn_bwd_apply': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'mcgen_px_sample_weight_elems': (_i64, [_i, _i, _i, _i]),
+    'mcgen_px_sample_row': (_i, [C.POINTER(PxSample), _i, _i, _vp]),
+    'mcgen_px_sample_col': (_i, [C.POINTER(PxSample), _i, _i, _i, _vp]),
 }
 
 _lib = None

@@ -139,6 +139,21 @@ class MCGatedPixelCNN(nn.Module):
                     inp['img'][:, i, j].copy_(sampler(probs))
         return inp['img']
 
+    def sample(self, C, x=None, uniform=None, greedy=False, return_logits=False):
+        """Eval-mode ancestral sampling with the contract of `generate`, computing every pixel of every layer once
+        (pixelcnn_sampler.py): x [N, H, W] int64 (zeros [N, 8, 8] by default) is overwritten in place and returned; its prior
+        contents are never read.  uniform [H*W, N] fp32 drives the inverse-CDF draw (torch.rand on the device by default);
+        greedy takes the first argmax.  return_logits: -> (x, logits [N, K, H, W] fp32 at each position as drawn)."""
+        from .. import pixelcnn_sampler
+        pixelcnn_sampler.validate(self, C)
+        if x is None:
+            x = torch.zeros((C.size(0), 8, 8), dtype=torch.long, device=cfg['device'])
+        dt = {'float32': torch.float32, 'bfloat16': torch.bfloat16}[cfg.get('compute_dtype', 'float32')]
+        dt = self.__dict__.get('_cdt') or dt
+        with torch.no_grad():
+            x, logits = pixelcnn_sampler.sample(self, C, x, dt, uniform=uniform, greedy=greedy, return_logits=return_logits)
+        return (x, logits) if return_logits else x
+
 
 def mcpixelcnn():
     p = cfg['pixelcnn']

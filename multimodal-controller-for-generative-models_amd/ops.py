@@ -1731,3 +1731,14 @@ def prep_weight_ex_many(jobs, dtype: torch.dtype):
         keep += [w, rs, cs]
     check(_lib.load().mcgen_prep_weight_ex_batch(arr, len(jobs), _dt(dtype), _stream()), 'prep_weight_ex_batch')
     return outs
+
+
+# ---- MCPixelCNN incremental sampling (pixelcnn_sampler.py) ------------------------------------------------------------
+def px_sample_row(P: '_lib.PxSample', i: int, dtype: torch.dtype):
+    """Row launch i: vertical stacks, gate_v and vert_to_horiz of row i for every layer (mcgen_px_sample_row)."""
+    check(_lib.load().mcgen_px_sample_row(C.byref(P), i, _dt(dtype), _stream()), 'px_sample_row')
+
+
+def px_sample_col(P: '_lib.PxSample', i: int, j: int, dtype: torch.dtype):
+    """Column launch (i, j): horizontal path, head, softmax and draw of position (i, j) (mcgen_px_sample_col)."""
+    check(_lib.load().mcgen_px_sample_col(C.byref(P), i, j, _dt(dtype), _stream()), 'px_sample_col')
