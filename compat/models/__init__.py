@@ -1,7 +1,7 @@
 """Drop-in for the reference's src/models/__init__.py: `import models; models.mcgan()` (train_gan.py:3,76) builds
 the MI355X module trees -- same factories, class names and state_dict keys (models/mcgan.py, mcvae.py, mcglow.py,
-mcpixelcnn.py, vqvae.py, utils.py).  The non-MC baselines (cgan, cvae, cglow, cpixelcnn) carry no
-MultimodalController op and stay the reference's own files."""
+mcpixelcnn.py, vqvae.py, utils.py) and the CGAN baseline (cgan.py: `cgan` / `CGAN` only, its block classes share
+MCGAN's names).  The other non-MC baselines (cvae, cglow, cpixelcnn) stay the reference's own files."""
 import os as _os
 import sys as _sys
 
@@ -19,3 +19,4 @@ from mcgen_amd.models.mcpixelcnn import mcpixelcnn  # noqa: F401,E402
 from mcgen_amd.models.mcvae import mcvae  # noqa: F401,E402
 from mcgen_amd.models.vqvae import vqvae  # noqa: F401,E402
 from mcgen_amd.models.classifier import classifier, Classifier  # noqa: F401,E402
+from mcgen_amd.models.cgan import cgan, CGAN  # noqa: F401,E402

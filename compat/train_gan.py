@@ -20,6 +20,7 @@ What differs, and why:
 """
 import argparse
 import os
+import shutil
 import sys
 import time
 
@@ -52,9 +53,25 @@ def parse():
     for k in list(a):
         if k in cfg or k == 'control_name':
             cfg[k] = a[k]
-    if cfg.get('control_name'):                              # train_gan.py:26-27
+    if cfg.get('control_name') == 'None':                    # train_gan.py:26-27: the baselines take no control
+        cfg['control'] = {}
+        cfg['control_name'] = ''
+    elif cfg.get('control_name'):
         cfg['control'] = {'controller_rate': cfg['control_name'].split('_')[0]}
     return extra
+
+
+def model_tag(seed):
+    """<seed>_<data>_<subset>_<model>[_<control>] (train_gan.py:57-59; empty parts dropped)."""
+    control = cfg.get('control_name') or cfg['control'].get('controller_rate', '')
+    return '_'.join(x for x in [str(seed), cfg['data_name'], cfg['subset'], cfg['model_name'], control] if x)
+
+
+def make_model():
+    """models.<model_name>() for the GANs this driver trains (train_gan.py:76)."""
+    if cfg['model_name'] not in ('mcgan', 'cgan'):
+        raise ValueError('Not valid model name')
+    return getattr(models, cfg['model_name'])()
 
 
 def make_optimizer(model, lr, betas):                        # train_gan.py:222-236 (Adam branch)
@@ -141,15 +158,14 @@ def run():
     seed = int(cfg['init_seed'])
     torch.manual_seed(seed); torch.cuda.manual_seed(seed)    # train_gan.py:54-55
     cfg['iter'] = {'generator': 1, 'discriminator': 5}       # train_gan.py:30-31
-    cfg['model_tag'] = '_'.join([str(seed), cfg['data_name'], cfg['subset'], cfg['model_name'],
-                                 cfg.get('control_name') or cfg['control']['controller_rate']])
+    cfg['model_tag'] = model_tag(seed)
     print(f'Experiment: {cfg["model_tag"]}')
     data_shim._SYNTHETIC['train'] = extra['synthetic_size']
     dataset = fetch_dataset(cfg['data_name'], cfg['subset'])                   # train_gan.py:71-73
     process_dataset(dataset['train'])
     loader = make_data_loader(dataset)['train']
     loader.drop_last = True
-    model = models.mcgan().to(cfg['device'])
+    model = make_model().to(cfg['device'])
     if cfg.get('compute_dtype') == 'bfloat16':
         model.set_compute_dtype(torch.bfloat16)
     if world > 1:
@@ -203,6 +219,10 @@ def run():
         logger.safe(False)
         if rank == 0:
             save(make_checkpoint(model, optimizer, epoch + 1, cfg, scheduler=scheduler, logger=logger), path)   # train_gan.py:111-119
+            if cfg['model_name'] == 'cgan':
+                # train_gan.py:120-123 copies the checkpoint to _best.pt when the pivot metric improves; the stand-in metric
+                # has no pivot, so the baseline's latest checkpoint is its best (what compat/generate.py reads)
+                shutil.copy(path, path[:-len('_checkpoint.pt')] + '_best.pt')
         logger.reset()
     logger.safe(False)
     if world > 1:

@@ -667,6 +667,35 @@ int64_t mcgen_px_sample_weight_elems(int C, int L, int Hd, int Kq);
 int mcgen_px_sample_row(const mcgen_px_sample_t* p, int i, int dtype, void* stream);
 int mcgen_px_sample_col(const mcgen_px_sample_t* p, int i, int j, int dtype, void* stream);
 
+/* ---- CGAN label embedding (csrc/cgan_ops.hip) ------------------------------------------------------------------------
+ * The reference's CGAN (models/cgan.py) concatenates a label embedding W[:, label] (W = embedding.weight [E, M] fp32,
+ * one-hot indicator) to the generator's latent and, spectrally normalised and broadcast over the image, to the
+ * discriminator's input.  int64 labels; a label outside [0, M) gives a zero embedding row and no gradient.
+ * Every reduction is fixed-order with no float atomics (bit-identical reruns).
+ * mcgen_cgan_gen_input: out [N, Cp] (compute dtype) = [z (L) | W[:, label_n] (E) | 0]: the Linear's input rows. */
+int mcgen_cgan_gen_input(const float* z, const float* w, const int64_t* label, void* out, int dtype, int N, int L, int E, int M,
+                         int Cp, void* stream);
+/* out [N, HW, Cp] = [img (Cimg of pitch Cpi) | W[:, label_n] / sigma[0] (E) | 0]: the discriminator's input image */
+int mcgen_cgan_dis_input(const void* img, const float* w, const float* sigma, const int64_t* label, void* out, int dtype, int N,
+                         int HW, int Cimg, int Cpi, int E, int M, int Cp, void* stream);
+/* dW [E, M] (+)= sum over n ascending with label_n == m of dE[n, :] (dE fp32, row pitch ld); absent modes get exactly 0 */
+int mcgen_cgan_embed_bwd(const float* dE, int ld, const int64_t* label, float* dW, int N, int E, int M, int accumulate, void* stream);
+/* dE [N, E] fp32 = W_lin[:, col0 : col0 + E]^T . dlin[n]; dlin [N, 16 * C0] in the compute dtype with column p * C0 + c holding
+ * Linear output row c * 16 + p (the generator's 4x4 map, row_perm 16); W_lin fp32 [16 * C0, in_features].  E divides 256. */
+int mcgen_cgan_lin_dembed(const void* dlin, const float* w, float* dE, int dtype, int N, int C0, int in_features, int col0, int E,
+                          void* stream);
+/* part [N, H, 3, C] fp32: per image row, the sums of dc1 [N, H, W, Cp] over the first column, the interior columns and the
+ * last column (H, W >= 2) */
+int mcgen_cgan_dis_window_sums(const void* dc1, float* part, int dtype, int N, int H, int W, int C, int Cp, void* stream);
+/* de [N, E] fp32: the embedding's input gradient through the FirstDisResBlock, from `part` (mcgen_cgan_dis_window_sums of
+ * conv1's output gradient) and dy [N, HWq, Cpq] (the block's output gradient, pooled map):
+ *   de[n][e] = sum_tap sum_co W1[co][Cimg + e][tap] / sigma1 * S_n[tap][co] + sum_co Wsc[co][Cimg + e] / sigma_sc * sum_q dy[n][q][co]
+ * S_n[tap] = the sum of conv1's output gradient over the pixels where the tap reads inside the image.  W1 fp32 [C, Cin, 3, 3],
+ * Wsc fp32 [C, Cin, 1, 1] (weight_orig), sigma1 / sigma_sc device scalars.  E divides 256; C <= 1024. */
+int mcgen_cgan_dis_dembed(const float* part, const void* dy, const float* w1, const float* wsc, const float* sigma1,
+                          const float* sigma_sc, float* de, int dtype, int N, int H, int C, int Cin, int Cimg, int E, int HWq,
+                          int Cpq, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -235,6 +235,12 @@ SYMBOLS = {
     'mcgen_px_sample_weight_elems': (_i64, [_i, _i, _i, _i]),
     'mcgen_px_sample_row': (_i, [C.POINTER(PxSample), _i, _i, _vp]),
     'mcgen_px_sample_col': (_i, [C.POINTER(PxSample), _i, _i, _i, _vp]),
+    'mcgen_cgan_gen_input': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'mcgen_cgan_dis_input': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'mcgen_cgan_embed_bwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'mcgen_cgan_lin_dembed': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'mcgen_cgan_dis_window_sums': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'mcgen_cgan_dis_dembed': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
 }
 
 _lib = None

@@ -5,3 +5,4 @@ from .mcpixelcnn import mcpixelcnn, MCGatedPixelCNN  # noqa: F401
 from .mcvae import mcvae, MCVAE  # noqa: F401
 from .vqvae import vqvae, VQVAE  # noqa: F401
 from .classifier import classifier, Classifier  # noqa: F401
+from .cgan import cgan, CGAN  # noqa: F401

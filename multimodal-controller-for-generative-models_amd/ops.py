@@ -1742,3 +1742,68 @@ def px_sample_row(P: '_lib.PxSample', i: int, dtype: torch.dtype):
 def px_sample_col(P: '_lib.PxSample', i: int, j: int, dtype: torch.dtype):
     """Column launch (i, j): horizontal path, head, softmax and draw of position (i, j) (mcgen_px_sample_col)."""
     check(_lib.load().mcgen_px_sample_col(C.byref(P), i, j, _dt(dtype), _stream()), 'px_sample_col')
+
+
+# ---- CGAN label embedding (cgan_engine.py) ------------------------------------------------------------------------------
+def _labels64(label: Tensor) -> Tensor:
+    if label.dtype != torch.int64 or label.dim() != 1:
+        raise _lib.McgenError(f'labels must be a 1-d int64 tensor, got {label.dtype} {tuple(label.shape)}')
+    return label.contiguous()
+
+
+def cgan_gen_input(z: Tensor, w: Tensor, label: Tensor, dtype: torch.dtype) -> Tensor:
+    """[N, 1, 1, pad8(L + E)] in `dtype`: the generator Linear's input rows z (+) W[:, label] (cgan.py:57-59), w = [E, M]."""
+    n, lat = z.shape
+    e, m = w.shape
+    cp = pad8(lat + e)
+    out = torch.empty((n, 1, 1, cp), dtype=dtype, device=z.device)
+    check(_lib.load().mcgen_cgan_gen_input(_f32(z.contiguous()), _f32(w), _p(_labels64(label)), _p(out), _dt(dtype), n, lat, e, m,
+                                           cp, _stream()), 'cgan_gen_input')
+    return out
+
+
+def cgan_dis_input(img: Tensor, cimg: int, w: Tensor, sigma: Tensor, label: Tensor) -> Tensor:
+    """[N, H, W, pad8(cimg + E)] in img's dtype: the image (NHWC, `cimg` true channels) (+) (W / sigma)[:, label] broadcast
+    over the pixels (cgan.py:166-169)."""
+    n, h, wd, cpi = img.shape
+    e, m = w.shape
+    cp = pad8(cimg + e)
+    out = torch.empty((n, h, wd, cp), dtype=img.dtype, device=img.device)
+    check(_lib.load().mcgen_cgan_dis_input(_p(img), _f32(w), _f32(sigma), _p(_labels64(label)), _p(out), _dt(img.dtype), n, h * wd,
+                                           cimg, cpi, e, m, cp, _stream()), 'cgan_dis_input')
+    return out
+
+
+def cgan_embed_bwd(de: Tensor, label: Tensor, dw: Tensor, accumulate: bool = False):
+    """dw [E, M] (+)= sum over samples n with label_n == m of de[n] (ascending n; absent modes 0)."""
+    n, e = de.shape
+    m = dw.shape[1]
+    check(_lib.load().mcgen_cgan_embed_bwd(_f32(de), de.stride(0), _p(_labels64(label)), _f32(dw), n, e, m, int(accumulate),
+                                           _stream()), 'cgan_embed_bwd')
+
+
+def cgan_lin_dembed(dlin: Tensor, w_lin: Tensor, col0: int, e: int) -> Tensor:
+    """[N, E] fp32: the Linear's input gradient at columns col0 .. col0 + E from its output gradient dlin ([N, 4, 4, C0], the
+    generator's row_perm-16 layout) and the fp32 master weight [16 C0, in_features]."""
+    n = dlin.shape[0]
+    c0 = dlin.shape[-1]
+    out = torch.empty((n, e), dtype=torch.float32, device=dlin.device)
+    check(_lib.load().mcgen_cgan_lin_dembed(_p(dlin), _f32(w_lin), _f32(out), _dt(dlin.dtype), n, c0, w_lin.shape[1], col0, e,
+                                            _stream()), 'cgan_lin_dembed')
+    return out
+
+
+def cgan_dis_dembed(dc1: Tensor, c: int, dy: Tensor, w1: Tensor, wsc: Tensor, sigma1: Tensor, sigma_sc: Tensor, cimg: int,
+                    e: int) -> Tensor:
+    """[N, E] fp32: the discriminator embedding's input gradient through the FirstDisResBlock from conv1's output gradient
+    dc1 [N, H, W, Cp] (per-image window sums) and the block's output gradient dy [N, H/2, W/2, Cp'] (the shortcut's sum);
+    w1 / wsc the fp32 weight_orig of conv1 / the 1x1 shortcut, sigma1 / sigma_sc their device sigmas.  Two launches."""
+    n, h, wd, cp = dc1.shape
+    part = torch.empty((n, h, 3, c), dtype=torch.float32, device=dc1.device)
+    check(_lib.load().mcgen_cgan_dis_window_sums(_p(dc1), _f32(part), _dt(dc1.dtype), n, h, wd, c, cp, _stream()),
+          'cgan_dis_window_sums')
+    out = torch.empty((n, e), dtype=torch.float32, device=dc1.device)
+    check(_lib.load().mcgen_cgan_dis_dembed(_f32(part), _p(dy), _f32(w1), _f32(wsc), _f32(sigma1), _f32(sigma_sc), _f32(out),
+                                            _dt(dy.dtype), n, h, c, w1.shape[1], cimg, e, dy.shape[1] * dy.shape[2], dy.shape[-1],
+                                            _stream()), 'cgan_dis_dembed')
+    return out

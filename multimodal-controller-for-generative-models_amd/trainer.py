@@ -156,6 +156,10 @@ class GANTrainer:
         self.grad_d = torch.zeros_like(self.deng.flat_p.flat)
         self.group, self.world = dist_group, world_size
         self.latent = model.latent_size
+        # CGAN (models/cgan.py): labels go to the engines' embedding kernels; no codes, no paired D pass (see _cgan_iteration)
+        self._cgan = bool(getattr(model, 'label_embedding', False))
+        if self._cgan and world_size > 1:
+            raise ValueError('CGAN training runs on one GPU: its gradients are not bucketed for a data-parallel exchange')
 
     # ---- data-parallel gradient exchange: two buckets per network, started under the backward pass -------------
     # The engines' backward passes hand out each network's flat gradient in two contiguous buckets: the LATE layers
@@ -360,6 +364,8 @@ class GANTrainer:
         (parity runs); drawn on the device when None.  Returns (D_loss, G_loss) device scalars of the
         last D and G update, as the reference logs them (train_gan.py:177)."""
         self.model.train(True)
+        if self._cgan:
+            return self._cgan_iteration(img, label, zs)
         n = img.shape[0]
         zi = iter(zs) if zs is not None else None
         draw = (lambda: next(zi)) if zi is not None else (lambda: torch.randn(n, self.latent, device=img.device))
@@ -381,6 +387,56 @@ class GANTrainer:
         for _ in range(self.g_iters):
             g_loss = self.g_update(ind, draw())
         return d_loss, g_loss
+
+
+    # ---- CGAN: the same loop body on label-embedding engines (cgan_engine.py) ---------------------------------------
+    # D(real) and D(fake) are two passes, each with its own power iteration, as in the reference (MCGAN's paired pass folds
+    # the sigma ratio into its MultimodalController codes, which CGAN does not have); the d_iters generator forwards still
+    # run as one grouped pass with per-group BatchNorm statistics.
+    def _cgan_fakes(self, label_rep, z_cat, groups: int) -> Nhwc:
+        fake, _ = self.geng.forward(z_cat, None, True, groups=groups, nhwc=True, label=label_rep)
+        return fake
+
+    def _cgan_d_compute(self, real: Nhwc, fake: Nhwc, label):
+        d_real, ctx_r = self.deng.forward(real, None, True, label=label)
+        d_fake, ctx_f = self.deng.forward(fake, None, True, label=label)
+        self.loss_d, dreal, dfake = ops.hinge_d(d_real.view(-1), d_fake.view(-1))
+        # (the fake pass first: its transposed weight images are the current ones; the sum is the same either way)
+        self.deng.backward(ctx_f, dfake, self.grad_d, False, False)
+        self.deng.backward(ctx_r, dreal, self.grad_d, True, False)
+
+    def _cgan_g_compute(self, label, z):
+        fake, gctx = self.geng.forward(z, None, True, nhwc=True, label=label)
+        d_fake, dctx = self.deng.forward(fake, None, True, tail_loss='g' if _FUSE_TAIL else None, label=label)
+        self.loss_g, dfake = ops.hinge_g(d_fake.view(-1))
+        if 'tail' in dctx:
+            dfake = dctx['tail'][0]
+        dimg = self.deng.backward(dctx, dfake, None, False, True)
+        self.geng.backward(gctx, dimg, self.grad_g, False)
+
+    def _cgan_real(self, img):
+        c = img.shape[1]
+        return Nhwc(ops.to_nhwc(img.detach().contiguous(), self.deng.dtype), c)
+
+    def _cgan_iteration(self, img, label, zs=None):
+        n = img.shape[0]
+        zi = iter(zs) if zs is not None else None
+        draw = (lambda: next(zi)) if zi is not None else (lambda: torch.randn(n, self.latent, device=img.device))
+        fg = self.fake_groups(n)
+        label_rep = label.repeat(fg) if fg > 1 else label
+        real = self._cgan_real(img)
+        fakes = None
+        for k in range(self.d_iters):
+            if k % fg == 0:
+                z_cat = torch.cat([draw() for _ in range(fg)]) if fg > 1 else draw()
+                fakes = self._cgan_fakes(label_rep, z_cat, fg)
+            j = k % fg
+            self._cgan_d_compute(real, Nhwc(fakes.t[j * n:(j + 1) * n], fakes.c), label)
+            self.d_apply()
+        for _ in range(self.g_iters):
+            self._cgan_g_compute(label, draw())
+            self.g_apply()
+        return self.loss_d, self.loss_g
 
 
 class GraphedGANTrainer(GANTrainer):
@@ -442,7 +498,56 @@ class GraphedGANTrainer(GANTrainer):
             _bump(t)
         self.geng.refresh_images(force=True)          # G's weight images follow its parameters (D's are rebuilt per pass)
 
+    def _capture_cgan(self, img: torch.Tensor, label: torch.Tensor, warmup: int = 1):
+        """The CGAN loop body as ONE graph (single rank), behind the latent-draw graph, as the MCGAN one-graph form."""
+        n = img.shape[0]
+        dev = img.device
+        fg = self.fake_groups(n)
+        self._fg = fg
+        passes = (self.d_iters + fg - 1) // fg                  # generator passes of the D updates, fg latent batches each
+        self._cgan_zd = passes * fg
+        self.s_img = img.clone()
+        self.s_label = label.clone()
+        self.s_zall = torch.randn((passes * fg + self.g_iters) * n, self.latent, device=dev)
+        self.s_zd, self.s_z = self.s_zall[:passes * fg * n], self.s_zall[passes * fg * n:]
+        self.model.train(True)
+
+        def body():
+            label_rep = self.s_label.repeat(fg) if fg > 1 else self.s_label
+            real = self._cgan_real(self.s_img)
+            fakes = None
+            for k in range(self.d_iters):
+                if k % fg == 0:
+                    fakes = self._cgan_fakes(label_rep, self.s_zd[k * n:(k + fg) * n], fg)
+                j = k % fg
+                self._cgan_d_compute(real, Nhwc(fakes.t[j * n:(j + 1) * n], fakes.c), self.s_label)
+                self.d_apply()
+            for i in range(self.g_iters):
+                self._cgan_g_compute(self.s_label, self.s_z[i * n:(i + 1) * n])
+                self.g_apply()
+
+        snap = self._snapshot()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):
+                body()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self._restore(snap)
+        torch.cuda.synchronize()
+        G = torch.cuda.CUDAGraph
+        self.g_draw, self.g_all = G(), G()
+        with torch.cuda.graph(self.g_all, capture_error_mode=_CAPTURE_MODE):
+            body()
+        with torch.cuda.graph(self.g_draw, pool=self.g_all.pool(), capture_error_mode=_CAPTURE_MODE):
+            self.s_zall.normal_()
+        self._graphs = True
+        self._hyper_key = (self.opt_g.hyper(), self.opt_d.hyper())
+
     def capture(self, img: torch.Tensor, label: torch.Tensor, warmup: int = 1):
+        if self._cgan:
+            return self._capture_cgan(img, label, warmup)
         n = img.shape[0]
         dev = img.device
         fg = self.fake_groups(n)
@@ -566,6 +671,13 @@ class GraphedGANTrainer(GANTrainer):
         self.s_label.copy_(label, non_blocking=True)
         n, fg = img.shape[0], self._fg
         zi = iter(zs) if zs is not None else None
+        if self._cgan:
+            if zi is None:
+                self.g_draw.replay()
+            else:
+                self.s_zall.copy_(torch.cat([next(zi) for _ in range(self._cgan_zd + self.g_iters)]), non_blocking=True)
+            self.g_all.replay()
+            return self.loss_d, self.loss_g
         if self.g_all is not None:
             if zi is None:
                 self.g_draw.replay()

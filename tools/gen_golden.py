@@ -920,6 +920,108 @@ def fx_classifier_train_full():
 
 FIXTURES.update(classifier_train_small=fx_classifier_train_small, classifier_train_full=fx_classifier_train_full)
 
+
+# ---- CGAN (models/cgan.py): the conditional baseline, label embeddings instead of MultimodalControllers ---------------
+def _set_cgan_cfg(g_hidden, d_hidden, classes, data_name='CIFAR10', channels=3):
+    set_gan_cfg(g_hidden, d_hidden, classes, data_name)
+    cfg['model_name'] = 'cgan'
+    cfg['data_shape'] = [channels, 32, 32]
+
+
+def _cgan_layout(shapes):
+    """The reference's state_dict layout as one string array: 'key:d0xd1x...' per entry, in state_dict order."""
+    return np.array([f"{k}:{'x'.join(str(d) for d in shp)}" for k, shp in shapes.items()])
+
+
+def _cgan_small(name, data_name, channels, classes, iters, full_final=True):
+    """Reduced-width CGAN on procedural weights (gu.procedural_state_generic over the reference's own state_dict layout,
+    which is stored), `iters` train iterations at B=8: per-iteration losses, probes, the eval-mode generated batch and
+    the state after training -- as its difference from the initial state (float16 for the >= 2-d weights, whose
+    differences are a few Adam steps; float32 otherwise), or (`full_final` False) as digests only."""
+    import models
+    _set_cgan_cfg([32] * 4, [16] * 4, classes, data_name, channels)
+    torch.manual_seed(0)
+    model = models.cgan()
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    seed = 4321
+    sd0 = gu.procedural_state_generic(shapes, seed=seed)
+    model.load_state_dict(sd0)
+    model.train(True)
+    arrays = {'layout': _cgan_layout(shapes), 'sd_seed': np.array(seed)}
+    B = 8
+    img, lab = gu.synthetic_batch(B, classes, seed=1, shape=(channels, 32, 32))
+    if classes > B:
+        lab[1] = lab[0]                                      # a repeated label among mostly distinct ones
+    zs = gu.latent_batches(6 * iters + 1, B, 128, seed=2)
+    arrays['img'] = img.numpy(); arrays['label'] = lab.numpy()
+    arrays['z'] = torch.stack(zs).numpy()
+    arrays['probe_generated'] = model.generate(lab, zs[-1]).detach().numpy()
+    arrays['probe_d_real'] = model.discriminate(img, lab).detach().numpy()
+    model.load_state_dict(sd0)
+    opt = make_opt(model)
+    losses = []
+    for it in range(iters):
+        losses.append(ref_train_iteration(model, opt, img, lab, zs[6 * it:6 * it + 6]))
+    arrays['losses'] = np.array(losses, dtype=np.float64)
+    fin = model.state_dict()
+    for k, v in fin.items():
+        if not v.is_floating_point():
+            arrays['sd_final_int/' + k] = v.numpy().copy()
+        elif full_final:
+            dv = (v - sd0[k]).detach().numpy()
+            arrays['sd_delta/' + k] = dv.astype(np.float16) if v.dim() >= 2 else dv
+        else:
+            arrays['digest/' + k] = gu.checksum(v)
+    model.train(False)
+    with torch.no_grad():
+        arrays['final_generated_eval'] = model.generate(lab, zs[-1]).numpy()
+        arrays['final_d_eval'] = model.discriminate(img, lab).numpy()
+    save(name, **arrays)
+
+
+def fx_cgan_small():
+    _cgan_small('cgan_small.npz', 'CIFAR10', 3, 10, 2)
+
+
+def fx_cgan_omniglot_small():
+    _cgan_small('cgan_omniglot_small.npz', 'Omniglot', 1, 1623, 1, full_final=False)
+
+
+def fx_cgan_full():
+    """The CIFAR10 CGAN (utils.py:156-162 sizes) at batch 128 with procedural weights: probes, one train iteration's
+    losses and digests of the state after it."""
+    import models
+    g_hidden, d_hidden = [256] * 4, [128] * 4
+    _set_cgan_cfg(g_hidden, d_hidden, 10)
+    torch.manual_seed(0)
+    model = models.cgan()
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    sd = gu.procedural_state_generic(shapes, seed=1234)
+    model.load_state_dict(sd)
+    model.train(True)
+    B = 128
+    img, lab = gu.synthetic_batch(B, 10, seed=1)
+    zs = gu.latent_batches(6, B, 128, seed=2)
+    arrays = {'sd_seed': np.array(1234)}
+    gen0 = model.generate(lab, zs[0])
+    d0 = model.discriminate(img, lab)
+    arrays['probe_generated_digest'] = gu.checksum(gen0)
+    arrays['probe_generated'] = gen0.detach().numpy()[:16, :, ::4, ::4].copy()
+    arrays['probe_d_real'] = d0.detach().numpy()
+    model.load_state_dict(sd)
+    opt = make_opt(model)
+    arrays['losses'] = np.array([ref_train_iteration(model, opt, img, lab, zs)], dtype=np.float64)
+    fin = model.state_dict()
+    for k in ['generator.embedding.weight', 'generator.linear.weight', 'generator.blocks.2.conv.6.weight',
+              'generator.blocks.3.running_var', 'discriminator.embedding.weight_orig', 'discriminator.embedding.weight_u',
+              'discriminator.blocks.0.conv.0.weight_orig', 'discriminator.blocks.1.conv.3.weight_orig',
+              'discriminator.blocks.6.weight_orig']:
+        arrays['digest/' + k] = gu.checksum(fin[k])
+    save('cgan_full_digest.npz', **arrays)
+
+
+FIXTURES.update(cgan_small=fx_cgan_small, cgan_omniglot_small=fx_cgan_omniglot_small, cgan_full=fx_cgan_full)
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--only', default=None)
