@@ -1,7 +1,8 @@
 """Drop-in for the reference's src/models/__init__.py: `import models; models.mcgan()` (train_gan.py:3,76) builds
 the MI355X module trees -- same factories, class names and state_dict keys (models/mcgan.py, mcvae.py, mcglow.py,
-mcpixelcnn.py, vqvae.py, utils.py) and the CGAN baseline (cgan.py: `cgan` / `CGAN` only, its block classes share
-MCGAN's names).  The other non-MC baselines (cvae, cglow, cpixelcnn) stay the reference's own files."""
+mcpixelcnn.py, vqvae.py, utils.py) and the CGAN and CPixelCNN baselines (cgan.py: `cgan` / `CGAN` only, its block classes
+share MCGAN's names; cpixelcnn.py: `cpixelcnn` and its classes).  The other non-MC baselines (cvae, cglow) stay the
+reference's own files."""
 import os as _os
 import sys as _sys
 
@@ -20,3 +21,5 @@ from mcgen_amd.models.mcvae import mcvae  # noqa: F401,E402
 from mcgen_amd.models.vqvae import vqvae  # noqa: F401,E402
 from mcgen_amd.models.classifier import classifier, Classifier  # noqa: F401,E402
 from mcgen_amd.models.cgan import cgan, CGAN  # noqa: F401,E402
+from mcgen_amd.models.cpixelcnn import (cpixelcnn, ConditionalGatedPixelCNN, ConditionalGatedMaskedConv2d,  # noqa: F401,E402
+                                        GatedActivation)

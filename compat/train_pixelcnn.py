@@ -4,7 +4,8 @@ frozen auto-encoder in front of the model -- `ae = models.<ae_name>()`, weights 
 through `utils.resume(ae, ae_tag, load_tag='best')` (train_pixelcnn.py:44-45,58-59), `ae.encode(img)` under no_grad
 turning every batch into its code map before the step (:111-113,146-147); pivot NLL, metrics Loss + NLL (:29-31).
 Shared parts and the differences from the reference: compat/_single.py.  (With no trained VQ-VAE checkpoint the
-reference prints 'Not exists model tag' and trains on the codes of a randomly initialised encoder; so does this.)"""
+reference prints 'Not exists model tag' and trains on the codes of a randomly initialised encoder; so does this.)
+--model_name mcpixelcnn or cpixelcnn (the conditional baseline, models/cpixelcnn.py; with --control_name None)."""
 import torch
 
 import models
@@ -34,9 +35,20 @@ class PixelCNNDriver(Driver):
         return self.tr.train_iteration(input['img'], input['label'])
 
 
+MODELS = ('mcpixelcnn', 'cpixelcnn')
+
+
+def apply_control():
+    """train_pixelcnn.py:24-27: --control_name None gives the baseline an empty control (tag <seed>_<data>_<subset>_cpixelcnn);
+    any other control name keeps the MC form parse() gave it."""
+    if cfg.get('control_name') == 'None':
+        cfg['control'], cfg['control_name'] = {}, ''
+
+
 def main():
     extra = parse({'pivot_metric': 'NLL', 'metric_name': {'train': ['Loss', 'NLL'], 'test': ['Loss', 'NLL']}})
-    if cfg['model_name'] != 'mcpixelcnn':
+    apply_control()
+    if cfg['model_name'] not in MODELS:
         raise ValueError('Not valid model name')
     PixelCNNDriver(extra).main()
 

@@ -696,6 +696,46 @@ int mcgen_cgan_dis_dembed(const float* part, const void* dy, const float* w1, co
                           const float* sigma_sc, float* de, int dtype, int N, int H, int C, int Cin, int Cimg, int E, int HWq,
                           int Cpq, void* stream);
 
+/* ---- CPixelCNN conditional gates (csrc/cpixelcnn_ops.hip) -------------------------------------------------------------
+ * ConditionalGatedMaskedConv2d (models/cpixelcnn.py) adds e_n = E[label_n] to both gate inputs: E = class_cond_embedding.weight
+ * [M][2C] fp32, label int64 [N], s [N, HW, 2C] in the compute dtype (h_vert, or vert_to_horiz + horiz_stack), stored WITHOUT
+ * the row.  A gathered label is clamped into [0, M); mcgen_cpx_embed_bwd skips a label outside it.  Every reduction is
+ * fixed-order with no float atomics.  One job per gate, up to MCGEN_CGATE_MAX gates per launch (blockIdx.y = gate). */
+#define MCGEN_CGATE_MAX 4
+typedef struct {
+    const void* s; const float* table; const int64_t* label;
+    const float* scale; const float* shift; void* out;    /* mcgen_cpx_gated_fwd */
+    float* partials;                                      /* mcgen_cpx_gate_stats: [blocks][2][C] */
+    int32_t N, HW, C, M, blocks, _pad;
+} mcgen_cgate_t;
+/* partials[b][0][c] / [b][1][c] = sum / sum of squares of a = s[:, c] + e_n[c] (c < C) over block b's pixel range (the
+ * layout mcgen_bn_finalize / mcgen_bn_finalize_batch read, pitch C, fold 1); C/8 divides 256 */
+int mcgen_cpx_gate_stats(const mcgen_cgate_t* jobs, int n, int dtype, void* stream);
+/* out [N, HW, C] = relu((s[:, :C] + e[:C]) * scale + shift) * sigmoid(s[:, C:] + e[C:]) (cpixelcnn.py:8-18, 50-56) */
+int mcgen_cpx_gated_fwd(const mcgen_cgate_t* jobs, int n, int dtype, void* stream);
+/* backward pass 1: ds = [dz | db] as mcgen_gated_bwd_stats with code 1, x = s + e; partials [blocks][2][C] of (dz, dz * xhat) */
+int mcgen_cpx_gated_bwd_stats(const void* s, const float* table, const int64_t* label, int M, const float* scale,
+                              const float* shift, const float* mean, const float* rstd, const void* g, void* ds,
+                              float* partials, int blocks, int dtype, int N, int HW, int C, void* stream);
+/* backward pass 2 (in place on ds[:, :C]), one workgroup per image: da = scale * (dz - (sums[0] + xhat * sums[1]) / count),
+ * and dsum [N][2C] fp32 = the per-image channel sums of the finished ds (pixels ascending) */
+int mcgen_cpx_gated_bwd_apply(void* ds, const void* s, const float* table, const int64_t* label, int M, const float* sums,
+                              const float* scale, const float* mean, const float* rstd, double count, float* dsum,
+                              int dtype, int N, int HW, int C, void* stream);
+/* dE [M][C2] = sum over n ascending with label_n == m of (dsum_v[n] + dsum_h[n]); dsum_v may be NULL; absent modes get 0 */
+int mcgen_cpx_embed_bwd(const float* dsum_v, const float* dsum_h, const int64_t* label, float* dE, int N, int C2, int M, void* stream);
+/* dE [K][C] fp32 = sum over pixels p ascending with codes[p] == k of dx[p][:C] (dx [P][Cp] in the compute dtype): the code
+ * embedding's gradient in a fixed order; a code outside [0, K) contributes nothing; C <= 256 */
+int mcgen_cpx_code_embed_bwd(const void* dx, int Cp, const int64_t* codes, float* dE, int64_t P, int K, int C, int dtype,
+                             void* stream);
+/* out [L][N][C2] = tables [L][M][C2] at row clamp(label_n): the sampler's per-sample rows */
+int mcgen_cpx_gather_rows(const float* tables, const int64_t* label, float* out, int L, int N, int C2, int M, void* stream);
+/* Incremental sampling of ConditionalGatedPixelCNN: mcgen_px_sample_row / _col with `mc` holding the per-sample rows
+ * [L][N][2C] (mcgen_cpx_gather_rows) that are added to h_vert before gate_v and to the sum s before gate_h; no controller
+ * multiplies anywhere (the weight pack and `p` keep the MCPixelCNN layout). */
+int mcgen_cpx_sample_row(const mcgen_px_sample_t* p, int i, int dtype, void* stream);
+int mcgen_cpx_sample_col(const mcgen_px_sample_t* p, int i, int j, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

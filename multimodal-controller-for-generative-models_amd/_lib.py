@@ -82,6 +82,12 @@ class PxSample(C.Structure):                               # mcgen_px_sample_t
                 ('Hd', C.c_int32), ('greedy', C.c_int32)]
 
 
+class CGate(C.Structure):                                  # mcgen_cgate_t
+    _fields_ = [('s', C.c_void_p), ('table', C.c_void_p), ('label', C.c_void_p), ('scale', C.c_void_p), ('shift', C.c_void_p),
+                ('out', C.c_void_p), ('partials', C.c_void_p), ('N', C.c_int32), ('HW', C.c_int32), ('C', C.c_int32),
+                ('M', C.c_int32), ('blocks', C.c_int32), ('_pad', C.c_int32)]
+
+
 class Code(C.Structure):
     _fields_ = [('codebook', C.c_void_p), ('out_off', C.c_int64), ('M', C.c_int32), ('C', C.c_int32),
                 ('scale_idx', C.c_int32), ('_pad', C.c_int32)]
@@ -241,6 +247,15 @@ SYMBOLS = {
     'mcgen_cgan_lin_dembed': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'mcgen_cgan_dis_window_sums': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'mcgen_cgan_dis_dembed': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'mcgen_cpx_gate_stats': (_i, [C.POINTER(CGate), _i, _i, _vp]),
+    'mcgen_cpx_gated_fwd': (_i, [C.POINTER(CGate), _i, _i, _vp]),
+    'mcgen_cpx_gated_bwd_stats': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'mcgen_cpx_gated_bwd_apply': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _d, _vp, _i, _i, _i, _i, _vp]),
+    'mcgen_cpx_embed_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'mcgen_cpx_gather_rows': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'mcgen_cpx_code_embed_bwd': (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    'mcgen_cpx_sample_row': (_i, [C.POINTER(PxSample), _i, _i, _vp]),
+    'mcgen_cpx_sample_col': (_i, [C.POINTER(PxSample), _i, _i, _i, _vp]),
 }
 
 _lib = None

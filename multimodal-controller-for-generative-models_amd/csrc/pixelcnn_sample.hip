@@ -129,7 +129,9 @@ struct RowLds {
     }
 };
 
-template <typename T>
+// COND: ConditionalGatedPixelCNN (models/cpixelcnn.py): P.mc holds per-sample rows [L][N][2C] added to both gate inputs, and
+// nothing is multiplied by a controller row
+template <typename T, bool COND = false>
 __global__ __launch_bounds__(PX_THREADS) void px_row_kernel(const mcgen_px_sample_t P, int i) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int C = P.C, C2 = 2 * C, W = P.W, H = P.H, N = P.N, L = P.L;
@@ -190,7 +192,12 @@ __global__ __launch_bounds__(PX_THREADS) void px_row_kernel(const mcgen_px_sampl
                 const int c = e % C, m = e / C, s = m / W, j = m % W, n = n0 + s;
                 float o = 0.f, prev = 0.f;
                 if (n < N) {
-                    o = gate(f(hv[(size_t)m * ldh + c]), f(hv[(size_t)m * ldh + C + c]), scv[c], shv[c], code_v[(size_t)n * C + c]);
+                    if (COND) {
+                        const float* row = P.mc + ((size_t)l * N + n) * C2;
+                        o = gate(f(hv[(size_t)m * ldh + c]) + row[c], f(hv[(size_t)m * ldh + C + c]) + row[C + c], scv[c], shv[c], 1.f);
+                    } else {
+                        o = gate(f(hv[(size_t)m * ldh + c]), f(hv[(size_t)m * ldh + C + c]), scv[c], shv[c], code_v[(size_t)n * C + c]);
+                    }
                     const T ot = rnd<T>(o);
                     ov[((((size_t)l * N + n) * 2 + par) * W + j) * C + c] = ot;
                     o = f(ot);
@@ -221,7 +228,7 @@ struct ColLds {
     }
 };
 
-template <typename T>
+template <typename T, bool COND = false>
 __global__ __launch_bounds__(PX_THREADS) void px_col_kernel(const mcgen_px_sample_t P, int i, int j) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int C = P.C, C2 = 2 * C, W = P.W, H = P.H, N = P.N, L = P.L, Hd = P.Hd, Kq = P.Kq;
@@ -273,8 +280,15 @@ __global__ __launch_bounds__(PX_THREADS) void px_col_kernel(const mcgen_px_sampl
         __syncthreads();
         for (int e = tid; e < 16 * C; e += PX_THREADS) {
             const int c = e % C, m = e / C, n = n0 + m;
-            const float o = n < N ? gate(f(sv[(size_t)m * lay.lds_ + c]), f(sv[(size_t)m * lay.lds_ + C + c]), sch[c], shh[c],
-                                         code_h[(size_t)n * C + c]) : 0.f;
+            float o = 0.f;
+            if (n < N) {
+                if (COND) {
+                    const float* row = P.mc + ((size_t)l * N + n) * C2;
+                    o = gate(f(sv[(size_t)m * lay.lds_ + c]) + row[c], f(sv[(size_t)m * lay.lds_ + C + c]) + row[C + c], sch[c], shh[c], 1.f);
+                } else {
+                    o = gate(f(sv[(size_t)m * lay.lds_ + c]), f(sv[(size_t)m * lay.lds_ + C + c]), sch[c], shh[c], code_h[(size_t)n * C + c]);
+                }
+            }
             oh[(size_t)m * lay.ldo + c] = rnd<T>(o);
         }
         __syncthreads();
@@ -287,7 +301,8 @@ __global__ __launch_bounds__(PX_THREADS) void px_col_kernel(const mcgen_px_sampl
             float x = 0.f;
             if (n < N) {
                 const float r = f(rnd<T>(a + br[col]));
-                x = fmaf(r, scr[col], shr[col]) * code_r[(size_t)n * C + col];
+                x = fmaf(r, scr[col], shr[col]);
+                if (!COND) x *= code_r[(size_t)n * C + col];
                 if (l > 0) x += f(xc[(size_t)m * C + col]);
             }
             const T xt = rnd<T>(x);
@@ -306,7 +321,7 @@ __global__ __launch_bounds__(PX_THREADS) void px_col_kernel(const mcgen_px_sampl
         if (col >= Hd) return;
         const int n = n0 + m;
         const float h = f(rnd<T>(a + b0[col]));
-        zz[(size_t)m * lay.ldz + col] = rnd<T>(n < N ? fmaxf(fmaf(h, sc0[col], sh0[col]), 0.f) * code0[(size_t)n * Hd + col] : 0.f);
+        zz[(size_t)m * lay.ldz + col] = rnd<T>(n < N ? fmaxf(fmaf(h, sc0[col], sh0[col]), 0.f) * (COND ? 1.f : code0[(size_t)n * Hd + col]) : 0.f);
     });
     __syncthreads();
     gemm<T>(M, r16(Kq), r32(Hd), wts + g.w4(), [&](int m, int k) -> V {
@@ -369,30 +384,50 @@ extern "C" int64_t mcgen_px_sample_weight_elems(int C, int L, int Hd, int Kq) {
     return (int64_t)(g.w4() + (size_t)r16(Kq) * r32(Hd));
 }
 
-extern "C" int mcgen_px_sample_row(const mcgen_px_sample_t* p, int i, int dtype, void* stream) {
+namespace {
+template <bool COND>
+int launch_row(const mcgen_px_sample_t* p, int i, int dtype, void* stream, const char* what) {
     if (int rc = px_check(p, dtype)) return rc;
-    MCGEN_CHECK(i >= 0 && i < p->H, "px_sample_row: row %d outside [0, %d)", i, p->H);
+    MCGEN_CHECK(i >= 0 && i < p->H, "%s: row %d outside [0, %d)", what, i, p->H);
     const RowLds lay(p->W, p->C, dtype ? 2 : 4);
-    MCGEN_CHECK(lay.bytes <= (size_t)PX_LDS_MAX, "px_sample_row: %zu bytes of LDS for W %d C %d", lay.bytes, p->W, p->C);
-    const void* k = dtype ? reinterpret_cast<const void*>(px_row_kernel<bf16_t>) : reinterpret_cast<const void*>(px_row_kernel<float>);
+    MCGEN_CHECK(lay.bytes <= (size_t)PX_LDS_MAX, "%s: %zu bytes of LDS for W %d C %d", what, lay.bytes, p->W, p->C);
+    const void* k = dtype ? reinterpret_cast<const void*>(px_row_kernel<bf16_t, COND>) : reinterpret_cast<const void*>(px_row_kernel<float, COND>);
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.bytes);
-    MCGEN_CHECK(e == hipSuccess, "px_sample_row: LDS attribute: %s", hipGetErrorString(e));
+    MCGEN_CHECK(e == hipSuccess, "%s: LDS attribute: %s", what, hipGetErrorString(e));
     const dim3 grid((p->N + lay.SR - 1) / lay.SR);
-    if (dtype) hipLaunchKernelGGL(px_row_kernel<bf16_t>, grid, dim3(PX_THREADS), lay.bytes, STREAM(stream), *p, i);
-    else hipLaunchKernelGGL(px_row_kernel<float>, grid, dim3(PX_THREADS), lay.bytes, STREAM(stream), *p, i);
-    MCGEN_LAUNCH_CHECK("px_sample_row"); return 0;
+    if (dtype) hipLaunchKernelGGL((px_row_kernel<bf16_t, COND>), grid, dim3(PX_THREADS), lay.bytes, STREAM(stream), *p, i);
+    else hipLaunchKernelGGL((px_row_kernel<float, COND>), grid, dim3(PX_THREADS), lay.bytes, STREAM(stream), *p, i);
+    MCGEN_LAUNCH_CHECK(what); return 0;
+}
+
+template <bool COND>
+int launch_col(const mcgen_px_sample_t* p, int i, int j, int dtype, void* stream, const char* what) {
+    if (int rc = px_check(p, dtype)) return rc;
+    MCGEN_CHECK(i >= 0 && i < p->H && j >= 0 && j < p->W && p->uniform, "%s: bad position (%d, %d) or no uniforms", what, i, j);
+    const ColLds lay(p->C, p->Hd, p->Kq, dtype ? 2 : 4);
+    MCGEN_CHECK(lay.bytes <= (size_t)PX_LDS_MAX, "%s: %zu bytes of LDS for C %d Hd %d Kq %d", what, lay.bytes, p->C, p->Hd, p->Kq);
+    const void* k = dtype ? reinterpret_cast<const void*>(px_col_kernel<bf16_t, COND>) : reinterpret_cast<const void*>(px_col_kernel<float, COND>);
+    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.bytes);
+    MCGEN_CHECK(e == hipSuccess, "%s: LDS attribute: %s", what, hipGetErrorString(e));
+    const dim3 grid((p->N + 15) / 16);
+    if (dtype) hipLaunchKernelGGL((px_col_kernel<bf16_t, COND>), grid, dim3(PX_THREADS), lay.bytes, STREAM(stream), *p, i, j);
+    else hipLaunchKernelGGL((px_col_kernel<float, COND>), grid, dim3(PX_THREADS), lay.bytes, STREAM(stream), *p, i, j);
+    MCGEN_LAUNCH_CHECK(what); return 0;
+}
+}  // namespace
+
+extern "C" int mcgen_px_sample_row(const mcgen_px_sample_t* p, int i, int dtype, void* stream) {
+    return launch_row<false>(p, i, dtype, stream, "px_sample_row");
 }
 
 extern "C" int mcgen_px_sample_col(const mcgen_px_sample_t* p, int i, int j, int dtype, void* stream) {
-    if (int rc = px_check(p, dtype)) return rc;
-    MCGEN_CHECK(i >= 0 && i < p->H && j >= 0 && j < p->W && p->uniform, "px_sample_col: bad position (%d, %d) or no uniforms", i, j);
-    const ColLds lay(p->C, p->Hd, p->Kq, dtype ? 2 : 4);
-    MCGEN_CHECK(lay.bytes <= (size_t)PX_LDS_MAX, "px_sample_col: %zu bytes of LDS for C %d Hd %d Kq %d", lay.bytes, p->C, p->Hd, p->Kq);
-    const void* k = dtype ? reinterpret_cast<const void*>(px_col_kernel<bf16_t>) : reinterpret_cast<const void*>(px_col_kernel<float>);
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.bytes);
-    MCGEN_CHECK(e == hipSuccess, "px_sample_col: LDS attribute: %s", hipGetErrorString(e));
-    const dim3 grid((p->N + 15) / 16);
-    if (dtype) hipLaunchKernelGGL(px_col_kernel<bf16_t>, grid, dim3(PX_THREADS), lay.bytes, STREAM(stream), *p, i, j);
-    else hipLaunchKernelGGL(px_col_kernel<float>, grid, dim3(PX_THREADS), lay.bytes, STREAM(stream), *p, i, j);
-    MCGEN_LAUNCH_CHECK("px_sample_col"); return 0;
+    return launch_col<false>(p, i, j, dtype, stream, "px_sample_col");
+}
+
+extern "C" int mcgen_cpx_sample_row(const mcgen_px_sample_t* p, int i, int dtype, void* stream) {
+    return launch_row<true>(p, i, dtype, stream, "cpx_sample_row");
+}
+
+extern "C" int mcgen_cpx_sample_col(const mcgen_px_sample_t* p, int i, int j, int dtype, void* stream) {
+    return launch_col<true>(p, i, j, dtype, stream, "cpx_sample_col");
 }

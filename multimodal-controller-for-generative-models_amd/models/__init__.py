@@ -6,3 +6,4 @@ from .mcvae import mcvae, MCVAE  # noqa: F401
 from .vqvae import vqvae, VQVAE  # noqa: F401
 from .classifier import classifier, Classifier  # noqa: F401
 from .cgan import cgan, CGAN  # noqa: F401
+from .cpixelcnn import cpixelcnn, ConditionalGatedPixelCNN  # noqa: F401

@@ -1807,3 +1807,100 @@ def cgan_dis_dembed(dc1: Tensor, c: int, dy: Tensor, w1: Tensor, wsc: Tensor, si
                                             _dt(dy.dtype), n, h, c, w1.shape[1], cimg, e, dy.shape[1] * dy.shape[2], dy.shape[-1],
                                             _stream()), 'cgan_dis_dembed')
     return out
+
+
+# ---- CPixelCNN conditional gates (cpixelcnn_engine.py) -------------------------------------------------------------------
+def _cgate_jobs(items, fwd: bool):
+    arr = (_lib.CGate * len(items))()
+    outs = []
+    for d, it in zip(arr, items):
+        s, table, label = it[:3]
+        n, h, w, c2 = s.shape
+        m = table.shape[0]
+        if table.dtype != torch.float32 or tuple(table.shape) != (m, c2) or not table.is_contiguous():
+            raise _lib.McgenError(f'cpx gate: the embedding table must be contiguous fp32 [M, {c2}], got {table.dtype} {tuple(table.shape)}')
+        d.s, d.table, d.label = _p(s), _p(table), _p(_labels64(label))
+        d.N, d.HW, d.C, d.M = n, h * w, c2 // 2, m
+        if fwd:
+            out = torch.empty((n, h, w, c2 // 2), dtype=s.dtype, device=s.device)
+            d.scale, d.shift, d.out = _f32(it[3]), _f32(it[4]), _p(out)
+        else:
+            blocks = max(1, min(256, (n * h * w) // 16))
+            out = torch.empty((blocks, 2, c2 // 2), dtype=torch.float32, device=s.device)
+            d.partials, d.blocks = _p(out), blocks
+        outs.append(out)
+    return arr, outs
+
+
+def cpx_gate_stats(items):
+    """items = [(s [N, H, W, 2C], table fp32 [M, 2C], label int64 [N])] -> [partials [blocks, 2, C]]: the BatchNorm sums of
+    s[..., :C] + table[label] per gate, in the layout bn_finalize / bn_finalize_batch read (mcgen_cpx_gate_stats, one launch)."""
+    arr, outs = _cgate_jobs(items, False)
+    check(_lib.load().mcgen_cpx_gate_stats(arr, len(items), _dt(items[0][0].dtype), _stream()), 'cpx_gate_stats')
+    return outs
+
+
+def cpx_gated_fwd(items):
+    """items = [(s, table, label, scale, shift)] -> [relu((a + e_a) * scale + shift) * sigmoid(b + e_b)], one launch."""
+    arr, outs = _cgate_jobs(items, True)
+    check(_lib.load().mcgen_cpx_gated_fwd(arr, len(items), _dt(items[0][0].dtype), _stream()), 'cpx_gated_fwd')
+    return outs
+
+
+def cpx_gated_bwd(s: Tensor, table: Tensor, label: Tensor, scale, shift, mean, rstd, g: Tensor, dgamma: Tensor, dbeta: Tensor):
+    """Backward of cpx_gated_fwd through the batch statistics -> (ds [.., 2C], per-image channel sums of ds [N, 2C] fp32);
+    fills dgamma / dbeta."""
+    n, h, w, c2 = s.shape
+    c = c2 // 2
+    pixels = n * h * w
+    blocks = max(1, min(256, pixels // 16))
+    lab = _labels64(label)
+    ds = torch.empty_like(s)
+    part = torch.empty((blocks, 2, c), dtype=torch.float32, device=s.device)
+    dsum = torch.empty((n, c2), dtype=torch.float32, device=s.device)
+    lib = _lib.load()
+    check(lib.mcgen_cpx_gated_bwd_stats(_p(s), _f32(table), _p(lab), table.shape[0], _f32(scale), _f32(shift), _f32(mean), _f32(rstd),
+                                        _p(g), _p(ds), _f32(part), blocks, _dt(s.dtype), n, h * w, c, _stream()), 'cpx_gated_bwd_stats')
+    sums = _bwd_sums(part, c, dgamma, dbeta)
+    check(lib.mcgen_cpx_gated_bwd_apply(_p(ds), _p(s), _f32(table), _p(lab), table.shape[0], _f32(sums), _f32(scale), _f32(mean),
+                                        _f32(rstd), float(pixels), _f32(dsum), _dt(s.dtype), n, h * w, c, _stream()),
+          'cpx_gated_bwd_apply')
+    return ds, dsum
+
+
+def cpx_embed_bwd(dsum_v: Optional[Tensor], dsum_h: Tensor, label: Tensor, de: Tensor):
+    """de [M, 2C] = sum over samples n with label_n == m of dsum_v[n] + dsum_h[n] (ascending n; absent modes 0)."""
+    n, c2 = dsum_h.shape
+    check(_lib.load().mcgen_cpx_embed_bwd(_f32(dsum_v), _f32(dsum_h), _p(_labels64(label)), _f32(de), n, c2, de.shape[0], _stream()),
+          'cpx_embed_bwd')
+
+
+def cpx_code_embed_bwd(dx: Tensor, codes: Tensor, de: Tensor):
+    """de [K, C] = sum over pixels (ascending) with codes == k of dx[..., :C]: the code embedding's gradient, fixed order
+    (mcgen_cpx_code_embed_bwd).  dx [N, H, W, Cp] in the compute dtype, codes int64 [N, H, W]."""
+    cp = dx.shape[-1]
+    k, c = de.shape
+    if codes.dtype != torch.int64 or codes.numel() * cp != dx.numel():
+        raise _lib.McgenError('cpx_code_embed_bwd: int64 codes, one per pixel of dx')
+    check(_lib.load().mcgen_cpx_code_embed_bwd(_p(dx), cp, _p(codes.contiguous()), _f32(de), codes.numel(), k, c, _dt(dx.dtype),
+                                               _stream()), 'cpx_code_embed_bwd')
+
+
+def cpx_gather_rows(tables: Tensor, label: Tensor) -> Tensor:
+    """tables fp32 [L, M, 2C] -> [L, N, 2C]: each layer's row of each sample's (clamped) label."""
+    nl, m, c2 = tables.shape
+    n = label.numel()
+    out = torch.empty((nl, n, c2), dtype=torch.float32, device=tables.device)
+    check(_lib.load().mcgen_cpx_gather_rows(_f32(tables.contiguous()), _p(_labels64(label)), _f32(out), nl, n, c2, m, _stream()),
+          'cpx_gather_rows')
+    return out
+
+
+def cpx_sample_row(P: '_lib.PxSample', i: int, dtype: torch.dtype):
+    """px_sample_row for ConditionalGatedPixelCNN: P.mc holds the per-sample rows [L][N][2C] (mcgen_cpx_sample_row)."""
+    check(_lib.load().mcgen_cpx_sample_row(C.byref(P), i, _dt(dtype), _stream()), 'cpx_sample_row')
+
+
+def cpx_sample_col(P: '_lib.PxSample', i: int, j: int, dtype: torch.dtype):
+    """px_sample_col for ConditionalGatedPixelCNN (mcgen_cpx_sample_col)."""
+    check(_lib.load().mcgen_cpx_sample_col(C.byref(P), i, j, _dt(dtype), _stream()), 'cpx_sample_col')

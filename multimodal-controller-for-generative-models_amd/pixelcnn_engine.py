@@ -28,6 +28,11 @@ _PAIR_GATES = _flag('MCGEN_PAIR_GATES', '1') != '0'      # a layer's two gates: 
 Tensor = torch.Tensor
 
 
+def _unwrap(mod):
+    """The module inside a reference `Wrapper` (MCPixelCNN), or the module itself (CPixelCNN has no wrappers)."""
+    return getattr(mod, 'module', mod)
+
+
 def _t1x1(w: Tensor) -> Tensor:
     """[Cout, Cin(,1,1)] -> transposed 1x1 master weight [Cin, Cout, 1, 1]."""
     return w.reshape(w.shape[0], -1).t().contiguous().reshape(-1, w.shape[0], 1, 1)
@@ -92,14 +97,15 @@ class PixelCNNEngine:
                     cats[(i, 'v2h+h')] = buf
                     add((i, 'v2h'), L.vert_to_horiz.weight, out=buf[:n1])
                     add((i, 'h'), L.horiz_stack.weight, ksize=3, kh0=1, out=buf[n1:])
-                    add((i, 'r'), L.horiz_resid[0].module.weight)
+                    add((i, 'r'), _unwrap(L.horiz_resid[0]).weight)
                     continue
                 add((i, 'h'), L.horiz_stack.weight, ksize=3, kh0=1)
             add((i, 'v2h'), L.vert_to_horiz.weight)
-            add((i, 'r'), L.horiz_resid[0].module.weight)
+            add((i, 'r'), _unwrap(L.horiz_resid[0]).weight)
         oc = m.output_conv
-        add(('head', 0), oc[0].module.weight)
-        add(('head', 4), oc[4].module.weight, **({'k_img': pad8(oc[4].module.out_channels)} if backward else {}))
+        last = _unwrap(oc[-1])                         # output_conv.4 (MCPixelCNN) / output_conv.3 (CPixelCNN)
+        add(('head', 0), _unwrap(oc[0]).weight)
+        add(('head', 4), last.weight, **({'k_img': pad8(last.out_channels)} if backward else {}))
         images = dict(zip(keys, ops.prep_weight_ex_many(jobs, dt)))
         images.update(cats)
         return images

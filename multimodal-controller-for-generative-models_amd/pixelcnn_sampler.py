@@ -9,7 +9,9 @@ positions already drawn and is final once they are:
     last column), layer l >= 1 reads x_h of layer l-1 at columns j-1 .. j, plus vert_to_horiz at (i, j); gate_h,
     horiz_resid, the residual and the head follow.
 So one call issues H row launches and H*W column launches back to back: every pixel of every layer is computed once (the
-arithmetic of ONE full forward), with no host synchronisation and no torch work between the launches."""
+arithmetic of ONE full forward), with no host synchronisation and no torch work between the launches.
+ConditionalGatedPixelCNN (models/cpixelcnn.py) runs the same schedule on the conditional kernel forms: the per-sample rows of
+every layer's class_cond_embedding are added to both gate inputs, and no controller multiplies anything."""
 from __future__ import annotations
 
 from typing import Optional
@@ -36,6 +38,21 @@ def _mat(w: Tensor, rows: int, k: int) -> Tensor:
     return F.pad(w, (0, k - w.shape[1], 0, rows - w.shape[0]))
 
 
+def _unwrap(mod):
+    return getattr(mod, 'module', mod)
+
+
+def conditional(m) -> bool:
+    """ConditionalGatedPixelCNN (label embedding rows) rather than MCGatedPixelCNN (MultimodalController codes)."""
+    return hasattr(m.layers[0], 'class_cond_embedding')
+
+
+def num_modes(m) -> int:
+    if conditional(m):
+        return m.layers[0].class_cond_embedding.num_embeddings
+    return m.output_conv[3].codebook.shape[0]
+
+
 def controllers(m):
     """Every MultimodalController in the order the kernels read their code rows (the engine's CodeBatch order)."""
     return [mc for L in m.layers for mc in (L.gate_v.mc, L.gate_h.mc, L.horiz_resid[2])] + [m.output_conv[3]]
@@ -45,7 +62,7 @@ def pack(m, dtype: torch.dtype):
     """-> (embedding [Kq, C] in `dtype`, weight pack in `dtype`, fp32 pack) in the layout of csrc/pixelcnn_sample.hip."""
     c, n_layer = m.hidden_size, len(m.layers)
     oc = m.output_conv
-    conv0, bn0, conv4 = oc[0].module, oc[1].module, oc[4].module
+    conv0, bn0, conv4 = _unwrap(oc[0]), _unwrap(oc[1]), _unwrap(oc[-1])
     hd, kq = conv0.out_channels, conv4.out_channels
     if c % 8 or hd % 8 or m.layers[0].kernel != 7 or any(L.kernel != 3 for L in m.layers[1:]):
         raise ValueError('Not valid model for sample: a 7x7 first layer, 3x3 layers after it, channels a multiple of 8')
@@ -59,9 +76,9 @@ def pack(m, dtype: torch.dtype):
         vm = wv.permute(0, 2, 3, 1).reshape(2 * c, -1)        # k = (tap row * KW + tap col) * C + channel
         hm = wh.permute(0, 2, 3, 1).reshape(2 * c, -1)
         mats += [_mat(vm, 2 * c, _r32(vm.shape[1])), _mat(L.vert_to_horiz.weight.detach(), 2 * c, _r32(2 * c)),
-                 _mat(hm, 2 * c, _r32(hm.shape[1])), _mat(L.horiz_resid[0].module.weight.detach(), _r16(c), _r32(c))]
-        vecs += [L.vert_stack.bias, L.vert_to_horiz.bias, L.horiz_stack.bias, L.horiz_resid[0].module.bias]
-        for bn in (L.gate_v.bn, L.gate_h.bn, L.horiz_resid[1].module):
+                 _mat(hm, 2 * c, _r32(hm.shape[1])), _mat(_unwrap(L.horiz_resid[0]).weight.detach(), _r16(c), _r32(c))]
+        vecs += [L.vert_stack.bias, L.vert_to_horiz.bias, L.horiz_stack.bias, _unwrap(L.horiz_resid[0]).bias]
+        for bn in (L.gate_v.bn, L.gate_h.bn, _unwrap(L.horiz_resid[1])):
             vecs += list(ops.bn_eval_affine(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps))
     mats += [_mat(conv0.weight.detach(), _r16(hd), _r32(c)), _mat(conv4.weight.detach(), _r16(kq), _r32(hd))]
     vecs += [conv0.bias, *ops.bn_eval_affine(bn0.weight.detach(), bn0.bias.detach(), bn0.running_mean, bn0.running_var, bn0.eps),
@@ -90,7 +107,7 @@ def validate(m, label: Tensor):
         raise ValueError('Not valid mode: sample needs eval mode (batch-statistics BatchNorm makes the incremental form inexact)')
     if label.dtype != torch.int64:
         raise ValueError(f'Not valid label dtype: {label.dtype}, sample needs int64')
-    modes = m.output_conv[3].codebook.shape[0]
+    modes = num_modes(m)
     if label.numel() and (int(label.min()) < 0 or int(label.max()) >= modes):
         raise ValueError(f'Not valid label: every label must lie in [0, {modes})')
 
@@ -101,7 +118,7 @@ def sample(m, label: Tensor, x: Tensor, dtype: torch.dtype, uniform: Optional[Te
     None).  uniform [H*W, N] fp32 drives the inverse-CDF draw (ignored when greedy)."""
     n, h, w = x.shape
     c, n_layer = m.hidden_size, len(m.layers)
-    hd, kq = m.output_conv[0].module.out_channels, m.output_conv[4].module.out_channels
+    hd, kq = _unwrap(m.output_conv[0]).out_channels, _unwrap(m.output_conv[-1]).out_channels
     if x.dtype != torch.int64 or not x.is_contiguous() or label.shape != (n,):
         raise ValueError('Not valid input: x must be a contiguous int64 [N, H, W] map and the label [N]')
     dev = x.device
@@ -111,7 +128,11 @@ def sample(m, label: Tensor, x: Tensor, dtype: torch.dtype, uniform: Optional[Te
         raise ValueError(f'Not valid uniform: fp32 [{h * w}, {n}] expected')
     uniform = uniform.contiguous()
     emb, wpack, ppack = pack(m, dtype)
-    mc = _code_rows(ops.CodeBatch(controllers(m)).run_labels(label))
+    cond = conditional(m)
+    if cond:                                    # [L][N][2C]: every layer's embedding row of every sample, one launch
+        mc = ops.cpx_gather_rows(torch.stack([L.class_cond_embedding.weight.detach() for L in m.layers]), label)
+    else:
+        mc = _code_rows(ops.CodeBatch(controllers(m)).run_labels(label))
     ov = torch.empty((n_layer, n, 2, w, c), dtype=dtype, device=dev)
     v2h = torch.empty((n_layer, n, w, 2 * c), dtype=torch.float32, device=dev)
     xh = torch.empty((n_layer, n, w, c), dtype=dtype, device=dev)
@@ -120,10 +141,11 @@ def sample(m, label: Tensor, x: Tensor, dtype: torch.dtype, uniform: Optional[Te
     P.codes, P.emb, P.w, P.p, P.mc = ops._p(x), ops._p(emb), ops._p(wpack), ops._f32(ppack), ops._f32(mc)
     P.ov, P.v2h, P.xh, P.uniform, P.logits = ops._p(ov), ops._f32(v2h), ops._p(xh), ops._f32(uniform), ops._f32(logits)
     P.N, P.H, P.W, P.C, P.L, P.Kq, P.Hd, P.greedy = n, h, w, c, n_layer, kq, hd, int(greedy)
+    row, col = (ops.cpx_sample_row, ops.cpx_sample_col) if cond else (ops.px_sample_row, ops.px_sample_col)
     for i in range(h):
-        ops.px_sample_row(P, i, dtype)
+        row(P, i, dtype)
         for j in range(w):
-            ops.px_sample_col(P, i, j, dtype)
+            col(P, i, j, dtype)
     # every buffer the launches read stays referenced until here; the stream orders their later reuse
     del emb, wpack, ppack, mc, ov, v2h, xh, uniform
     return x, (logits.permute(0, 3, 1, 2).contiguous() if logits is not None else None)

@@ -850,6 +850,11 @@ class GlowTrainer(_FlatTrainer):
 class PixelCNNTrainer(_FlatTrainer):
     """train_pixelcnn.py:108-121 on the HIP path: the code map comes from the (frozen) VQ-VAE encoder upstream."""
 
+    def __init__(self, model, *a, world_size=1, **k):
+        if world_size > 1 and hasattr(model.layers[0], 'class_cond_embedding'):
+            raise ValueError('CPixelCNN training runs on one GPU: multi-GPU CPixelCNN is not supported; run with world_size 1')
+        super().__init__(model, *a, world_size=world_size, **k)
+
     def _compute(self, codes, label):
         eng = self.model._engine()
         self.gflat.zero_()

@@ -1022,6 +1022,110 @@ def fx_cgan_full():
 
 FIXTURES.update(cgan_small=fx_cgan_small, cgan_omniglot_small=fx_cgan_omniglot_small, cgan_full=fx_cgan_full)
 
+
+# ---- CPixelCNN (models/cpixelcnn.py): the conditional PixelCNN baseline, per-layer label embeddings -------------------
+def _set_cpixelcnn_cfg(hidden, layers, codes, classes):
+    cfg['model_name'] = 'cpixelcnn'; cfg['device'] = 'cpu'; cfg['classes_size'] = classes
+    cfg['pixelcnn'] = {'num_layer': layers, 'hidden_size': hidden, 'num_embedding': codes}
+
+
+def _cpixelcnn_small(name, classes, full_final):
+    """Hidden 16, 4 layers, 32 codes on 8x8 maps, B=6, procedural weights over the reference's layout (stored), 3
+    train_pixelcnn.py steps: logits of the first forward, the losses, the state after training (differences from the
+    initial state, or digests only), eval-mode logits of the trained model and its greedy decode (argmax per position
+    through reference forwards, cpixelcnn.py:100-108 with the draw replaced)."""
+    import models
+    _set_cpixelcnn_cfg(16, 4, 32, classes)
+    torch.manual_seed(0)
+    model = models.cpixelcnn()
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    seed = 2468
+    sd0 = gu.procedural_state_generic(shapes, seed=seed)
+    model.load_state_dict(sd0)
+    model.train(True)
+    arrays = {'layout': _cgan_layout(shapes), 'sd_seed': np.array(seed)}
+    g = torch.Generator().manual_seed(47)
+    codes = torch.randint(0, 32, (6, 8, 8), generator=g)
+    lab = torch.randint(0, classes, (6,), generator=g)
+    lab[1] = lab[0]                                          # a repeated label; with 6 samples most modes are absent
+    lab[2] = classes - 1
+    arrays['codes'] = codes.numpy(); arrays['label'] = lab.numpy()
+    first = _single_opt_steps(model, {'img': codes, 'label': lab}, 500, 3, arrays)
+    arrays['logits0'] = first['logits'].detach().numpy()
+    fin = model.state_dict()
+    for k, v in fin.items():
+        if not v.is_floating_point():
+            arrays['sd_final_int/' + k] = v.numpy().copy()
+        elif full_final:
+            arrays['sd_delta/' + k] = (v - sd0[k]).detach().numpy()
+        else:
+            arrays['digest/' + k] = gu.checksum(v)
+    model.train(False)
+    with torch.no_grad():
+        arrays['logits_eval'] = model({'img': codes, 'label': lab})['logits'].numpy()
+        x = torch.zeros((6, 8, 8), dtype=torch.long)
+        for i in range(8):
+            for j in range(8):
+                out = model({'img': x, 'label': lab})
+                x[:, i, j] = out['logits'][:, :, i, j].argmax(1)
+        arrays['greedy'] = x.numpy()
+    save(name, **arrays)
+
+
+def fx_cpixelcnn_small():
+    _cpixelcnn_small('cpixelcnn_small.npz', 10, True)
+
+
+def fx_cpixelcnn_omniglot_small():
+    _cpixelcnn_small('cpixelcnn_omniglot_small.npz', 1623, False)
+
+
+def fx_cpixelcnn_full():
+    """configs[4] shapes (utils.py:139-143): 15 layers, hidden 128, 512 codes, 10 modes (6,406,016 parameters), B=128,
+    procedural weights: the first training forward's loss and logits digest, the digest of every parameter's gradient of
+    that step (before clip_grad_norm_; the last layer's gate_v.bn gets none), two train_pixelcnn.py steps' losses."""
+    import models
+    _set_cpixelcnn_cfg(128, 15, 512, 10)
+    torch.manual_seed(0)
+    model = models.cpixelcnn(); model.train(True)
+    assert sum(p.numel() for p in model.parameters()) == 6406016
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    seed = 4243
+    model.load_state_dict(gu.procedural_state_generic(shapes, seed=seed))
+    arrays = {'layout': _cgan_layout(shapes), 'sd_seed': np.array(seed)}
+    g = torch.Generator().manual_seed(44)
+    B = 128
+    codes = torch.randint(0, 512, (B, 8, 8), generator=g)
+    lab = torch.randint(0, 9, (B,), generator=g)              # mode 9 absent
+    arrays['codes'] = codes.numpy(); arrays['label'] = lab.numpy()
+    opt = torch.optim.Adam(model.parameters(), lr=3e-4)
+    losses = []
+    for step in range(2):
+        opt.zero_grad()
+        out = model({'img': codes.clone(), 'label': lab})
+        out['loss'].backward()
+        if step == 0:
+            arrays['logits0_digest'] = gu.checksum(out['logits'].detach())
+            names, dead = [], []
+            for k, p in model.named_parameters():
+                if p.grad is None:
+                    dead.append(k)
+                    continue
+                names.append(k)
+                arrays['grad0_digest/' + k] = gu.checksum(p.grad)
+                arrays['grad0_absmax/' + k] = np.array(float(p.grad.abs().max()))
+            arrays['grad_keys'] = np.array(names)
+            arrays['nograd_keys'] = np.array(dead)
+        torch.nn.utils.clip_grad_norm_(model.parameters(), 1)
+        opt.step()
+        losses.append(out['loss'].item())
+    arrays['losses'] = np.array(losses, dtype=np.float64)
+    save('cpixelcnn_full_digest.npz', **arrays)
+
+
+FIXTURES.update(cpixelcnn_small=fx_cpixelcnn_small, cpixelcnn_omniglot_small=fx_cpixelcnn_omniglot_small,
+                cpixelcnn_full=fx_cpixelcnn_full)
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--only', default=None)
