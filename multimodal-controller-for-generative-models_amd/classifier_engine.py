@@ -17,34 +17,19 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .engine_base import EngineBase, _t3x3
 from .ops import Seg
 
 Tensor = torch.Tensor
 
 
-def _t3x3(w: Tensor) -> Tensor:
-    return w.flip(2, 3).transpose(0, 1).contiguous()
-
-
-class ClassifierEngine:
+class ClassifierEngine(EngineBase):
     def __init__(self, model, dtype: torch.dtype = torch.float32):
-        self.m = model
-        self.dtype = dtype
-        self._gsink = None
+        super().__init__(model, dtype)
         self.convs = [b for b in model.blocks if isinstance(b, nn.Conv2d)]
         self.bns = [b for b in model.blocks if isinstance(b, nn.BatchNorm2d)]
         if any(c.out_channels % 8 for c in self.convs):
             raise ValueError('Not valid hidden size: the fused path needs multiples of 8')
-
-    def _grad(self, p: Tensor) -> Tensor:
-        if self._gsink is not None:
-            g = self._gsink.get(id(p))
-            if g is None:
-                g = self._gsink[id(p)] = torch.zeros_like(p)
-            return g
-        if p.grad is None:
-            p.grad = torch.zeros_like(p)
-        return p.grad
 
     def _head_weight(self, h: int, w: int) -> Tensor:
         """Linear weight [classes, c * h * w] -> the 1x1 weight over the NHWC flattening [classes, h * w * c, 1, 1]."""
@@ -63,12 +48,7 @@ class ClassifierEngine:
             h, st = ops.conv_fused([Seg(x)], ops.prep_weight(conv.weight.detach(), dt), conv.out_channels, bias=conv.bias.detach(),
                                    stats_mode=1 if train else 0)
             n, hh, ww, _ = h.shape
-            if train:
-                b = ops.bn_finalize(st, n * hh * ww, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
-                                    bn.momentum, bn.eps)
-                bn.num_batches_tracked += 1
-            else:
-                b = ops.bn_eval_affine(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps) + (None, None)
+            b = self._bn(bn, st, n * hh * ww, train)
             y = ops.affine_relu_maxpool2(h, b[0], b[1]) if i < last else ops.affine_code_res(h, b[0], b[1], None, None, pre_relu=True)
             if tape is not None:
                 tape.append(dict(x=x, h=h, bn=b))

@@ -16,16 +16,15 @@ from typing import List
 import torch
 
 from . import ops
+from .engine_base import EngineBase
 from .ops import Seg, pad8
 
 Tensor = torch.Tensor
 
 
-class GlowEngine:
+class GlowEngine(EngineBase):
     def __init__(self, model, dtype: torch.dtype = torch.float32):
-        self.m = model
-        self.dtype = dtype
-        self._gsink = None          # id(param) -> gradient tensor while an autograd backward is collecting
+        super().__init__(model, dtype)
         self.assume_initialized = False   # set by a graph capture: skip the host read of ActNorm.initialized
         self._const = {}
         self._pass = None                          # per-pass batches (ActNorm vectors, codes): _begin_pass
@@ -270,16 +269,6 @@ class GlowEngine:
     # ---- backward: gradients of the mean bits/dim w.r.t. every parameter -------------------------------------------
     # Autograd of the same reference lines, written out.  g0 = d loss / d (logdet_n | logp_n) = -1 / (N log2 n_pixel)
     # (train-mode loss: NaN samples are replaced by 0 in the reference; a batch that produces NaNs is not handled here).
-    def _grad(self, p: Tensor) -> Tensor:
-        if self._gsink is not None:
-            g = self._gsink.get(id(p))
-            if g is None:
-                g = self._gsink[id(p)] = torch.zeros_like(p)
-            return g
-        if p.grad is None:
-            p.grad = torch.zeros_like(p)
-        return p.grad
-
     def _zero_conv_bwd(self, zc, seg_in, out: Tensor, dout: Tensor, cout: int, cin: int, need_dx: bool, res=None, **dgrad_kw):
         """ZeroConv2d backward: out = (conv(A) + b) * exp(3 scale).  Returns (dA, stats) when need_dx."""
         dt = self.dtype

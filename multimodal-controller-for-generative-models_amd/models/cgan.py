@@ -16,8 +16,7 @@ import torch.nn as nn
 
 from ..cgan_engine import CDiscriminatorEngine, CGeneratorEngine
 from ..config import cfg
-from .mcgan import _FusedNet
-from .utils import init_param, make_SpectralNormalization
+from .utils import FusedNet, init_param, make_SpectralNormalization
 
 
 class GenResBlock(nn.Module):
@@ -52,7 +51,7 @@ class _GenFn(torch.autograd.Function):
         return (None, None, None, None, *eng.flat_p.views(gflat))
 
 
-class Generator(_FusedNet):
+class Generator(FusedNet):
     _engine_cls = CGeneratorEngine
 
     def __init__(self, data_shape, latent_size, hidden_size, num_mode, embedding_size):
@@ -122,7 +121,7 @@ class _DisFn(torch.autograd.Function):
         return (None, dimg, None, None, *grads)
 
 
-class Discriminator(_FusedNet):
+class Discriminator(FusedNet):
     _engine_cls = CDiscriminatorEngine
 
     def __init__(self, data_shape, hidden_size, num_mode, embedding_size):

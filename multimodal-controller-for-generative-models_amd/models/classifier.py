@@ -24,7 +24,7 @@ from .._lib import McgenError
 from ..classifier_engine import ClassifierEngine
 from ..config import cfg
 from ..ops import Seg
-from .utils import init_param
+from .utils import FusedNet, init_param
 
 
 def loss(input, output):
@@ -32,32 +32,9 @@ def loss(input, output):
     return F.cross_entropy(output['label'], input['label'], reduction='mean')
 
 
-class _ClassifierFn(torch.autograd.Function):
-    """One autograd node for the whole model: only the loss carries gradient (train_classifier.py:108-109)."""
+class Classifier(FusedNet):
+    _engine_cls = ClassifierEngine
 
-    @staticmethod
-    def forward(ctx, engine, img, label, holder, *params):
-        tape = []
-        loss, logits = engine.forward(img, label, True, tape, want_grad=True)
-        holder['label'] = logits
-        ctx.engine, ctx.tape = engine, tape
-        ctx.params = params
-        return loss
-
-    @staticmethod
-    def backward(ctx, gloss):
-        eng = ctx.engine
-        sink = {}
-        eng._gsink = sink
-        try:
-            eng.backward(ctx.tape)
-        finally:
-            eng._gsink = None
-        ctx.tape = None
-        return (None, None, None, None) + tuple(sink[id(p)] * gloss if id(p) in sink else None for p in ctx.params)
-
-
-class Classifier(nn.Module):
     def __init__(self, data_shape, hidden_size, classes_size):
         super().__init__()
         blocks, cin = [], data_shape[0]
@@ -71,27 +48,12 @@ class Classifier(nn.Module):
         self.encoded_shape = [hidden_size[-1], data_shape[1] // down, data_shape[2] // down]
         self.classifier = nn.Linear(int(np.prod(self.encoded_shape)), classes_size)
 
-    def set_compute_dtype(self, dtype):
-        self.__dict__['_cdt'] = dtype
-        return self
-
-    def _dt(self):
-        return self.__dict__.get('_cdt') or {'float32': torch.float32, 'bfloat16': torch.bfloat16}[cfg.get('compute_dtype', 'float32')]
-
-    def _engine(self):
-        eng = self.__dict__.get('_eng')
-        dt = self._dt()
-        if eng is None or eng.dtype != dt:
-            eng = ClassifierEngine(self, dt)
-            self.__dict__['_eng'] = eng
-        return eng
-
     def _encode(self, x: torch.Tensor) -> torch.Tensor:
         """-> NHWC map of the last stage after BatchNorm + ReLU, [N, h, w, pad8(C)]."""
         if self.training:
             raise McgenError('Classifier.feature is the evaluation-mode feature network of IS / FID (metrics.py:55,95); '
                              'training runs through Classifier.forward / trainer.ClassifierTrainer')
-        dt = self._dt()
+        dt = self.compute_dtype
         stages = [m for m in self.blocks if isinstance(m, nn.Conv2d)]
         bns = [m for m in self.blocks if isinstance(m, nn.BatchNorm2d)]
         y = ops.to_nhwc(x.detach().contiguous().float(), dt)
@@ -120,9 +82,13 @@ class Classifier(nn.Module):
         if self.training:
             eng = self._engine()
             if torch.is_grad_enabled():
+                def run(holder):
+                    tape = []
+                    loss, holder['label'] = eng.forward(input['img'], input['label'], True, tape, want_grad=True)
+                    return loss, lambda: eng.backward(tape)
+
                 holder = {}
-                params = [p for p in self.parameters() if p.requires_grad]
-                ce = _ClassifierFn.apply(eng, input['img'], input['label'], holder, *params)
+                ce = self._loss_node(run, holder)
                 return {'label': holder['label'], 'loss': ce}
             with torch.no_grad():
                 ce, logits = eng.forward(input['img'], input['label'], True)

@@ -10,8 +10,7 @@ import torch.nn.functional as F
 
 from ..config import cfg
 from ..cpixelcnn_engine import CPixelCNNEngine
-from .mcpixelcnn import _PixelFn
-from .utils import init_param
+from .utils import FusedNet, init_param
 
 
 def _check_labels(m, label):
@@ -57,9 +56,10 @@ class ConditionalGatedMaskedConv2d(nn.Module):
             self.horiz_stack.weight[:, :, :, -1].zero_()
 
 
-class ConditionalGatedPixelCNN(nn.Module):
+class ConditionalGatedPixelCNN(FusedNet):
     """cpixelcnn.py:65-108 -- embedding of the code map, one 7x7 mask-A layer without residual, 3x3 mask-B layers with
     residual, a two-layer 1x1 head over 512 channels."""
+    _engine_cls = CPixelCNNEngine
 
     def __init__(self, input_size=256, hidden_size=64, num_layer=15, num_mode=10):
         super().__init__()
@@ -72,22 +72,6 @@ class ConditionalGatedPixelCNN(nn.Module):
         self.output_conv = nn.Sequential(nn.Conv2d(hidden_size, head, 1), nn.BatchNorm2d(head), nn.ReLU(True),
                                          nn.Conv2d(head, input_size, 1))
 
-    def _dtype(self):
-        dt = {'float32': torch.float32, 'bfloat16': torch.bfloat16}[cfg.get('compute_dtype', 'float32')]
-        return self.__dict__.get('_cdt') or dt
-
-    def _engine(self):
-        eng = self.__dict__.get('_eng')
-        dt = self._dtype()
-        if eng is None or eng.dtype != dt:
-            eng = CPixelCNNEngine(self, dt)
-            self.__dict__['_eng'] = eng
-        return eng
-
-    def set_compute_dtype(self, dtype):
-        self.__dict__['_cdt'] = dtype
-        return self
-
     def forward(self, input):
         """{'img': int64 code map [N,H,W], 'label': int64 [N] in [0, num_mode)} -> {'logits' [N,K,H,W] fp32, 'loss'}
         (cpixelcnn.py:86-98)."""
@@ -97,9 +81,14 @@ class ConditionalGatedPixelCNN(nn.Module):
         _check_labels(self, label)
         eng = self._engine()
         if torch.is_grad_enabled() and self.training:
+
+            def run(holder):
+                tape = {}
+                loss, holder['logits'], _ = eng.forward(codes, label, True, tape, want_grad=True)
+                return loss, lambda: eng.backward(tape)
+
             holder = {}
-            params = [p for p in self.parameters() if p.requires_grad]
-            loss = _PixelFn.apply(eng, codes, label, holder, *params)
+            loss = self._loss_node(run, holder)
             logits = holder['logits']
         else:
             loss, logits, _ = eng.forward(codes, label, self.training)
@@ -131,7 +120,7 @@ class ConditionalGatedPixelCNN(nn.Module):
         if x is None:
             x = torch.zeros((C.size(0), 8, 8), dtype=torch.long, device=cfg['device'])
         with torch.no_grad():
-            x, logits = pixelcnn_sampler.sample(self, C, x, self._dtype(), uniform=uniform, greedy=greedy,
+            x, logits = pixelcnn_sampler.sample(self, C, x, self.compute_dtype, uniform=uniform, greedy=greedy,
                                                 return_logits=return_logits)
         return (x, logits) if return_logits else x
 

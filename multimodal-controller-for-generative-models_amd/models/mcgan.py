@@ -15,37 +15,12 @@ import torch.nn.functional as F
 from ..config import cfg
 from ..gan_engine import DiscriminatorEngine, GeneratorEngine
 from ..modules import MultimodalController, Wrapper
-from .utils import init_param, make_SpectralNormalization
+from .utils import FusedNet, init_param, make_SpectralNormalization
 
 
 def _chain(*mods):
     """nn.Sequential over the list protocol: bare tensor modules get a Wrapper."""
     return nn.Sequential(*[m if isinstance(m, (MultimodalController, Wrapper)) else Wrapper(m) for m in mods])
-
-
-def _compute_dtype():
-    name = cfg.get('compute_dtype', 'float32')
-    return {'float32': torch.float32, 'bfloat16': torch.bfloat16}[name]
-
-
-class _FusedNet(nn.Module):
-    """Shared plumbing: lazily built engine, compute dtype switch, autograd bridge."""
-    _engine_cls = None
-
-    def _engine(self):
-        eng = self.__dict__.get('_eng')
-        if eng is None or eng.dtype != self.compute_dtype:
-            eng = self._engine_cls(self, self.compute_dtype)
-            self.__dict__['_eng'] = eng
-        return eng
-
-    @property
-    def compute_dtype(self):
-        return self.__dict__.get('_cdt') or _compute_dtype()
-
-    def set_compute_dtype(self, dtype):
-        self.__dict__['_cdt'] = dtype
-        return self
 
 
 # --------------------------------------------------------------------------------------------- #
@@ -84,7 +59,7 @@ class _GenFn(torch.autograd.Function):
         return (None, None, None, None, *eng.flat_p.views(gflat))
 
 
-class Generator(_FusedNet):
+class Generator(FusedNet):
     _engine_cls = GeneratorEngine
 
     def __init__(self, data_shape, latent_size, hidden_size, num_mode, controller_rate):
@@ -158,7 +133,7 @@ class _DisFn(torch.autograd.Function):
         return (None, dimg, None, None, *grads)
 
 
-class Discriminator(_FusedNet):
+class Discriminator(FusedNet):
     _engine_cls = DiscriminatorEngine
 
     def __init__(self, data_shape, hidden_size, num_mode, controller_rate):

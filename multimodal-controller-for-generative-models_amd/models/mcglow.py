@@ -16,33 +16,7 @@ import torch.nn as nn
 from ..config import cfg
 from ..glow_engine import GlowEngine
 from ..modules import MultimodalController, Wrapper
-from .utils import init_param
-
-
-class _GlowFn(torch.autograd.Function):
-    """loss = engine.forward(...); backward = engine.backward over the saved tape (one node for the whole model)."""
-
-    @staticmethod
-    def forward(ctx, engine, img, label, noise, train, holder, *params):
-        tape = []
-        loss, zs = engine.forward(img, None, noise, train, tape, label=label)
-        holder['z'] = zs
-        ctx.engine, ctx.tape, ctx.params = engine, tape, params
-        ctx.n, ctx.n_pixel = img.shape[0], float(img[0].numel())
-        return loss
-
-    @staticmethod
-    def backward(ctx, gloss):
-        eng = ctx.engine
-        sink = {}
-        eng._gsink = sink
-        try:
-            eng.backward(ctx.tape, ctx.n, ctx.n_pixel)
-        finally:
-            eng._gsink = None
-        ctx.tape = None
-        grads = tuple(sink[id(p)] * gloss if id(p) in sink else None for p in ctx.params)
-        return (None, None, None, None, None, None) + grads
+from .utils import FusedNet, init_param
 
 
 class ActNorm(nn.Module):
@@ -129,8 +103,9 @@ class Block(nn.Module):
         self.prior = ZeroConv2d(input_size * 2, input_size * 4) if split else ZeroConv2d(input_size * 4, input_size * 8)
 
 
-class MCGlow(nn.Module):
+class MCGlow(FusedNet):
     """mcglow.py:268-350."""
+    _engine_cls = GlowEngine
 
     def __init__(self, data_shape, hidden_size, K, L, affine=True, conv_lu=True, num_mode=None, controller_rate=0.5):
         super().__init__()
@@ -144,28 +119,21 @@ class MCGlow(nn.Module):
         self.blocks.append(Block(c, hidden_size, K, False, affine, conv_lu, num_mode, controller_rate))
 
     # ---- fused path ------------------------------------------------------------------------------------------
-    def _engine(self):
-        eng = self.__dict__.get('_eng')
-        dt = {'float32': torch.float32, 'bfloat16': torch.bfloat16}[cfg.get('compute_dtype', 'float32')]
-        dt = self.__dict__.get('_cdt') or dt
-        if eng is None or eng.dtype != dt:
-            eng = GlowEngine(self, dt)
-            self.__dict__['_eng'] = eng
-        return eng
-
-    def set_compute_dtype(self, dtype):
-        self.__dict__['_cdt'] = dtype
-        return self
-
     def forward(self, input):
         """Negative log-likelihood in bits/dim (mcglow.py:283-312).  The dequantisation noise U(0,1)/256 is
         drawn here unless `input['noise']` supplies it (parity runs)."""
         label = self._check_label(input['label'])        # one_hot(label) @ codebook == codebook[label] (modules.py:73)
         noise = input['noise'] if 'noise' in input else torch.rand_like(input['img'])
         if torch.is_grad_enabled() and self.training:
+            img, eng = input['img'], self._engine()
+
+            def run(holder):
+                tape = []
+                loss, holder['z'] = eng.forward(img, None, noise, True, tape, label=label)
+                return loss, lambda: eng.backward(tape, img.shape[0], float(img[0].numel()))
+
             holder = {}
-            params = [p for p in self.parameters() if p.requires_grad]
-            loss = _GlowFn.apply(self._engine(), input['img'], label, noise, True, holder, *params)
+            loss = self._loss_node(run, holder)
             return {'loss': loss, 'z': holder['z']}
         loss, z = self._engine().forward(input['img'], None, noise, self.training, label=label)
         return {'loss': loss, 'z': z}

@@ -10,32 +10,7 @@ import torch.nn.functional as F
 from ..config import cfg
 from ..modules import MultimodalController, Wrapper
 from ..pixelcnn_engine import PixelCNNEngine
-from .utils import init_param
-
-
-class _PixelFn(torch.autograd.Function):
-    """loss, logits = engine.forward(...); backward replays the engine's tape (one node for the whole model).
-    Only the loss carries gradient (train_pixelcnn.py:115-117 back-propagates the loss alone)."""
-
-    @staticmethod
-    def forward(ctx, engine, codes, label, holder, *params):
-        tape = {}
-        loss, logits, _ = engine.forward(codes, label, True, tape, want_grad=True)
-        holder['logits'] = logits
-        ctx.engine, ctx.tape, ctx.params = engine, tape, params
-        return loss
-
-    @staticmethod
-    def backward(ctx, gloss):
-        eng = ctx.engine
-        sink = {}
-        eng._gsink = sink
-        try:
-            eng.backward(ctx.tape)
-        finally:
-            eng._gsink = None
-        ctx.tape = None
-        return (None, None, None, None) + tuple(sink[id(p)] * gloss if id(p) in sink else None for p in ctx.params)
+from .utils import FusedNet, init_param
 
 
 def _controller(width, modes, rate):
@@ -78,9 +53,10 @@ class MCGatedMaskedConv2d(nn.Module):
             self.horiz_stack.weight[:, :, :, -1].zero_()
 
 
-class MCGatedPixelCNN(nn.Module):
+class MCGatedPixelCNN(FusedNet):
     """mcpixelcnn.py:64-112 -- embedding of the code map, one 7x7 mask-A layer without residual, 3x3 mask-B layers with
     residual, a two-layer 1x1 head over 512 channels."""
+    _engine_cls = PixelCNNEngine
 
     def __init__(self, input_size=256, hidden_size=64, num_layer=15, num_mode=10, controller_rate=0.5):
         super().__init__()
@@ -94,19 +70,6 @@ class MCGatedPixelCNN(nn.Module):
                                          Wrapper(nn.ReLU(inplace=True)), _controller(head, num_mode, controller_rate),
                                          Wrapper(nn.Conv2d(head, input_size, kernel_size=1)))
 
-    def _engine(self):
-        eng = self.__dict__.get('_eng')
-        dt = {'float32': torch.float32, 'bfloat16': torch.bfloat16}[cfg.get('compute_dtype', 'float32')]
-        dt = self.__dict__.get('_cdt') or dt
-        if eng is None or eng.dtype != dt:
-            eng = PixelCNNEngine(self, dt)
-            self.__dict__['_eng'] = eng
-        return eng
-
-    def set_compute_dtype(self, dtype):
-        self.__dict__['_cdt'] = dtype
-        return self
-
     def forward(self, input):
         """{'img': int64 code map [N,H,W], 'label': int64 [N]} -> {'logits' [N,K,H,W] fp32, 'loss'} (mcpixelcnn.py:89-101)."""
         codes, label = input['img'], input['label']
@@ -114,9 +77,14 @@ class MCGatedPixelCNN(nn.Module):
             raise ValueError('Not valid input: code map and label must be int64')
         eng = self._engine()
         if torch.is_grad_enabled() and self.training:
+
+            def run(holder):
+                tape = {}
+                loss, holder['logits'], _ = eng.forward(codes, label, True, tape, want_grad=True)
+                return loss, lambda: eng.backward(tape)
+
             holder = {}
-            params = [p for p in self.parameters() if p.requires_grad]
-            loss = _PixelFn.apply(eng, codes, label, holder, *params)
+            loss = self._loss_node(run, holder)
             logits = holder['logits']
         else:
             loss, logits, _ = eng.forward(codes, label, self.training)
@@ -148,10 +116,9 @@ class MCGatedPixelCNN(nn.Module):
         pixelcnn_sampler.validate(self, C)
         if x is None:
             x = torch.zeros((C.size(0), 8, 8), dtype=torch.long, device=cfg['device'])
-        dt = {'float32': torch.float32, 'bfloat16': torch.bfloat16}[cfg.get('compute_dtype', 'float32')]
-        dt = self.__dict__.get('_cdt') or dt
         with torch.no_grad():
-            x, logits = pixelcnn_sampler.sample(self, C, x, dt, uniform=uniform, greedy=greedy, return_logits=return_logits)
+            x, logits = pixelcnn_sampler.sample(self, C, x, self.compute_dtype, uniform=uniform, greedy=greedy,
+                                                return_logits=return_logits)
         return (x, logits) if return_logits else x
 
 

@@ -10,31 +10,7 @@ import torch.nn as nn
 from ..config import cfg
 from ..modules import MultimodalController, Wrapper
 from ..vae_engine import VAEEngine
-from .utils import init_param
-
-
-class _VAEFn(torch.autograd.Function):
-    """One autograd node for the whole model: only the loss carries gradient (train_vae.py:107-109)."""
-
-    @staticmethod
-    def forward(ctx, engine, img, label, eps, holder, *params):
-        tape = []
-        out = engine.forward(img, label, True, eps, tape, want_grad=True)
-        holder.update(out)
-        ctx.engine, ctx.tape, ctx.params, ctx.label = engine, tape, params, label
-        return out['loss']
-
-    @staticmethod
-    def backward(ctx, gloss):
-        eng = ctx.engine
-        sink = {}
-        eng._gsink = sink
-        try:
-            eng.backward(ctx.tape, ctx.label)
-        finally:
-            eng._gsink = None
-        ctx.tape = None
-        return (None, None, None, None, None) + tuple(sink[id(p)] * gloss if id(p) in sink else None for p in ctx.params)
+from .utils import FusedNet, init_param
 
 
 def _mc(width, modes, rate):
@@ -103,8 +79,9 @@ class Decoder(nn.Module):
         self.blocks = nn.Sequential(*layers)
 
 
-class MCVAE(nn.Module):
+class MCVAE(FusedNet):
     """mcvae.py:104-144."""
+    _engine_cls = VAEEngine
 
     def __init__(self, data_shape=(3, 32, 32), hidden_size=(64, 128, 256), latent_size=128, num_res_block=2,
                  num_mode=None, controller_rate=0.5):
@@ -113,19 +90,6 @@ class MCVAE(nn.Module):
         self.num_res_block, self.num_mode, self.controller_rate = num_res_block, num_mode, controller_rate
         self.encoder = Encoder(data_shape, hidden_size, latent_size, num_res_block, num_mode, controller_rate)
         self.decoder = Decoder(data_shape, hidden_size, latent_size, num_res_block, num_mode, controller_rate)
-
-    def _engine(self):
-        eng = self.__dict__.get('_eng')
-        dt = {'float32': torch.float32, 'bfloat16': torch.bfloat16}[cfg.get('compute_dtype', 'float32')]
-        dt = self.__dict__.get('_cdt') or dt
-        if eng is None or eng.dtype != dt:
-            eng = VAEEngine(self, dt)
-            self.__dict__['_eng'] = eng
-        return eng
-
-    def set_compute_dtype(self, dtype):
-        self.__dict__['_cdt'] = dtype
-        return self
 
     @staticmethod
     def _label(label):
@@ -151,9 +115,15 @@ class MCVAE(nn.Module):
         if torch.is_grad_enabled() and self.training:
             if eps is None:
                 eps = torch.randn(input['img'].shape[0], self.latent_size, device=input['img'].device)
+
+            def run(holder):
+                tape = []
+                out = eng.forward(input['img'], label, True, eps, tape, want_grad=True)
+                holder.update(out)
+                return out['loss'], lambda: eng.backward(tape, label)
+
             holder = {}
-            params = [p for p in self.parameters() if p.requires_grad]
-            loss = _VAEFn.apply(eng, input['img'], label, eps, holder, *params)
+            loss = self._loss_node(run, holder)
             return {'loss': loss, 'mu': holder['mu'], 'logvar': holder['logvar'], 'img': holder['img']}
         return eng.forward(input['img'], label, self.training, eps)
 

@@ -1,5 +1,5 @@
 """Parameter initialisation, spectral-norm applicator and codebook surgery with the reference's
-names and arity (src/models/utils.py:7-152)."""
+names and arity (src/models/utils.py:7-152); the plumbing every fused model shares (engine holder, autograd bridge)."""
 from __future__ import annotations
 
 import numpy as np
@@ -8,6 +8,59 @@ import torch.nn as nn
 
 from ..config import cfg
 from ..modules import sample_codebook
+
+
+def compute_dtype() -> torch.dtype:
+    return {'float32': torch.float32, 'bfloat16': torch.bfloat16}[cfg.get('compute_dtype', 'float32')]
+
+
+class FusedNet(nn.Module):
+    """A module computed by a fused engine: the lazily built engine and the compute dtype switch."""
+    _engine_cls = None
+
+    def _engine(self):
+        eng = self.__dict__.get('_eng')
+        if eng is None or eng.dtype != self.compute_dtype:
+            eng = self._engine_cls(self, self.compute_dtype)
+            self.__dict__['_eng'] = eng
+        return eng
+
+    @property
+    def compute_dtype(self):
+        return self.__dict__.get('_cdt') or compute_dtype()
+
+    def set_compute_dtype(self, dtype):
+        self.__dict__['_cdt'] = dtype
+        return self
+
+    def _loss_node(self, run, holder: dict):
+        """The training loss as one autograd node over every trainable parameter (see EngineLossFn)."""
+        params = [p for p in self.parameters() if p.requires_grad]
+        return EngineLossFn.apply(self._engine(), run, holder, *params)
+
+
+class EngineLossFn(torch.autograd.Function):
+    """One autograd node for a whole model: only the loss carries gradient.  `run(holder)` runs the engine's forward on a
+    tape, may leave further outputs in `holder`, and returns (loss, backward): backward() replays the tape, its parameter
+    gradients collected in the engine's gradient sink."""
+
+    @staticmethod
+    def forward(ctx, engine, run, holder, *params):
+        loss, ctx.backward_fn = run(holder)
+        ctx.engine, ctx.params = engine, params
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        eng = ctx.engine
+        sink = {}
+        eng._gsink = sink
+        try:
+            ctx.backward_fn()
+        finally:
+            eng._gsink = None
+        ctx.backward_fn = None
+        return (None, None, None) + tuple(sink[id(p)] * gloss if id(p) in sink else None for p in ctx.params)
 
 
 def init_param(m):

@@ -15,31 +15,7 @@ from ..config import cfg
 from ..modules import VectorQuantization
 from ..ops import Seg, pad8
 from ..vqvae_engine import VQVAEEngine
-from .utils import init_param
-
-
-class _VQVAEFn(torch.autograd.Function):
-    """One autograd node for the whole model: only the loss carries gradient (train_vqvae.py:106-108)."""
-
-    @staticmethod
-    def forward(ctx, engine, img, holder, *params):
-        tape = []
-        out = engine.forward(img, True, tape, want_grad=True)
-        holder.update(out)
-        ctx.engine, ctx.tape, ctx.params = engine, tape, params
-        return out['loss']
-
-    @staticmethod
-    def backward(ctx, gloss):
-        eng = ctx.engine
-        sink = {}
-        eng._gsink = sink
-        try:
-            eng.backward(ctx.tape)
-        finally:
-            eng._gsink = None
-        ctx.tape = None
-        return (None, None, None) + tuple(sink[id(p)] * gloss if id(p) in sink else None for p in ctx.params)
+from .utils import FusedNet, init_param
 
 
 class ResBlock(nn.Module):
@@ -86,8 +62,9 @@ def _affine(bn):
     return ops.bn_eval_affine(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps)
 
 
-class VQVAE(nn.Module):
+class VQVAE(FusedNet):
     """vqvae.py:78-114."""
+    _engine_cls = VQVAEEngine
 
     def __init__(self, data_shape=(3, 32, 32), hidden_size=(128, 128), num_res_block=2, embedding_size=64,
                  num_embedding=512, vq_commit=0.25):
@@ -100,25 +77,10 @@ class VQVAE(nn.Module):
         self.quantizer = VectorQuantization(embedding_size, num_embedding)
         self.decoder = Decoder(data_shape, hidden_size, num_res_block, embedding_size)
 
-    def set_compute_dtype(self, dtype):
-        self.__dict__['_cdt'] = dtype
-        return self
-
-    def _dt(self):
-        return self.__dict__.get('_cdt') or {'float32': torch.float32, 'bfloat16': torch.bfloat16}[cfg.get('compute_dtype', 'float32')]
-
     def _frozen(self):
         if self.training:
             raise NotImplementedError('VQVAE.encode / decode_code are the frozen (eval-mode) paths: training runs through '
                                       'VQVAE.forward / trainer.VQVAETrainer')
-
-    def _engine(self):
-        eng = self.__dict__.get('_eng')
-        dt = self._dt()
-        if eng is None or eng.dtype != dt:
-            eng = VQVAEEngine(self, dt)
-            self.__dict__['_eng'] = eng
-        return eng
 
     # ---- fused building blocks (eval-mode BatchNorm folded into prologues) -------------------------------------
     def _res(self, blk, x):
@@ -133,7 +95,7 @@ class VQVAE(nn.Module):
         return ops.affine_code_res(h2, s4, t4, None, x, post_relu=True)
 
     def _encoder(self, img):
-        dt = self._dt()
+        dt = self.compute_dtype
         blocks = self.encoder.blocks
         x = ops.to_nhwc(img.contiguous(), dt)
         ns = len(self.hidden_size)
@@ -170,7 +132,7 @@ class VQVAE(nn.Module):
     def decode_code(self, code):
         """code map [N, W, H] (as `encode` returns it) -> images in (-1, 1)  (vqvae.py:101-104)."""
         self._frozen()
-        dt = self._dt()
+        dt = self.compute_dtype
         with torch.no_grad():
             x = self.quantizer.embedding_code(code.transpose(1, 2)).to(dt).contiguous()       # NHWC [N, H, W, D]
             blocks = self.decoder.blocks
@@ -203,9 +165,14 @@ class VQVAE(nn.Module):
         eng = self._engine()
         img = input['img']
         if torch.is_grad_enabled() and self.training:
+            def run(holder):
+                tape = []
+                out = eng.forward(img, True, tape, want_grad=True)
+                holder.update(out)
+                return out['loss'], lambda: eng.backward(tape)
+
             holder = {}
-            params = [p for p in self.parameters() if p.requires_grad]
-            loss = _VQVAEFn.apply(eng, img, holder, *params)
+            loss = self._loss_node(run, holder)
             return {'loss': loss, 'code': holder['code'], 'img': holder['img']}
         with torch.no_grad():
             out = eng.forward(img, self.training)

@@ -21,6 +21,8 @@ import torch.nn.functional as F
 
 from . import ops
 from ._tuning import flag as _flag
+from .engine_base import EngineBase, _t1x1, _unwrap
+from .modules import MultimodalController
 from .ops import Seg, pad8
 
 _PAIR_GATES = _flag('MCGEN_PAIR_GATES', '1') != '0'      # a layer's two gates: BatchNorm statistics / activations as one launch each
@@ -28,43 +30,23 @@ _PAIR_GATES = _flag('MCGEN_PAIR_GATES', '1') != '0'      # a layer's two gates: 
 Tensor = torch.Tensor
 
 
-def _unwrap(mod):
-    """The module inside a reference `Wrapper` (MCPixelCNN), or the module itself (CPixelCNN has no wrappers)."""
-    return getattr(mod, 'module', mod)
+def _controller(seq, i: int):
+    """seq[i] if it is a MultimodalController, else None (CPixelCNN's chains have none)."""
+    return seq[i] if i < len(seq) and isinstance(seq[i], MultimodalController) else None
 
 
-def _t1x1(w: Tensor) -> Tensor:
-    """[Cout, Cin(,1,1)] -> transposed 1x1 master weight [Cin, Cout, 1, 1]."""
-    return w.reshape(w.shape[0], -1).t().contiguous().reshape(-1, w.shape[0], 1, 1)
+class PixelCNNEngine(EngineBase):
+    """The layer / head chain of both PixelCNNs.  The gates are the hooks a model without MultimodalControllers
+    (cpixelcnn_engine.py) overrides: _gates_fwd, _gate_bwd and _code_embed_bwd."""
+    _CONV_GATE_STATS = True              # the gates' BatchNorm statistics come from the two convolutions' epilogues
 
-
-class PixelCNNEngine:
     def __init__(self, model, dtype: torch.dtype = torch.float32):
-        self.m = model
-        self.dtype = dtype
-        self._gsink = None
+        super().__init__(model, dtype)
         if model.hidden_size % 8 != 0:
             raise ValueError('Not valid hidden size: the fused path needs a multiple of 8')
 
-    # ---- helpers -----------------------------------------------------------------------------------------------
-    def _grad(self, p: Tensor) -> Tensor:
-        if self._gsink is not None:
-            g = self._gsink.get(id(p))
-            if g is None:
-                g = self._gsink[id(p)] = torch.zeros_like(p)
-            return g
-        if p.grad is None:
-            p.grad = torch.zeros_like(p)
-        return p.grad
-
-    def _bn(self, bn, stats: Optional[Tensor], count: int, train: bool):
-        if train:
-            sc, sh, mean, rstd = ops.bn_finalize(stats, count, bn.weight.detach(), bn.bias.detach(), bn.running_mean,
-                                                 bn.running_var, bn.momentum, bn.eps)
-            self._nbt.append(bn.num_batches_tracked)       # bumped together at the end of the forward (46 launches -> 1)
-            return sc, sh, mean, rstd
-        sc, sh = ops.bn_eval_affine(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps)
-        return sc, sh, None, None
+    def _bump(self, num_batches_tracked: Tensor) -> None:
+        self._nbt.append(num_batches_tracked)       # bumped together at the end of the forward (46 launches -> 1)
 
     def _stack_weights(self, L):
         """Forward-orientation master weights of the two stacks as the fused kernel wants them.
@@ -111,8 +93,48 @@ class PixelCNNEngine:
         return images
 
     def _code(self, mc, label):
+        """The batch's code rows of a MultimodalController (None for a model without controllers)."""
+        if mc is None:
+            return None
         cached = getattr(self, '_codes', None)
         return cached[id(mc)] if cached is not None and id(mc) in cached else mc.code_of_labels(label)
+
+    def _bn_pair(self, bv, st_v, bh, st_s, count: int):
+        """Training-mode BatchNorm of a layer's two gates, finalized in one launch."""
+        bn_v, bn_h = ops.bn_finalize_batch([
+            (st_v, count, bv.weight.detach(), bv.bias.detach(), bv.running_mean, bv.running_var, bv.momentum, bv.eps),
+            (st_s, count, bh.weight.detach(), bh.bias.detach(), bh.running_mean, bh.running_var, bh.momentum, bh.eps)])
+        self._nbt += [bv.num_batches_tracked, bh.num_batches_tracked]
+        return bn_v, bn_h
+
+    # ---- model hooks: the gates and the code embedding's gradient -------------------------------------------------
+    def _gates_fwd(self, L, h_vert: Tensor, st_v, s: Tensor, st_s, label: Tensor, train: bool, count: int):
+        """-> (out_v, out_h, bn_v, bn_h, code_v, code_h): BN affine + ReLU, sigmoid gate, MC code."""
+        code_v, code_h = self._code(L.gate_v.mc, label), self._code(L.gate_h.mc, label)
+        if train and _PAIR_GATES:
+            # the two gates of a layer wait for the same two convolutions and for nothing else: their BatchNorm statistics in
+            # one launch, their activations in another (4 launches -> 2 per layer)
+            bn_v, bn_h = self._bn_pair(L.gate_v.bn, st_v, L.gate_h.bn, st_s, count)
+            out_v, out_h = ops.gated_fwd_batch([(h_vert, bn_v[0], bn_v[1], code_v), (s, bn_h[0], bn_h[1], code_h)])
+        else:
+            bn_v = self._bn(L.gate_v.bn, st_v, count, train)
+            bn_h = self._bn(L.gate_h.bn, st_s, count, train)
+            out_v = ops.gated_fwd(h_vert, bn_v[0], bn_v[1], code_v)
+            out_h = ops.gated_fwd(s, bn_h[0], bn_h[1], code_h)
+        return out_v, out_h, bn_v, bn_h, code_v, code_h
+
+    def _gate_bwd(self, L, gate, x: Tensor, bn, code, g: Optional[Tensor], label: Tensor, aux=None):
+        """Backward of one gate -> (gradient w.r.t. its input, or None without g; aux).  A layer calls it for gate_h, then
+        for gate_v with gate_h's aux."""
+        if g is None:
+            return None, None
+        sc, sh, mean, rstd = bn
+        return ops.gated_bwd(x, sc, sh, mean, rstd, code, g, self._grad(gate.bn.weight), self._grad(gate.bn.bias)), None
+
+    def _code_embed_bwd(self, d_x: Tensor, codes: Tensor):
+        ge = self._grad(self.m.embedding.weight)
+        ge.zero_()
+        ge.index_add_(0, codes.reshape(-1), d_x.reshape(-1, d_x.shape[-1]).float()[:, :ge.shape[1]])
 
     # ---- forward ------------------------------------------------------------------------------------------------
     def _layer_forward(self, L, x_v: Tensor, x_h: Tensor, label: Tensor, train: bool, tape, I, li):
@@ -120,6 +142,7 @@ class PixelCNNEngine:
         n, h, w, c = x_v.shape
         count = n * h * w
         sm = 1 if train else 0
+        sg = sm if self._CONV_GATE_STATS else 0
         if L.mask_type == 'A':
             L.make_causal()                                   # zeroes the parameters in place, as the reference does
         k2 = L.kernel // 2
@@ -133,32 +156,18 @@ class PixelCNNEngine:
             in_v = Seg(ops.im2col(x_v, k2 + 1, L.kernel, k2, k2), ksize=1)
             in_h = Seg(ops.im2col(x_h, 1, k2 + 1, 0, k2), ksize=1)
             img_v, img_h = ops.prep_weight(wv, dt), ops.prep_weight(wh, dt)
-        h_vert, st_v = ops.conv_fused([in_v], img_v, 2 * c, bias=L.vert_stack.bias.detach(), stats_mode=sm)
+        h_vert, st_v = ops.conv_fused([in_v], img_v, 2 * c, bias=L.vert_stack.bias.detach(), stats_mode=sg)
         wimg = I.get((li, 'v2h+h'))
         if wimg is None:
             wimg = torch.cat([I[(li, 'v2h')], img_h])
         s, st_s = ops.conv_fused([Seg(h_vert, ksize=1), in_h], wimg, 2 * c,
-                                 bias=L.vert_to_horiz.bias.detach(), bias2=L.horiz_stack.bias.detach(), stats_mode=sm)
-        code_v, code_h = self._code(L.gate_v.mc, label), self._code(L.gate_h.mc, label)
-        if train and _PAIR_GATES:
-            # the two gates of a layer wait for the same two convolutions and for nothing else: their BatchNorm statistics in
-            # one launch, their activations in another (4 launches -> 2 per layer)
-            bv, bh = L.gate_v.bn, L.gate_h.bn
-            bn_v, bn_h = ops.bn_finalize_batch([
-                (st_v, count, bv.weight.detach(), bv.bias.detach(), bv.running_mean, bv.running_var, bv.momentum, bv.eps),
-                (st_s, count, bh.weight.detach(), bh.bias.detach(), bh.running_mean, bh.running_var, bh.momentum, bh.eps)])
-            self._nbt += [bv.num_batches_tracked, bh.num_batches_tracked]
-            out_v, out_h = ops.gated_fwd_batch([(h_vert, bn_v[0], bn_v[1], code_v), (s, bn_h[0], bn_h[1], code_h)])
-        else:
-            bn_v = self._bn(L.gate_v.bn, st_v, count, train)
-            bn_h = self._bn(L.gate_h.bn, st_s, count, train)
-            out_v = ops.gated_fwd(h_vert, bn_v[0], bn_v[1], code_v)
-            out_h = ops.gated_fwd(s, bn_h[0], bn_h[1], code_h)
-        conv_r, bn_rm, mc_r = L.horiz_resid[0].module, L.horiz_resid[1].module, L.horiz_resid[2]
+                                 bias=L.vert_to_horiz.bias.detach(), bias2=L.horiz_stack.bias.detach(), stats_mode=sg)
+        out_v, out_h, bn_v, bn_h, code_v, code_h = self._gates_fwd(L, h_vert, st_v, s, st_s, label, train, count)
+        conv_r, bn_rm = _unwrap(L.horiz_resid[0]), _unwrap(L.horiz_resid[1])
         r, st_r = ops.conv_fused([Seg(out_h, ksize=1)], I[(li, 'r')], c,
                                  bias=conv_r.bias.detach(), stats_mode=sm)
         bn_r = self._bn(bn_rm, st_r, count, train)
-        code_r = self._code(mc_r, label)
+        code_r = self._code(_controller(L.horiz_resid, 2), label)
         x_h_new = ops.affine_code_res(r, bn_r[0], bn_r[1], code_r, x_h if L.residual else None)
         if tape is not None:
             tape.append(dict(in_v=in_v, in_h=in_h, h_vert=h_vert, s=s, out_h=out_h, r=r, bn_v=bn_v, bn_h=bn_h, bn_r=bn_r,
@@ -166,7 +175,7 @@ class PixelCNNEngine:
         return out_v, x_h_new
 
     def forward(self, codes: Tensor, label: Tensor, train: bool, tape=None, want_grad: bool = False):
-        """-> (loss, logits NHWC, dlogits or None).  `codes` int64 [N, H, W]."""
+        """-> (loss, logits NHWC, dlogits or None).  `codes` int64 [N, H, W], `label` int64 [N]."""
         m, dt = self.m, self.dtype
         n, h, w = codes.shape
         x = F.embedding(codes, m.embedding.weight.detach()).to(dt).contiguous()           # [N, H, W, C] is already NHWC
@@ -175,28 +184,29 @@ class PixelCNNEngine:
         self._nbt = []
         I = self._images(False)
         # every MultimodalController's code rows of this batch in one launch (a row gather per module: one_hot(label) @ codebook)
-        mcs = [mc for L in m.layers for mc in (L.gate_v.mc, L.gate_h.mc, L.horiz_resid[2])] + [m.output_conv[3]]
-        if getattr(self, '_code_batch', None) is None or [id(x_) for x_ in self._code_batch.mcs] != [id(x_) for x_ in mcs]:
-            self._code_batch = ops.CodeBatch(mcs)
-        self._codes = {id(mc): cd for mc, cd in zip(mcs, self._code_batch.run_labels(label))}
+        mcs = [mc for mc in m.modules() if isinstance(mc, MultimodalController)]
+        if mcs:
+            if getattr(self, '_code_batch', None) is None or [id(x_) for x_ in self._code_batch.mcs] != [id(x_) for x_ in mcs]:
+                self._code_batch = ops.CodeBatch(mcs)
+            self._codes = {id(mc): cd for mc, cd in zip(mcs, self._code_batch.run_labels(label))}
         for li, L in enumerate(m.layers):
             x_v, x_h = self._layer_forward(L, x_v, x_h, label, train, layers, I, li)
         oc = m.output_conv
-        conv0, bn0, mc0, conv4 = oc[0].module, oc[1].module, oc[3], oc[4].module
+        conv0, bn0, last = _unwrap(oc[0]), _unwrap(oc[1]), _unwrap(oc[-1])
         count = n * h * w
         h0, st0 = ops.conv_fused([Seg(x_h, ksize=1)], I[('head', 0)], conv0.out_channels,
                                  bias=conv0.bias.detach(), stats_mode=1 if train else 0)
         bn = self._bn(bn0, st0, count, train)
-        code0 = self._code(mc0, label)
+        code0 = self._code(_controller(oc, 3), label)
         logits, _ = ops.conv_fused([Seg(h0, ksize=1, scale=bn[0], shift=bn[1], relu=True, code=code0)],
-                                   I[('head', 4)], conv4.out_channels, bias=conv4.bias.detach())
+                                   I[('head', 4)], last.out_channels, bias=last.bias.detach())
         self._codes = None
         if self._nbt:
             torch._foreach_add_(self._nbt, 1)
         self._nbt = []
-        rows, dlogits = ops.cross_entropy(logits, codes.reshape(-1), conv4.out_channels, want_grad)
+        rows, dlogits = ops.cross_entropy(logits, codes.reshape(-1), last.out_channels, want_grad)
         if tape is not None:
-            tape.update(layers=layers, codes=codes, x_h=x_h, h0=h0, bn0=bn, code0=code0, dlogits=dlogits)
+            tape.update(layers=layers, codes=codes, label=label, x_h=x_h, h0=h0, bn0=bn, code0=code0, dlogits=dlogits)
         return rows.mean(), logits, dlogits
 
     # ---- backward -----------------------------------------------------------------------------------------------
@@ -212,16 +222,15 @@ class PixelCNNEngine:
             wt = ops.prep_weight_ex(conv.weight.detach(), dt, transpose=True, k_img=dy.shape[-1])
         return ops.conv_fused([Seg(dy, ksize=1)], wt, conv.in_channels, **dgrad_kw)
 
-    def _layer_backward(self, L, r, g_v: Optional[Tensor], g_h: Tensor, need_dx: bool, I, li):
+    def _layer_backward(self, L, r, g_v: Optional[Tensor], g_h: Tensor, need_dx: bool, I, li, label: Tensor):
         """g_v / g_h: gradients w.r.t. this layer's (out_v, x_h').  Returns gradients w.r.t. (x_v, x_h)."""
         dt = self.dtype
         c = L.hidden_size
-        conv_r, bn_rm = L.horiz_resid[0].module, L.horiz_resid[1].module
+        conv_r, bn_rm = _unwrap(L.horiz_resid[0]), _unwrap(L.horiz_resid[1])
         sc_r, _, mean_r, rstd_r = r['bn_r']
         d_r = ops.code_bn_bwd(g_h, r['code_r'], r['r'], sc_r, mean_r, rstd_r, self._grad(bn_rm.weight), self._grad(bn_rm.bias))
         d_out_h, _ = self._conv1x1_bwd(conv_r, Seg(r['out_h'], ksize=1), d_r, wt=I[(li, 'r')])
-        sc, sh, mean, rstd = r['bn_h']
-        ds = ops.gated_bwd(r['s'], sc, sh, mean, rstd, r['code_h'], d_out_h, self._grad(L.gate_h.bn.weight), self._grad(L.gate_h.bn.bias))
+        ds, aux = self._gate_bwd(L, L.gate_h, r['s'], r['bn_h'], r['code_h'], d_out_h, label)
         # s = vert_to_horiz(h_vert) + horiz_stack(x_h): both biases see sum(ds)
         c2 = 2 * c
         ops.wgrad(Seg(r['h_vert'], ksize=1), ds, c2, c2, self._grad(L.vert_to_horiz.weight), bias_grad=self._grad(L.vert_to_horiz.bias),
@@ -237,12 +246,8 @@ class PixelCNNEngine:
             gwh = torch.empty((c2, cin_h, in_h.ksize, in_h.ksize), dtype=torch.float32, device=ds.device)
             ops.wgrad(in_h, ds, c2, cin_h, gwh)
             self._post.append(lambda: gh.copy_(gwh.reshape(c2, 1, k2 + 1, c).permute(0, 3, 1, 2)))
-        # gate_v and the vertical stack
-        d_hv = None
-        if g_v is not None:
-            sc, sh, mean, rstd = r['bn_v']
-            d_hv = ops.gated_bwd(r['h_vert'], sc, sh, mean, rstd, r['code_v'], g_v, self._grad(L.gate_v.bn.weight),
-                                 self._grad(L.gate_v.bn.bias))
+        # gate_v (the last layer's out_v feeds nothing: g_v is None there) and the vertical stack
+        d_hv, _ = self._gate_bwd(L, L.gate_v, r['h_vert'], r['bn_v'], r['code_v'], g_v, label, aux)
         d_hv, _ = ops.conv_fused([Seg(ds, ksize=1)], I[(li, 'v2h')], c2, res=d_hv)
         in_v = r['in_v']
         cin_v = in_v.x.shape[-1]
@@ -279,24 +284,20 @@ class PixelCNNEngine:
         self._post = []
 
     def _backward_body(self, tape):
-        m, dt = self.m, self.dtype
+        m = self.m
         oc = m.output_conv
-        conv0, bn0, conv4 = oc[0].module, oc[1].module, oc[4].module
+        conv0, bn0, last = _unwrap(oc[0]), _unwrap(oc[1]), _unwrap(oc[-1])
         sc, sh, mean, rstd = tape['bn0']
         h0, code0 = tape['h0'], tape['code0']
-        # logits = conv4(code * relu(BN(h0))): input gradient through the gate with BN-backward sums in the epilogue
+        # logits = last(code * relu(BN(h0))): input gradient through the gate with BN-backward sums in the epilogue
         I = self._images(True)
-        dz, st = self._conv1x1_bwd(conv4, Seg(h0, ksize=1, scale=sc, shift=sh, relu=True, code=code0), tape['dlogits'], wt=I[('head', 4)],
+        dz, st = self._conv1x1_bwd(last, Seg(h0, ksize=1, scale=sc, shift=sh, relu=True, code=code0), tape['dlogits'], wt=I[('head', 4)],
                                    ocode=code0, gate_x=h0, gscale=sc, gshift=sh, gmean=mean, grstd=rstd, stats_mode=2)
         n, h, w, _ = h0.shape
         d_h0 = ops.bn_backward(st, dz, h0, n * h * w, sc, mean, rstd, self._grad(bn0.weight), self._grad(bn0.bias))
         g_h, _ = self._conv1x1_bwd(conv0, Seg(tape['x_h'], ksize=1), d_h0, wt=I[('head', 0)])
         g_v = None                                              # the last layer's out_v feeds nothing
-        layers = tape['layers']
-        d_emb = None
+        layers, label = tape['layers'], tape['label']
         for i in reversed(range(len(m.layers))):
-            g_v, g_h = self._layer_backward(m.layers[i], layers[i], g_v, g_h, True, I, i)
-        d_x = g_v + g_h                                          # layer 0: x_v and x_h are the same embedding output
-        ge = self._grad(m.embedding.weight)
-        ge.zero_()
-        ge.index_add_(0, tape['codes'].reshape(-1), d_x.reshape(-1, d_x.shape[-1]).float()[:, :ge.shape[1]])
+            g_v, g_h = self._layer_backward(m.layers[i], layers[i], g_v, g_h, True, I, i, label)
+        self._code_embed_bwd(g_v + g_h, tape['codes'])           # layer 0: x_v and x_h are the same embedding output

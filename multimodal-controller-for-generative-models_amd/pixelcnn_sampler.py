@@ -20,6 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, ops
+from .engine_base import _unwrap
 
 Tensor = torch.Tensor
 
@@ -36,10 +37,6 @@ def _mat(w: Tensor, rows: int, k: int) -> Tensor:
     """[R, K] -> zero-padded [rows, k] (the kernels' [Nout][Kp] weight images, K contiguous)."""
     w = w.reshape(w.shape[0], -1)
     return F.pad(w, (0, k - w.shape[1], 0, rows - w.shape[0]))
-
-
-def _unwrap(mod):
-    return getattr(mod, 'module', mod)
 
 
 def conditional(m) -> bool:

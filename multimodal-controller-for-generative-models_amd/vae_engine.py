@@ -20,58 +20,26 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from .engine_base import EngineBase, _padv, _t1x1, _t3x3
 from .ops import Seg, pad8
 
 Tensor = torch.Tensor
 
 
-def _t1x1(w: Tensor) -> Tensor:
-    return w.reshape(w.shape[0], -1).t().contiguous().reshape(-1, w.shape[0], 1, 1)
-
-
-def _t3x3(w: Tensor) -> Tensor:
-    return w.flip(2, 3).transpose(0, 1).contiguous()
-
-
-class VAEEngine:
-    def __init__(self, model, dtype: torch.dtype = torch.float32):
-        self.m = model
-        self.dtype = dtype
-        self._gsink = None
-        if any(h % 8 for h in model.hidden_size) or model.latent_size % 8:
-            raise ValueError('Not valid hidden/latent size: the fused path needs multiples of 8')
-        self._perm = None
-
-    # ---- helpers -----------------------------------------------------------------------------------------------
-    def _grad(self, p: Tensor) -> Tensor:
-        if self._gsink is not None:
-            g = self._gsink.get(id(p))
-            if g is None:
-                g = self._gsink[id(p)] = torch.zeros_like(p)
-            return g
-        if p.grad is None:
-            p.grad = torch.zeros_like(p)
-        return p.grad
+class ConvAEEngine(EngineBase):
+    """The strided-down, residual and transposed-up blocks MCVAE and VQ-VAE share.  `mc` / `mc3` / `mc6` are the
+    blocks' MultimodalControllers (their codes gate the BatchNorm outputs), None for VQ-VAE's plain blocks."""
 
     @staticmethod
-    def _bn(bn, stats: Optional[Tensor], count: int, train: bool):
-        if train:
-            sc, sh, mean, rstd = ops.bn_finalize(stats, count, bn.weight.detach(), bn.bias.detach(), bn.running_mean,
-                                                 bn.running_var, bn.momentum, bn.eps)
-            bn.num_batches_tracked += 1
-            return sc, sh, mean, rstd
-        sc, sh = ops.bn_eval_affine(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps)
-        return sc, sh, None, None
+    def _res_parts(blk):
+        """-> (conv, bn, mc, conv, bn, mc) of a residual block."""
+        c = blk.conv
+        return c[0].module, c[1].module, c[3], c[4].module, c[5].module, c[6]
 
-    def _flat_perm(self, device) -> Tensor:
-        """perm[p * C + c] = c * hw + p : NHWC feature index -> the reference's (c, h, w) flattening."""
-        if self._perm is None or self._perm.device != device:
-            c, h, w = self.m.encoder.encoded_shape
-            idx = torch.arange(c * h * w, device=device).reshape(c, h * w)
-            self._perm = idx.t().reshape(-1).contiguous()
-        return self._perm
+    @staticmethod
+    def _code(mc, label):
+        return None if mc is None else mc.code_of_labels(label)
 
-    # ---- building blocks -----------------------------------------------------------------------------------------
     def _down_fwd(self, conv, bn, mc, x: Tensor, label, train: bool, tape):
         dt = self.dtype
         cp = x.shape[-1]
@@ -82,7 +50,7 @@ class VAEEngine:
                                stats_mode=1 if train else 0)
         n, ho, wo, _ = h.shape
         b = self._bn(bn, st, n * ho * wo, train)
-        code = mc.code_of_labels(label)
+        code = self._code(mc, label)
         a = ops.affine_code_res(h, b[0], b[1], code, None, pre_relu=True)
         if tape is not None:
             tape.append(dict(kind='down', col=col, wm=wm, h=h, bn=b, code=code, cin_p=cp))
@@ -103,19 +71,19 @@ class VAEEngine:
         return ops.col2im(dcol, cp, 4, 4, 1, 1, stride=2)
 
     def _res_fwd(self, blk, x: Tensor, label, train: bool, tape):
+        """relu(BN(conv(relu(BN(conv(x))) * code3)) * code6 + x)."""
         dt = self.dtype
-        conv0, bn1m, mc3, conv4, bn5m, mc6 = (blk.conv[0].module, blk.conv[1].module, blk.conv[3], blk.conv[4].module,
-                                              blk.conv[5].module, blk.conv[6])
+        conv0, bn1m, mc3, conv4, bn5m, mc6 = self._res_parts(blk)
         c = conv0.out_channels
         n, h, w, _ = x.shape
         sm = 1 if train else 0
         h1, st1 = ops.conv_fused([Seg(x)], ops.prep_weight(conv0.weight.detach(), dt), c, bias=conv0.bias.detach(), stats_mode=sm)
         b1 = self._bn(bn1m, st1, n * h * w, train)
-        code3 = mc3.code_of_labels(label)
+        code3 = self._code(mc3, label)
         h2, st2 = ops.conv_fused([Seg(h1, scale=b1[0], shift=b1[1], relu=True, code=code3)],
                                  ops.prep_weight(conv4.weight.detach(), dt), c, bias=conv4.bias.detach(), stats_mode=sm)
         b2 = self._bn(bn5m, st2, n * h * w, train)
-        code6 = mc6.code_of_labels(label)
+        code6 = self._code(mc6, label)
         y = ops.affine_code_res(h2, b2[0], b2[1], code6, x, post_relu=True)
         if tape is not None:
             tape.append(dict(kind='res', x=x, h1=h1, b1=b1, code3=code3, h2=h2, b2=b2, code6=code6, y=y))
@@ -123,7 +91,7 @@ class VAEEngine:
 
     def _res_bwd(self, blk, r, g: Tensor):
         dt = self.dtype
-        conv0, bn1m, conv4, bn5m = blk.conv[0].module, blk.conv[1].module, blk.conv[4].module, blk.conv[5].module
+        conv0, bn1m, _, conv4, bn5m, _ = self._res_parts(blk)
         c = conv0.out_channels
         sc2, sh2, mean2, rstd2 = r['b2']
         d_h2, g_res = ops.code_bn_bwd(g, r['code6'], r['h2'], sc2, mean2, rstd2, self._grad(bn5m.weight), self._grad(bn5m.bias),
@@ -168,6 +136,45 @@ class VAEEngine:
             return None
         dx, _ = ops.conv_fused([Seg(ddcol, ksize=1)], ops.prep_weight(_t1x1(r['wm']), dt), ci)
         return dx
+
+    def _uptail_fwd(self, out: Tensor, bn, mc, label, train: bool, tape):
+        """relu(BN(out)) * code after a transposed convolution; out's padding channels stay zero."""
+        nb, ho, wo, cp = out.shape
+        b = self._bn(bn, ops.channel_stats(out) if train else None, nb * ho * wo, train)
+        code = self._code(mc, label)
+        if code is not None and code.shape[1] != cp:
+            code = F.pad(code, (0, cp - code.shape[1]))
+        x = ops.affine_code_res(out, _padv(b[0], cp), _padv(b[1], cp), code, None, pre_relu=True)
+        if tape is not None:
+            tape.append(dict(kind='uptail', out=out, bn=b, code=code))
+        return x
+
+    def _uptail_bwd(self, bn, tail, g: Tensor) -> Tensor:
+        sc, sh, mean, rstd = tail['bn']
+        cp = tail['out'].shape[-1]
+        co = bn.weight.numel()
+        dgam = torch.zeros(cp, dtype=torch.float32, device=g.device)
+        dbet = torch.zeros(cp, dtype=torch.float32, device=g.device)
+        d_out = ops.code_bn_bwd(g, tail['code'], tail['out'], _padv(sc, cp), _padv(mean, cp), _padv(rstd, cp),
+                                dgam, dbet, shift=_padv(sh, cp), pre_relu=True)
+        self._grad(bn.weight).copy_(dgam[:co]); self._grad(bn.bias).copy_(dbet[:co])
+        return d_out
+
+
+class VAEEngine(ConvAEEngine):
+    def __init__(self, model, dtype: torch.dtype = torch.float32):
+        super().__init__(model, dtype)
+        if any(h % 8 for h in model.hidden_size) or model.latent_size % 8:
+            raise ValueError('Not valid hidden/latent size: the fused path needs multiples of 8')
+        self._perm = None
+
+    def _flat_perm(self, device) -> Tensor:
+        """perm[p * C + c] = c * hw + p : NHWC feature index -> the reference's (c, h, w) flattening."""
+        if self._perm is None or self._perm.device != device:
+            c, h, w = self.m.encoder.encoded_shape
+            idx = torch.arange(c * h * w, device=device).reshape(c, h * w)
+            self._perm = idx.t().reshape(-1).contiguous()
+        return self._perm
 
     # ---- forward -------------------------------------------------------------------------------------------------
     def encode(self, img01: Tensor, label: Tensor, train: bool, eps: Optional[Tensor], tape):
@@ -231,20 +238,9 @@ class VAEEngine:
         k = 1 + nr
         for _ in range(ns - 1):
             out = self._up_fwd(blocks[k].module, x, tape)
-            nb, ho, wo, _ = out.shape
-            bn = blocks[k + 1].module
-            b = self._bn(bn, ops.channel_stats(out) if train else None, nb * ho * wo, train)
-            code = blocks[k + 3].code_of_labels(label)
-            code = F.pad(code, (0, out.shape[-1] - code.shape[1])) if code.shape[1] != out.shape[-1] else code
-            x = ops.affine_code_res(out, self._padv(b[0], out.shape[-1]), self._padv(b[1], out.shape[-1]), code, None, pre_relu=True)
-            if tape is not None:
-                tape.append(dict(kind='uptail', out=out, bn=b, code=code))
+            x = self._uptail_fwd(out, blocks[k + 1].module, blocks[k + 3], label, train, tape)
             k += 4
         return self._up_fwd(blocks[k].module, x, tape)                           # logits of the final Sigmoid
-
-    @staticmethod
-    def _padv(v: Tensor, n: int) -> Tensor:
-        return v if v.numel() == n else F.pad(v, (0, n - v.numel()))
 
     def forward(self, img: Tensor, label: Tensor, train: bool, eps: Optional[Tensor] = None, tape=None, want_grad: bool = False):
         """-> dict(loss, mu, logvar, img) with img back in (-1, 1) as NCHW fp32 (mcvae.py:133-144)."""
@@ -279,16 +275,7 @@ class VAEEngine:
         k = k_last
         for _ in range(ns - 1):
             k -= 4
-            tail = recs.pop()
-            bn = dblocks[k + 1].module
-            sc, sh, mean, rstd = tail['bn']
-            cp = tail['out'].shape[-1]
-            co = bn.weight.numel()
-            dgam = torch.zeros(cp, dtype=torch.float32, device=g.device)
-            dbet = torch.zeros(cp, dtype=torch.float32, device=g.device)
-            d_out = ops.code_bn_bwd(g, tail['code'], tail['out'], self._padv(sc, cp), self._padv(mean, cp), self._padv(rstd, cp),
-                                    dgam, dbet, shift=self._padv(sh, cp), pre_relu=True)
-            self._grad(bn.weight).copy_(dgam[:co]); self._grad(bn.bias).copy_(dbet[:co])
+            d_out = self._uptail_bwd(dblocks[k + 1].module, recs.pop(), g)
             g = self._up_bwd(dblocks[k].module, recs.pop(), d_out)
         for r in reversed(range(nr)):
             g = self._res_bwd(dblocks[1 + r], recs.pop(), g)

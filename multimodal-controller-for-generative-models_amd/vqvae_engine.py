@@ -18,54 +18,26 @@ decoder input gradient plus vq_commit * 2 (f - q) / numel, which rides into the 
 from __future__ import annotations
 
 import torch
-import torch.nn.functional as F
 
 from . import ops
-from .ops import Seg, pad8
+from .engine_base import _t3x3
+from .ops import Seg
+from .vae_engine import ConvAEEngine
 
 Tensor = torch.Tensor
 
 
-def _t1x1(w: Tensor) -> Tensor:
-    return w.reshape(w.shape[0], -1).t().contiguous().reshape(-1, w.shape[0], 1, 1)
-
-
-def _t3x3(w: Tensor) -> Tensor:
-    return w.flip(2, 3).transpose(0, 1).contiguous()
-
-
-class VQVAEEngine:
+class VQVAEEngine(ConvAEEngine):
     def __init__(self, model, dtype: torch.dtype = torch.float32):
-        self.m = model
-        self.dtype = dtype
-        self._gsink = None
+        super().__init__(model, dtype)
         if any(h % 8 for h in model.hidden_size) or model.embedding_size % 8:
             raise ValueError('Not valid hidden/embedding size: the fused path needs multiples of 8')
 
-    # ---- helpers -----------------------------------------------------------------------------------------------
-    def _grad(self, p: Tensor) -> Tensor:
-        if self._gsink is not None:
-            g = self._gsink.get(id(p))
-            if g is None:
-                g = self._gsink[id(p)] = torch.zeros_like(p)
-            return g
-        if p.grad is None:
-            p.grad = torch.zeros_like(p)
-        return p.grad
-
     @staticmethod
-    def _bn(bn, stats, count: int, train: bool):
-        if train:
-            sc, sh, mean, rstd = ops.bn_finalize(stats, count, bn.weight.detach(), bn.bias.detach(), bn.running_mean,
-                                                 bn.running_var, bn.momentum, bn.eps)
-            bn.num_batches_tracked += 1
-            return sc, sh, mean, rstd
-        sc, sh = ops.bn_eval_affine(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps)
-        return sc, sh, None, None
-
-    @staticmethod
-    def _padv(v, n: int):
-        return v if v is None or v.numel() == n else F.pad(v, (0, n - v.numel()))
+    def _res_parts(blk):
+        """relu(BN(conv(relu(BN(conv(x))))) + x)  (vqvae.py:21-24): no controllers."""
+        c = blk.conv
+        return c[0], c[1], None, c[3], c[4], None
 
     # ---- building blocks -----------------------------------------------------------------------------------------
     def _conv3_fwd(self, conv, bn, x: Tensor, train: bool, tape, kind: str):
@@ -93,99 +65,6 @@ class VQVAEEngine:
         dx, _ = ops.conv_fused([Seg(g)], ops.prep_weight(_t3x3(conv.weight.detach()), dt), conv.in_channels, res=res)
         return dx
 
-    def _down_fwd(self, conv, bn, x: Tensor, train: bool, tape):
-        dt = self.dtype
-        cp = x.shape[-1]
-        col = ops.im2col(x, 4, 4, 1, 1, stride=2)
-        w = conv.weight.detach().permute(0, 2, 3, 1)                            # [co, 4, 4, ci]
-        wm = F.pad(w, (0, cp - w.shape[-1])).reshape(w.shape[0], 16 * cp, 1, 1).contiguous()
-        h, st = ops.conv_fused([Seg(col, ksize=1)], ops.prep_weight(wm, dt), conv.out_channels, bias=conv.bias.detach(),
-                               stats_mode=1 if train else 0)
-        n, ho, wo, _ = h.shape
-        b = self._bn(bn, st, n * ho * wo, train)
-        a = ops.affine_code_res(h, b[0], b[1], None, None, pre_relu=True)
-        if tape is not None:
-            tape.append(dict(kind='down', col=col, wm=wm, h=h, bn=b, cin_p=cp))
-        return a
-
-    def _down_bwd(self, conv, bn, r, g: Tensor, need_dx: bool):
-        dt = self.dtype
-        sc, sh, mean, rstd = r['bn']
-        d_h = ops.code_bn_bwd(g, None, r['h'], sc, mean, rstd, self._grad(bn.weight), self._grad(bn.bias), shift=sh, pre_relu=True)
-        co, cp = conv.out_channels, r['cin_p']
-        gw = torch.empty((co, 16 * cp), dtype=torch.float32, device=g.device)
-        ops.wgrad(Seg(r['col'], ksize=1), d_h, co, 16 * cp, gw, bias_grad=self._grad(conv.bias))
-        self._grad(conv.weight).copy_(gw.view(co, 4, 4, cp)[..., :conv.in_channels].permute(0, 3, 1, 2))
-        if not need_dx:
-            return None
-        wt = F.pad(_t1x1(r['wm']), (0, 0, 0, 0, 0, d_h.shape[-1] - co)).contiguous()
-        dcol, _ = ops.conv_fused([Seg(d_h, ksize=1)], ops.prep_weight(wt, dt), 16 * cp)
-        return ops.col2im(dcol, cp, 4, 4, 1, 1, stride=2)
-
-    def _res_fwd(self, blk, x: Tensor, train: bool, tape):
-        """relu(BN(conv(relu(BN(conv(x))))) + x)  (vqvae.py:21-24)."""
-        dt = self.dtype
-        conv0, bn1, conv3, bn4 = blk.conv[0], blk.conv[1], blk.conv[3], blk.conv[4]
-        c = conv0.out_channels
-        n, h, w, _ = x.shape
-        sm = 1 if train else 0
-        h1, st1 = ops.conv_fused([Seg(x)], ops.prep_weight(conv0.weight.detach(), dt), c, bias=conv0.bias.detach(), stats_mode=sm)
-        b1 = self._bn(bn1, st1, n * h * w, train)
-        h2, st2 = ops.conv_fused([Seg(h1, scale=b1[0], shift=b1[1], relu=True)], ops.prep_weight(conv3.weight.detach(), dt), c,
-                                 bias=conv3.bias.detach(), stats_mode=sm)
-        b2 = self._bn(bn4, st2, n * h * w, train)
-        y = ops.affine_code_res(h2, b2[0], b2[1], None, x, post_relu=True)
-        if tape is not None:
-            tape.append(dict(kind='res', x=x, h1=h1, b1=b1, h2=h2, b2=b2, y=y))
-        return y
-
-    def _res_bwd(self, blk, r, g: Tensor):
-        dt = self.dtype
-        conv0, bn1, conv3, bn4 = blk.conv[0], blk.conv[1], blk.conv[3], blk.conv[4]
-        c = conv0.out_channels
-        sc2, sh2, mean2, rstd2 = r['b2']
-        d_h2, g_res = ops.code_bn_bwd(g, None, r['h2'], sc2, mean2, rstd2, self._grad(bn4.weight), self._grad(bn4.bias),
-                                      y_post=r['y'], want_gated=True)
-        sc1, sh1, mean1, rstd1 = r['b1']
-        h1, x = r['h1'], r['x']
-        ops.wgrad(Seg(h1, scale=sc1, shift=sh1, relu=True), d_h2, c, c, self._grad(conv3.weight), bias_grad=self._grad(conv3.bias))
-        dz1, st = ops.conv_fused([Seg(d_h2)], ops.prep_weight(_t3x3(conv3.weight.detach()), dt), c, gate_x=h1,
-                                 gscale=sc1, gshift=sh1, gmean=mean1, grstd=rstd1, stats_mode=2)
-        n, h, w, _ = h1.shape
-        d_h1 = ops.bn_backward(st, dz1, h1, n * h * w, sc1, mean1, rstd1, self._grad(bn1.weight), self._grad(bn1.bias))
-        ops.wgrad(Seg(x), d_h1, c, c, self._grad(conv0.weight), bias_grad=self._grad(conv0.bias))
-        dx, _ = ops.conv_fused([Seg(d_h1)], ops.prep_weight(_t3x3(conv0.weight.detach()), dt), c, res=g_res)
-        return dx
-
-    def _up_fwd(self, convt, x: Tensor, tape):
-        """ConvTranspose2d(ci, co, 4, 2, 1) -> pre-activation output [N, 2h, 2w, pad8(co)]."""
-        dt = self.dtype
-        co = convt.out_channels
-        cop = pad8(co)
-        w = convt.weight.detach().permute(2, 3, 1, 0)                           # [4, 4, co, ci]
-        wm = F.pad(w, (0, 0, 0, cop - co)).reshape(16 * cop, w.shape[-1], 1, 1).contiguous()
-        dcol, _ = ops.conv_fused([Seg(x, ksize=1)], ops.prep_weight(wm, dt), 16 * cop)
-        out = ops.col2im(dcol, cop, 4, 4, 1, 1, stride=2, bias=convt.bias.detach())
-        if tape is not None:
-            tape.append(dict(kind='up', x=x, wm=wm, out=out))
-        return out
-
-    def _up_bwd(self, convt, r, d_out: Tensor, need_dx: bool = True):
-        dt = self.dtype
-        co, ci = convt.out_channels, convt.in_channels
-        cop = d_out.shape[-1]
-        ops.colsum(d_out, co, self._grad(convt.bias))
-        ddcol = ops.im2col(d_out, 4, 4, 1, 1, stride=2)
-        x = r['x']
-        cip = x.shape[-1]
-        gw = torch.empty((16 * cop, cip), dtype=torch.float32, device=d_out.device)
-        ops.wgrad(Seg(x, ksize=1), ddcol, 16 * cop, cip, gw)
-        self._grad(convt.weight).copy_(gw.view(4, 4, cop, cip)[:, :, :co, :ci].permute(3, 2, 0, 1))
-        if not need_dx:
-            return None
-        dx, _ = ops.conv_fused([Seg(ddcol, ksize=1)], ops.prep_weight(_t1x1(r['wm']), dt), ci)
-        return dx
-
     # ---- forward -------------------------------------------------------------------------------------------------
     def encode(self, img: Tensor, train: bool, tape):
         """-> encoder output [N, H, W, D] in the compute dtype (vqvae.py:27-47)."""
@@ -194,9 +73,9 @@ class VQVAEEngine:
         blocks = m.encoder.blocks
         x = ops.to_nhwc(img.contiguous(), self.dtype)
         for i in range(ns):
-            x = self._down_fwd(blocks[3 * i], blocks[3 * i + 1], x, train, tape)
+            x = self._down_fwd(blocks[3 * i], blocks[3 * i + 1], None, x, None, train, tape)
         for r in range(nr):
-            x = self._res_fwd(blocks[3 * ns + r], x, train, tape)
+            x = self._res_fwd(blocks[3 * ns + r], x, None, train, tape)
         return self._conv3_fwd(blocks[3 * ns + nr], None, x, train, tape, 'enc_out')
 
     def quantize(self, feat: Tensor, train: bool, want_grad: bool, want_counts: bool = False):
@@ -220,15 +99,11 @@ class VQVAEEngine:
         blocks = m.decoder.blocks
         x = self._conv3_fwd(blocks[0], blocks[1], q, train, tape, 'dec_in')
         for r in range(nr):
-            x = self._res_fwd(blocks[3 + r], x, train, tape)
+            x = self._res_fwd(blocks[3 + r], x, None, train, tape)
         k = 3 + nr
         for _ in range(ns - 1):
             out = self._up_fwd(blocks[k], x, tape)
-            nb, ho, wo, cp = out.shape
-            b = self._bn(blocks[k + 1], ops.channel_stats(out) if train else None, nb * ho * wo, train)
-            x = ops.affine_code_res(out, self._padv(b[0], cp), self._padv(b[1], cp), None, None, pre_relu=True)
-            if tape is not None:
-                tape.append(dict(kind='uptail', out=out, bn=b))
+            x = self._uptail_fwd(out, blocks[k + 1], None, None, train, tape)
             k += 3
         return self._up_fwd(blocks[k], x, tape)
 
@@ -263,16 +138,7 @@ class VQVAEEngine:
         g = self._up_bwd(dec[k], recs.pop(), loss_rec['dpre'])
         for _ in range(ns - 1):
             k -= 3
-            tail = recs.pop()
-            bn = dec[k + 1]
-            sc, sh, mean, rstd = tail['bn']
-            cp = tail['out'].shape[-1]
-            co = bn.weight.numel()
-            dgam = torch.zeros(cp, dtype=torch.float32, device=g.device)
-            dbet = torch.zeros(cp, dtype=torch.float32, device=g.device)
-            d_out = ops.code_bn_bwd(g, None, tail['out'], self._padv(sc, cp), self._padv(mean, cp), self._padv(rstd, cp),
-                                    dgam, dbet, shift=self._padv(sh, cp), pre_relu=True)
-            self._grad(bn.weight).copy_(dgam[:co]); self._grad(bn.bias).copy_(dbet[:co])
+            d_out = self._uptail_bwd(dec[k + 1], recs.pop(), g)
             g = self._up_bwd(dec[k], recs.pop(), d_out)
         for r in reversed(range(nr)):
             g = self._res_bwd(dec[3 + r], recs.pop(), g)
