@@ -7,11 +7,13 @@ GPU: 5 discriminator updates + 1 generator update (hinge loss, 2 x Adam), G [256
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
 
-Prints ONE JSON line (rank 0) with the throughput, a `roofline` object for the dominant kernel
-(per-launch HIP-event timing of an instrumented pass of the same step) and a `cpu_baseline` object
-(the CPU oracle timed on this host's cores, N=1 only).  `--dump-outputs DIR` also writes what the last timed
-step computed (its losses and the state_dict it left in the model) as DIR/<name>.npy: the inputs are seeded, so two
-builds run with the same arguments can be compared output for output.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the throughput; its
+`roofline`, `cpu_baseline`, `sustained_ms_per_step` and (N > 1) `comm` fields are null.  `--full` adds what takes
+runs of its own after the timed region: the sustained-clock loop (`--sustain-steps`), the gradient all-reduce overlap
+(N > 1), a `roofline` object for the dominant kernel (per-launch HIP-event timing of an instrumented pass of the same
+step) and a `cpu_baseline` object (the CPU oracle timed on this host's cores, N=1 only).  `--dump-outputs DIR` also
+writes what the last timed step computed (its losses and the state_dict it left in the model) as DIR/<name>.npy: the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -288,7 +290,7 @@ def bench_mcglow(a, dev, dtype, world, rank, group):
     if a.dump_outputs and rank == 0:
         dump_outputs(a.dump_outputs, step_outputs({'loss': loss}, model))
     roofline = None
-    if not a.no_roofline and rank == 0:
+    if a.full and not a.no_roofline and rank == 0:
         roofline = profile_alone(tr, lambda: tr._eager(img, lab, torch.rand_like(img)), PEAK_TFLOPS[a.dtype])
     if rank == 0:
         print(json.dumps({
@@ -352,7 +354,7 @@ def bench_mcvae(a, dev, dtype, world, rank, group):
     if a.dump_outputs and rank == 0:
         dump_outputs(a.dump_outputs, step_outputs({'loss': loss}, model))
     roofline = None
-    if not a.no_roofline and rank == 0:
+    if a.full and not a.no_roofline and rank == 0:
         eps = torch.randn(a.batch, model.latent_size, device=dev)
         roofline = profile_alone(tr, lambda: tr._eager(img, lab, eps), PEAK_TFLOPS[a.dtype])
     if rank == 0:
@@ -417,7 +419,7 @@ def bench_mcpixelcnn(a, dev, dtype, world, rank, group):
     if a.dump_outputs and rank == 0:
         dump_outputs(a.dump_outputs, step_outputs({'loss': loss}, model))
     roofline = None
-    if not a.no_roofline and rank == 0:
+    if a.full and not a.no_roofline and rank == 0:
         roofline = profile_alone(tr, lambda: tr._eager(codes, lab), PEAK_TFLOPS[a.dtype])
     if rank == 0:
         print(json.dumps({
@@ -451,10 +453,13 @@ def main():
     ap.add_argument('--workload', default='cifar10', choices=['cifar10', 'coil100', 'mcglow', 'mcglow-cifar10', 'mcpixelcnn', 'mcvae'],
                     help='cifar10 = the headline config (BASELINE configs[1]); coil100 = configs[2] as the reference runs it (32x32, 100 modes)')
     ap.add_argument('--no-graph', action='store_true')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also run the sustained-clock loop, the N > 1 overlap probe, the roofline '
+                         'pass and the CPU baseline (off: their fields in the line are null)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-roofline', action='store_true', help='--full without the roofline pass')
     ap.add_argument('--sustain-steps', type=int, default=1000,
-                    help='extra untimed-for-the-headline steps after the timed region, reported as sustained_ms_per_step')
+                    help='--full: extra untimed-for-the-headline steps after the timed region, reported as sustained_ms_per_step')
     ap.add_argument('--pool', type=int, default=64, help='distinct synthetic batches (images + label sets) the loop cycles through')
     ap.add_argument('--real-data', default='generator', choices=['generator', 'uniform'],
                     help="the pool's images: samples of the initial generator (default: keeps the GAN game non-degenerate) or U(-1,1) pixels")
@@ -463,7 +468,7 @@ def main():
                          "generator-drawn pool the discriminator loss stays in 0.1-1.2 over 600+ iterations); the copies run "
                          'inside the timed region')
     ap.add_argument('--grad-bf16', action='store_true', help='N > 1: gradient buckets cross the links as bf16 (off: fp32, as the reference sums them)')
-    ap.add_argument('--roofline-passes', type=int, default=5, help='instrumented eager iterations the roofline object averages')
+    ap.add_argument('--roofline-passes', type=int, default=5, help='--full: instrumented eager iterations the roofline object averages')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last one returned (losses) and left in the model (state_dict) '
                          'as DIR/<name>.npy, at most 64 MB in all (rank 0)')
@@ -551,7 +556,9 @@ def main():
     # losses of EVERY iteration are kept (`loss_trace`) to show that the step never degenerates into all-zero hinge
     # gradients (measured with the default pool: D_loss 0.1-1.2 over 625 iterations without any reset).
     snap = tr.device_snapshot()
-    total_its = a.warmup + a.steps + max(0, a.sustain_steps) + (5 if world > 1 else 0)
+    sustain_steps = max(0, a.sustain_steps) if a.full else 0
+    probe_overlap = a.full and world > 1
+    total_its = a.warmup + a.steps + sustain_steps + (5 if probe_overlap else 0)
     trace = torch.zeros(total_its + 1, 2, device=dev)
     it = 0
 
@@ -586,17 +593,17 @@ def main():
         dump_outputs(a.dump_outputs, step_outputs({'d_loss': dl, 'g_loss': gl}, model))
     # the same loop for >= 9 s more: sustained clocks, and long enough for an outside sampler to see the GPU busy
     sustained = None
-    if a.sustain_steps > 0:
+    if sustain_steps > 0:
         barrier()
         t1 = time.perf_counter()
-        for _ in range(a.sustain_steps):
+        for _ in range(sustain_steps):
             step()
         barrier()
-        sustained = 1e3 * (time.perf_counter() - t1) / a.sustain_steps
-        log(f'sustained check: {sustained:.3f} ms/step over {a.sustain_steps} steps')
+        sustained = 1e3 * (time.perf_counter() - t1) / sustain_steps
+        log(f'sustained check: {sustained:.3f} ms/step over {sustain_steps} steps')
     # N > 1: how much of the gradient all-reduce time hides under the backward pass (a few extra, untimed iterations)
     overlap = None
-    if world > 1:
+    if probe_overlap:
         barrier()
         tr.overlap_begin()
         n_ov = 5
@@ -618,7 +625,7 @@ def main():
     }
 
     roofline = None
-    if not a.no_roofline and rank == 0:
+    if a.full and not a.no_roofline and rank == 0:
         def eager_pass(i):
             # same schedule as the timed loop: fresh batch, state re-loaded on the reset period
             if a.reset_every > 0 and (i + 1) % a.reset_every == 0:
@@ -627,9 +634,9 @@ def main():
             tr.eager_iteration(imgs[k], labs[k])
         tr.device_restore(snap)
         roofline = profile_alone(tr, eager_pass, PEAK_TFLOPS[a.dtype], iters=a.roofline_passes)
-    log('roofline pass done')
+        log('roofline pass done')
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.workload == 'cifar10':
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.workload == 'cifar10':
         cpu = cpu_baseline(sd, a.batch)
 
     if rank == 0:
@@ -650,10 +657,10 @@ def main():
             # figures of roofline.by_kernel count what the launch actually multiplies
             'mask_compaction': bool(_mask_compaction(a.dtype)),
             'step_mfma_frac': value / world * FLOP_PER_IMAGE[a.workload] / (PEAK_TFLOPS[a.dtype] * 1e12),
-            'last_losses': losses, 'loss_trace': loss_trace, 'sustained_ms_per_step': sustained, 'sustain_steps': a.sustain_steps,
+            'last_losses': losses, 'loss_trace': loss_trace, 'sustained_ms_per_step': sustained, 'sustain_steps': sustain_steps,
             'data_pool': {'batches': pool, 'reset_every': a.reset_every, 'real_data': a.real_data},
             # rank 0's view, per iteration: comm_us = time its gradient all-reduces ran, overlap_us = the part hidden under
-            # the backward pass, exposed_us = the part the optimizer step waited for (None on one GPU)
+            # the backward pass, exposed_us = the part the optimizer step waited for (None on one GPU or without --full)
             'overlap_us': overlap['overlap_us'] if overlap else None, 'comm': overlap,
             'grad_wire_dtype': 'bf16' if a.grad_bf16 else 'f32',
             'tuning_switches': dict(_tuning_active()),

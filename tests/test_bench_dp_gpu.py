@@ -21,7 +21,7 @@ def test_bench_two_ranks_one_card(workload, batch, extra):
     env = dict(os.environ, MCGEN_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', '29533', os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--workload', workload, '--steps', '2',
-           '--warmup', '1', '--batch', str(batch), '--sustain-steps', '0'] + extra
+           '--warmup', '1', '--batch', str(batch), '--full', '--sustain-steps', '0'] + extra
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -40,7 +40,7 @@ def test_bench_default_path_replays_graphs(workload):
     """The single-GPU bench command at its real batch: the HIP-graph capture must succeed (an eager fall-back would still
     print a line -- `config.graph_replay` says which path was timed) and the line carries the contract's keys."""
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', workload, '--steps', '3', '--warmup', '1',
-           '--no-cpu-baseline', '--sustain-steps', '0']
+           '--full', '--no-cpu-baseline', '--sustain-steps', '0']
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
@@ -48,6 +48,21 @@ def test_bench_default_path_replays_graphs(workload):
     assert out['n_gpus'] == 1 and out['value'] > 0 and out['mask_compaction'] is True
     rf = out['roofline']
     assert rf['unit'] in ('TFLOP/s', 'GB/s') and 0 < rf['frac'] < 1 and rf['bound'] in ('mfma', 'hbm')
+
+
+def test_bench_plain_run_is_headline_only():
+    """Without --full the line carries the headline figure and nothing that needs runs of its own: no sustained loop, no
+    roofline pass, no CPU baseline; the iterations it ran are the warm-up and the timed steps."""
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1']
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
+    assert out['metric'] == 'images/sec (train step) MCGAN CIFAR-10 32x32' and out['unit'] == 'images/s'
+    assert out['higher_is_better'] is True and out['dtype'] == 'bf16' and out['steps'] == 3 and out['warmup'] == 1
+    assert out['value'] > 0 and abs(out['value'] * out['ms_per_step'] - 128 * 1e3) < 1e-6 * 128 * 1e3
+    assert out['config']['graph_replay'] is True, r.stderr[-3000:]
+    assert out['roofline'] is None and out['cpu_baseline'] is None and out['comm'] is None
+    assert out['sustained_ms_per_step'] is None and out['sustain_steps'] == 0 and out['loss_trace']['iterations'] == 4
 
 
 def test_bench_dump_outputs_last_timed_step(tmp_path):

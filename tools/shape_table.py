@@ -8,7 +8,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 env = dict(os.environ, MCGEN_PROF_SHAPES='1')
-out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--no-cpu-baseline', '--sustain-steps', '0',
+out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--no-cpu-baseline', '--sustain-steps', '0',
                       '--steps', '5', '--warmup', '2'] + sys.argv[1:], env=env, capture_output=True, text=True)
 line = [l for l in out.stdout.splitlines() if l.startswith('{')][-1]
 r = json.loads(line)['roofline']
