@@ -736,6 +736,37 @@ int mcgen_cpx_gather_rows(const float* tables, const int64_t* label, float* out,
 int mcgen_cpx_sample_row(const mcgen_px_sample_t* p, int i, int dtype, void* stream);
 int mcgen_cpx_sample_col(const mcgen_px_sample_t* p, int i, int j, int dtype, void* stream);
 
+/* ---- CVAE label embedding (csrc/cvae_ops.hip) ------------------------------------------------------------------------
+ * The reference's CVAE (models/cvae.py) concatenates a label embedding W[:, label] (W = embedding.weight [E, M] fp32) to the
+ * encoder's input image, broadcast over the pixels, and to the latent in front of the decoder's Linear.  int64 labels; a
+ * label outside [0, M) gives a zero embedding row and no gradient.  Every reduction is fixed-order with no float atomics.
+ * The table gradients are mcgen_cgan_embed_bwd over the dE rows below.
+ * mcgen_cvae_enc_input: out [N, HW, Cp] (compute dtype) = [(img + 1) / 2 (C) | W[:, label_n] (E) | 0] from the NCHW fp32
+ * image img [N, C, HW] in (-1, 1).  E <= 4096. */
+int mcgen_cvae_enc_input(const float* img, const float* w, const int64_t* label, void* out, int dtype, int N, int HW, int C,
+                         int E, int M, int Cp, void* stream);
+/* de [N, E] fp32: the encoder embedding's input gradient through Conv2d(Cin, C, 4, 2, 1) without the convolution's input
+ * gradient, from part [N, H, 3, C] (mcgen_cgan_dis_window_sums of the convolution's output gradient, H output rows):
+ *   de[n][e] = sum_{kh, kw} sum_co w[co][Cimg + e][kh][kw] * S_n[kh][kw][co]
+ * S_n[kh][kw] = the sum of the output gradient over the output pixels where tap (kh, kw) reads inside the (even-sized)
+ * image: tap 0 all rows / columns but the first, tap 3 all but the last, taps 1 and 2 every one.  w fp32 [C, Cin, 4, 4].
+ * E divides 256; C <= 960. */
+int mcgen_cvae_enc_dembed(const float* part, const float* w, float* de, int N, int H, int C, int Cin, int Cimg, int E,
+                          void* stream);
+/* The latent step.  ml [N] rows of pitch ldm = [mu (L) | logvar (L)] in the compute dtype (the head's output); eps [N, L] fp32
+ * or NULL (evaluation: z = mu).  Writes mu / logvar [N, L] fp32, zrow [N, Cp] (compute dtype) =
+ * [z = mu + eps * exp(logvar / 2) (L) | W[:, label_n] (E) | 0], kl [N] = 0.5 * sum_j (mu^2 + exp(logvar) - 1 - logvar) per
+ * sample and kld [1] = their sum in ascending n (a second one-thread launch). */
+int mcgen_cvae_latent_fwd(const void* ml, int ldm, const float* eps, const float* w, const int64_t* label, float* mu,
+                          float* logvar, void* zrow, float* kl, float* kld, int dtype, int N, int L, int E, int M, int Cp,
+                          void* stream);
+/* dml [N, Cq] (compute dtype) = [dmu (L) | dlogvar (L) | 0] from the decoder Linear's input gradient dzrow (rows of pitch
+ * ldz, compute dtype; dz = columns [0, L)):  dmu = dz + mu * inv_numel,
+ * dlogvar = dz * eps * 0.5 * exp(logvar / 2) + 0.5 * (exp(logvar) - 1) * inv_numel.
+ * de [N, E] fp32 (NULL with E = 0) = columns [L, L + E) of dzrow: the decoder embedding's dE. */
+int mcgen_cvae_latent_bwd(const void* dzrow, int ldz, const float* mu, const float* logvar, const float* eps, float inv_numel,
+                          void* dml, float* de, int dtype, int N, int L, int E, int Cq, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -256,6 +256,10 @@ SYMBOLS = {
     'mcgen_cpx_code_embed_bwd': (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp]),
     'mcgen_cpx_sample_row': (_i, [C.POINTER(PxSample), _i, _i, _vp]),
     'mcgen_cpx_sample_col': (_i, [C.POINTER(PxSample), _i, _i, _i, _vp]),
+    'mcgen_cvae_enc_input': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'mcgen_cvae_enc_dembed': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'mcgen_cvae_latent_fwd': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'mcgen_cvae_latent_bwd': (_i, [_vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
 
 _lib = None

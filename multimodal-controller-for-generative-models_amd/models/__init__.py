@@ -7,3 +7,4 @@ from .vqvae import vqvae, VQVAE  # noqa: F401
 from .classifier import classifier, Classifier  # noqa: F401
 from .cgan import cgan, CGAN  # noqa: F401
 from .cpixelcnn import cpixelcnn, ConditionalGatedPixelCNN  # noqa: F401
+from .cvae import cvae, CVAE  # noqa: F401

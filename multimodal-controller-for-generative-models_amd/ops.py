@@ -1904,3 +1904,76 @@ def cpx_sample_row(P: '_lib.PxSample', i: int, dtype: torch.dtype):
 def cpx_sample_col(P: '_lib.PxSample', i: int, j: int, dtype: torch.dtype):
     """px_sample_col for ConditionalGatedPixelCNN (mcgen_cpx_sample_col)."""
     check(_lib.load().mcgen_cpx_sample_col(C.byref(P), i, j, _dt(dtype), _stream()), 'cpx_sample_col')
+
+
+# ---- CVAE label embedding (cvae_engine.py) -------------------------------------------------------------------------------
+def _table(w: Tensor, what: str) -> Tensor:
+    if w.dtype != torch.float32 or w.dim() != 2 or not w.is_contiguous():
+        raise _lib.McgenError(f'{what}: the embedding table must be contiguous fp32 [E, M], got {w.dtype} {tuple(w.shape)}')
+    return w
+
+
+def cvae_enc_input(img: Tensor, w: Tensor, label: Tensor, dtype: torch.dtype) -> Tensor:
+    """[N, H, W, pad8(C + E)] in `dtype` from the NCHW fp32 image in (-1, 1): (img + 1) / 2 (+) W[:, label] broadcast over the
+    pixels (cvae.py:58-62, 133), w = [E, M].  One launch (mcgen_cvae_enc_input)."""
+    n, c, h, wd = img.shape
+    e, m = _table(w, 'cvae_enc_input').shape
+    if label.numel() != n:
+        raise _lib.McgenError(f'cvae_enc_input: {label.numel()} labels for {n} images')
+    cp = pad8(c + e)
+    out = torch.empty((n, h, wd, cp), dtype=dtype, device=img.device)
+    check(_lib.load().mcgen_cvae_enc_input(_f32(img), _f32(w), _p(_labels64(label)), _p(out), _dt(dtype), n, h * wd, c, e, m, cp,
+                                           _stream()), 'cvae_enc_input')
+    return out
+
+
+def cvae_enc_dembed(d_h: Tensor, w_conv: Tensor, cimg: int, e: int) -> Tensor:
+    """[N, E] fp32: the encoder embedding's input gradient through Conv2d(cimg + E, C, 4, 2, 1) from the convolution's output
+    gradient d_h [N, Ho, Wo, Cp] alone (per-image window sums; no input gradient of the convolution); w_conv the fp32 weight
+    [C, cimg + E, 4, 4].  Two launches (mcgen_cgan_dis_window_sums + mcgen_cvae_enc_dembed)."""
+    n, h, wd, cp = d_h.shape
+    c, cin = w_conv.shape[0], w_conv.shape[1]
+    if tuple(w_conv.shape[2:]) != (4, 4) or not w_conv.is_contiguous() or c > cp:
+        raise _lib.McgenError(f'cvae_enc_dembed: expected a contiguous [C <= {cp}, Cin, 4, 4] weight, got {tuple(w_conv.shape)}')
+    part = torch.empty((n, h, 3, c), dtype=torch.float32, device=d_h.device)
+    check(_lib.load().mcgen_cgan_dis_window_sums(_p(d_h), _f32(part), _dt(d_h.dtype), n, h, wd, c, cp, _stream()),
+          'cgan_dis_window_sums')
+    out = torch.empty((n, e), dtype=torch.float32, device=d_h.device)
+    check(_lib.load().mcgen_cvae_enc_dembed(_f32(part), _f32(w_conv), _f32(out), n, h, c, cin, cimg, e, _stream()), 'cvae_enc_dembed')
+    return out
+
+
+def cvae_latent_fwd(ml: Tensor, eps: Optional[Tensor], w: Tensor, label: Tensor, latent: int):
+    """The latent step in one host call: ml [N, >= 2L] (compute dtype; mu | logvar head output), eps [N, L] fp32 or None
+    (evaluation: z = mu), w = [E, M] -> (mu, logvar [N, L] fp32, zrow [N, 1, 1, pad8(L + E)] in ml's dtype =
+    z (+) W[:, label], kld device scalar [1] = 0.5 sum(mu^2 + exp(logvar) - 1 - logvar), summed per sample then over n
+    ascending)."""
+    n, ldm = ml.shape
+    e, m = _table(w, 'cvae_latent_fwd').shape
+    if label.numel() != n or (eps is not None and tuple(eps.shape) != (n, latent)):
+        raise _lib.McgenError('cvae_latent_fwd: one label and one eps row [L] per sample')
+    cp = pad8(latent + e)
+    dev = ml.device
+    mu = torch.empty((n, latent), dtype=torch.float32, device=dev)
+    logvar = torch.empty_like(mu)
+    zrow = torch.empty((n, 1, 1, cp), dtype=ml.dtype, device=dev)
+    kl = torch.empty(n, dtype=torch.float32, device=dev)
+    kld = torch.empty(1, dtype=torch.float32, device=dev)
+    check(_lib.load().mcgen_cvae_latent_fwd(_p(ml), ldm, _f32(eps), _f32(w), _p(_labels64(label)), _f32(mu), _f32(logvar), _p(zrow),
+                                            _f32(kl), _f32(kld), _dt(ml.dtype), n, latent, e, m, cp, _stream()), 'cvae_latent_fwd')
+    return mu, logvar, zrow, kld
+
+
+def cvae_latent_bwd(dzrow: Tensor, mu: Tensor, logvar: Tensor, eps: Tensor, inv_numel: float, e: int):
+    """dzrow [N, >= L + E] (compute dtype; the decoder Linear's input gradient) -> (dml [N, 1, 1, pad8(2L)] in its dtype =
+    [dmu | dlogvar | 0] for the head's weight gradient, de [N, E] fp32 = columns [L, L + E): the decoder embedding's dE)."""
+    n, ldz = dzrow.shape
+    latent = mu.shape[1]
+    if tuple(logvar.shape) != (n, latent) or tuple(eps.shape) != (n, latent) or mu.shape[0] != n:
+        raise _lib.McgenError('cvae_latent_bwd: mu, logvar and eps must be [N, L]')
+    cq = pad8(2 * latent)
+    dml = torch.empty((n, 1, 1, cq), dtype=dzrow.dtype, device=dzrow.device)
+    de = torch.empty((n, e), dtype=torch.float32, device=dzrow.device)
+    check(_lib.load().mcgen_cvae_latent_bwd(_p(dzrow), ldz, _f32(mu), _f32(logvar), _f32(eps), float(inv_numel), _p(dml), _f32(de),
+                                            _dt(dzrow.dtype), n, latent, e, cq, _stream()), 'cvae_latent_bwd')
+    return dml, de

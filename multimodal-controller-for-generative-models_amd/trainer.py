@@ -874,7 +874,12 @@ class PixelCNNTrainer(_FlatTrainer):
 
 class VAETrainer(_FlatTrainer):
     """train_vae.py:98-126 on the HIP path (config 1 of the reference runs this model on the CPU; this is the same
-    loop body on the GPU kernels)."""
+    loop body on the GPU kernels).  MCVAE or the CVAE baseline (one GPU)."""
+
+    def __init__(self, model, *a, world_size=1, **k):
+        if world_size > 1 and hasattr(model.encoder, 'embedding'):
+            raise ValueError('CVAE training runs on one GPU: multi-GPU CVAE is not supported; run with world_size 1')
+        super().__init__(model, *a, world_size=world_size, **k)
 
     def _compute(self, img, label, eps):
         eng = self.model._engine()

@@ -56,7 +56,8 @@ class ConvAEEngine(EngineBase):
             tape.append(dict(kind='down', col=col, wm=wm, h=h, bn=b, code=code, cin_p=cp))
         return a
 
-    def _down_bwd(self, conv, bn, r, g: Tensor, need_dx: bool):
+    def _down_bwd(self, conv, bn, r, g: Tensor, need_dx: bool, want_dh: bool = False):
+        """-> the stage's input gradient (None without need_dx); with want_dh, -> (that, the convolution's output gradient)."""
         dt = self.dtype
         sc, sh, mean, rstd = r['bn']
         d_h = ops.code_bn_bwd(g, r['code'], r['h'], sc, mean, rstd, self._grad(bn.weight), self._grad(bn.bias), shift=sh, pre_relu=True)
@@ -65,10 +66,11 @@ class ConvAEEngine(EngineBase):
         ops.wgrad(Seg(r['col'], ksize=1), d_h, co, 16 * cp, gw, bias_grad=self._grad(conv.bias))
         self._grad(conv.weight).copy_(gw.view(co, 4, 4, cp)[..., :conv.in_channels].permute(0, 3, 1, 2))
         if not need_dx:
-            return None
+            return (None, d_h) if want_dh else None
         wt = F.pad(_t1x1(r['wm']), (0, 0, 0, 0, 0, d_h.shape[-1] - co)).contiguous()
         dcol, _ = ops.conv_fused([Seg(d_h, ksize=1)], ops.prep_weight(wt, dt), 16 * cp)
-        return ops.col2im(dcol, cp, 4, 4, 1, 1, stride=2)
+        dx = ops.col2im(dcol, cp, 4, 4, 1, 1, stride=2)
+        return (dx, d_h) if want_dh else dx
 
     def _res_fwd(self, blk, x: Tensor, label, train: bool, tape):
         """relu(BN(conv(relu(BN(conv(x))) * code3)) * code6 + x)."""

@@ -1,0 +1,478 @@
+"""GPU parity of the CVAE kernels (csrc/cvae_ops.hip) against fp64 torch restatements, and of the model (models/cvae.py on
+cvae_engine.py) against the reference-generated fixtures tests/golden/cvae_*.npz: forward, gradients, train steps, graphed
+steps, bf16, full size and the driver pipeline."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import golden_util as gu
+from test_cvae_cpu import layout
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SMALL = ([8, 16, 32], 16)
+FIXTURES = [('cvae_small.npz', 10, 3), ('cvae_omniglot_small.npz', 1623, 1)]
+
+
+def _rel(a, b):
+    a = torch.as_tensor(a).detach().double().cpu()
+    b = b.detach().double().cpu() if torch.is_tensor(b) else torch.as_tensor(np.asarray(b)).double()
+    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
+
+
+def _labels(n, modes, g):
+    """Repeated labels, the last mode present, most modes absent."""
+    lab = torch.randint(0, min(modes, 7), (n,), generator=g)
+    lab[1] = lab[0]; lab[2] = modes - 1; lab[3] = lab[0]
+    return lab
+
+
+# ---- kernels ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize('modes,c', [(10, 3), (1623, 1)])
+def test_encoder_input_kernel(dtype, modes, c):
+    from mcgen_amd import ops
+    g = torch.Generator().manual_seed(modes + c)
+    n, e, hw = 9, 32, 32
+    img = torch.rand(n, c, hw, hw, generator=g) * 2 - 1
+    w = torch.randn(e, modes, generator=g)
+    lab = _labels(n, modes, g)
+    out = ops.cvae_enc_input(img.cuda(), w.cuda(), lab.cuda(), dtype)
+    cp = (c + e + 7) // 8 * 8
+    assert out.shape == (n, hw, hw, cp) and out.dtype == dtype
+    ref = torch.zeros(n, hw, hw, cp, dtype=torch.float64)
+    ref[..., :c] = ((img.double() + 1) / 2).permute(0, 2, 3, 1)
+    ref[..., c:c + e] = w.double().t()[lab][:, None, None, :]
+    f32 = dtype == torch.float32
+    print('enc_input rel err', _rel(out.float(), ref))
+    assert _rel(out.float(), ref) < (5e-5 if f32 else 1e-2)
+    assert float(out[..., c + e:].float().abs().max()) == 0.0
+    if f32:                                                      # the embedding channels are copies, the image (x + 1) * 0.5
+        assert torch.equal(out[..., c:c + e].cpu(), w.t()[lab][:, None, None, :].expand(n, hw, hw, e))
+    assert torch.equal(out, ops.cvae_enc_input(img.cuda(), w.cuda(), lab.cuda(), dtype))
+    # a label outside the table reads a zero row
+    bad = lab.clone(); bad[0] = -1; bad[4] = modes; bad[5] = 10 ** 12
+    ob = ops.cvae_enc_input(img.cuda(), w.cuda(), bad.cuda(), dtype)
+    keep = torch.ones(n, dtype=torch.bool); keep[[0, 4, 5]] = False
+    assert torch.equal(ob[keep], out[keep]) and float(ob[~keep][..., c:].float().abs().max()) == 0.0
+    assert torch.equal(ob[..., :c], out[..., :c])
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize('modes,c,co,ho', [(10, 3, 64, 16), (1623, 1, 8, 16), (10, 3, 16, 2)])
+def test_encoder_embedding_gradient_kernels(dtype, modes, c, co, ho):
+    """dE of the encoder embedding from the first convolution's output gradient alone, against autograd through F.conv2d on
+    the concatenated input; then the table gradient."""
+    from mcgen_amd import ops
+    g = torch.Generator().manual_seed(modes + co + ho)
+    n, e = 9, 32
+    wconv = torch.randn(co, c + e, 4, 4, generator=g) * 0.1
+    d_h = torch.randn(n, ho, ho, co, generator=g).to(dtype).float()
+    emb = torch.randn(n, e, generator=g).double().requires_grad_(True)
+    img = torch.rand(n, c, 2 * ho, 2 * ho, generator=g).double()
+    x = torch.cat([img, emb[:, :, None, None].expand(n, e, 2 * ho, 2 * ho)], 1)
+    y = F.conv2d(x, wconv.double(), None, stride=2, padding=1)
+    (y * d_h.double().permute(0, 3, 1, 2)).sum().backward()
+    cop = (co + 7) // 8 * 8
+    d_hp = F.pad(d_h, (0, cop - co)).to(dtype).cuda().contiguous()
+    de = ops.cvae_enc_dembed(d_hp, wconv.cuda(), c, e)
+    f32 = dtype == torch.float32
+    print('enc_dembed rel err', _rel(de, emb.grad))
+    assert _rel(de, emb.grad) < (5e-5 if f32 else 1e-2)
+    assert torch.equal(de, ops.cvae_enc_dembed(d_hp, wconv.cuda(), c, e))
+    # table gradient: dW[:, m] = sum of dE[n] over label_n == m; absent modes exactly 0; labels outside the table skipped
+    lab = _labels(n, modes, g)
+    ref = torch.zeros(modes, e, dtype=torch.float64).index_add_(0, lab, emb.grad).t()
+    dw = torch.full((e, modes), float('nan'), device='cuda')
+    ops.cgan_embed_bwd(de, lab.cuda(), dw)
+    assert _rel(dw, ref) < (5e-5 if f32 else 1e-2)
+    absent = torch.ones(modes, dtype=torch.bool); absent[lab] = False
+    assert float(dw[:, absent.cuda()].abs().max()) == 0.0
+    dw2 = torch.empty_like(dw)
+    ops.cgan_embed_bwd(de, lab.cuda(), dw2)
+    assert torch.equal(dw, dw2)
+    bad = lab.clone(); bad[0] = -2; bad[4] = modes
+    keep = torch.ones(n, dtype=torch.bool); keep[[0, 4]] = False
+    refb = torch.zeros(modes, e, dtype=torch.float64).index_add_(0, lab[keep], emb.grad[keep]).t()
+    ops.cgan_embed_bwd(de, bad.cuda(), dw2)
+    assert _rel(dw2, refb) < (5e-5 if f32 else 1e-2)
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize('modes,L', [(10, 128), (1623, 16), (10, 264)])
+def test_latent_kernels(dtype, modes, L):
+    """Reparameterisation + KL + the decoder Linear's input row, and their backward, against fp64 autograd."""
+    from mcgen_amd import ops
+    g = torch.Generator().manual_seed(modes + L)
+    n, e, numel = 9, 32, 9 * 3 * 32 * 32
+    f32 = dtype == torch.float32
+    tol = 5e-5 if f32 else 1e-2
+    pitch = 2 * L + 8                                            # a head output wider than 2 L: the kernel reads by pitch
+    ml = torch.zeros(n, pitch)
+    ml[:, :2 * L] = torch.randn(n, 2 * L, generator=g) * 0.7
+    ml = ml.to(dtype).float()
+    eps = torch.randn(n, L, generator=g)
+    w = torch.randn(e, modes, generator=g)
+    lab = _labels(n, modes, g)
+    mu_r = ml[:, :L].double().clone().requires_grad_(True)
+    lv_r = ml[:, L:2 * L].double().clone().requires_grad_(True)
+    z_r = mu_r + eps.double() * torch.exp(0.5 * lv_r)
+    kld_r = 0.5 * torch.sum(mu_r.pow(2) + lv_r.exp() - 1 - lv_r)
+    kld_ref = float(kld_r.detach())
+    mu, logvar, zrow, kld = ops.cvae_latent_fwd(ml.to(dtype).cuda(), eps.cuda(), w.cuda(), lab.cuda(), L)
+    assert zrow.shape == (n, 1, 1, L + e) and zrow.dtype == dtype and mu.dtype == torch.float32
+    assert torch.equal(mu.cpu(), ml[:, :L]) and torch.equal(logvar.cpu(), ml[:, L:2 * L])
+    zr = zrow.reshape(n, -1).float()
+    print('latent fwd rel err z', _rel(zr[:, :L], z_r), 'kld', abs(float(kld) - kld_ref) / kld_ref)
+    assert _rel(zr[:, :L], z_r) < tol
+    assert _rel(zr[:, L:], w.t()[lab].to(dtype).float()) == 0.0
+    assert abs(float(kld) - kld_ref) < 5e-5 * kld_ref              # the KL sum is fp32 in both compute dtypes
+    again = ops.cvae_latent_fwd(ml.to(dtype).cuda(), eps.cuda(), w.cuda(), lab.cuda(), L)
+    assert all(torch.equal(a, b) for a, b in zip((mu, logvar, zrow, kld), again))
+    # evaluation: z = mu
+    _, _, zrow_e, kld_e = ops.cvae_latent_fwd(ml.to(dtype).cuda(), None, w.cuda(), lab.cuda(), L)
+    assert torch.equal(zrow_e.reshape(n, -1)[:, :L].float().cpu(), ml[:, :L].to(dtype).float()) and torch.equal(kld_e, kld)
+    # a label outside the table reads a zero row
+    bad = lab.clone(); bad[0] = -1; bad[4] = modes
+    zb = ops.cvae_latent_fwd(ml.to(dtype).cuda(), eps.cuda(), w.cuda(), bad.cuda(), L)[2].reshape(n, -1)
+    keep = torch.ones(n, dtype=torch.bool); keep[[0, 4]] = False
+    assert torch.equal(zb[keep], zrow.reshape(n, -1)[keep]) and float(zb[~keep][:, L:].float().abs().max()) == 0.0
+    assert torch.equal(zb[:, :L], zrow.reshape(n, -1)[:, :L])
+    # backward: the gradient of sum(z * dz) + kld / numel with respect to mu and logvar
+    dzrow = torch.zeros(n, L + e + 8)
+    dzrow[:, :L + e] = torch.randn(n, L + e, generator=g) * 1e-3
+    dzrow = dzrow.to(dtype).float()
+    ((z_r * dzrow[:, :L].double()).sum() + kld_r / numel).backward()
+    dml, de = ops.cvae_latent_bwd(dzrow.to(dtype).cuda(), mu, logvar, eps.cuda(), 1.0 / numel, e)
+    d2 = dml.reshape(n, -1).float()
+    assert dml.shape == (n, 1, 1, (2 * L + 7) // 8 * 8) and dml.dtype == dtype
+    print('latent bwd rel err dmu', _rel(d2[:, :L], mu_r.grad), 'dlogvar', _rel(d2[:, L:2 * L], lv_r.grad))
+    assert _rel(d2[:, :L], mu_r.grad) < tol and _rel(d2[:, L:2 * L], lv_r.grad) < tol
+    assert d2.shape[1] == 2 * L or float(d2[:, 2 * L:].abs().max()) == 0.0
+    assert torch.equal(de.cpu(), dzrow[:, L:L + e])
+    dml2, de2 = ops.cvae_latent_bwd(dzrow.to(dtype).cuda(), mu, logvar, eps.cuda(), 1.0 / numel, e)
+    assert torch.equal(dml, dml2) and torch.equal(de, de2)
+
+
+# ---- model -----------------------------------------------------------------------------------------------------------------
+def _init_state(d):
+    return gu.procedural_state_generic(layout(d), seed=int(d['sd_seed']))
+
+
+def _final_state(d):
+    out = {}
+    for k, v in _init_state(d).items():
+        out[k] = torch.from_numpy(np.array(d['sd_final_int/' + k])) if 'sd_final_int/' + k in d else \
+            v + torch.from_numpy(d['sd_delta/' + k])
+    return out
+
+
+def _bias_before_bn(shapes):
+    """Biases of a convolution / Linear whose output goes straight into a BatchNorm: their gradient is exactly zero."""
+    out = set()
+    for k in shapes:
+        if not k.endswith('.bias'):
+            continue
+        pre, idx = k[:-len('.bias')].rsplit('.', 1)
+        if not idx.isdigit():
+            continue
+        if pre + '.' + idx + '.running_mean' not in shapes and f'{pre}.{int(idx) + 1}.running_mean' in shapes:
+            out.add(k)
+    return out
+
+
+def _model(sd, classes, channels=3, hidden=SMALL[0], latent=SMALL[1], dtype=torch.float32):
+    from mcgen_amd import models
+    from mcgen_amd.config import cfg
+    cfg.update(model_name='cvae', data_name='CIFAR10', device='cuda', classes_size=classes, data_shape=[channels, 32, 32],
+               compute_dtype='float32')
+    cfg['vae'] = {'hidden_size': list(hidden), 'latent_size': latent, 'num_res_block': 2, 'embedding_size': 32}
+    m = models.cvae()
+    m.load_state_dict(sd)
+    return m.cuda().set_compute_dtype(dtype)
+
+
+def _noise(d, s):
+    return torch.from_numpy(d[f'noise/{s}/0']).cuda()
+
+
+@pytest.mark.parametrize('fixture,classes,channels', FIXTURES)
+def test_cvae_forward_vs_reference(fixture, classes, channels):
+    d = gu.load_npz(fixture)
+    img, lab = torch.from_numpy(d['img']).cuda(), torch.from_numpy(d['label']).cuda()
+    m = _model(_init_state(d), classes, channels)
+    m.train(True)
+    with torch.no_grad():
+        out = m({'img': img, 'label': lab, 'eps': _noise(d, 0)})
+    print('loss', float(out['loss']), float(d['losses'][0]), 'mu', _rel(out['mu'], d['mu0']), 'logvar', _rel(out['logvar'], d['logvar0']),
+          'img', _rel(out['img'], d['img0']))
+    assert abs(float(out['loss']) - float(d['losses'][0])) < 1e-5
+    assert _rel(out['mu'], d['mu0']) < 2e-4 and _rel(out['logvar'], d['logvar0']) < 2e-4
+    assert _rel(out['img'], d['img0']) < 2e-4
+    assert int(m.decoder.linear[1].num_batches_tracked) == 1 and int(m.encoder.blocks[1].num_batches_tracked) == 1
+
+
+def test_cvae_generate_vs_reference():
+    """Eval-mode generate on the reference's trained state (cvae_small stores it whole)."""
+    d = gu.load_npz('cvae_small.npz')
+    m = _model(_final_state(d), 10)
+    m.train(False)
+    gen = m.generate(torch.from_numpy(d['label']).cuda(), torch.from_numpy(d['gen_z']).cuda())
+    print('generate', _rel(gen, d['generated_eval']))
+    assert gen.shape == (8, 3, 32, 32) and _rel(gen, d['generated_eval']) < 5e-4
+    # eval-mode forward takes z = mu: the reconstruction is generate(label, mu)
+    img, lab = torch.from_numpy(d['img']).cuda(), torch.from_numpy(d['label']).cuda()
+    with torch.no_grad():
+        out = m({'img': img, 'label': lab})
+    assert _rel(out['img'], m.generate(lab, out['mu'])) < 1e-6
+
+
+def _ref_forward(P, img, lab, eps, nstage=3, nres=2):
+    """fp64 torch restatement of CVAE's training-mode forward (cvae.py) over a dict of parameters -> loss."""
+    def bn(x, pre):
+        return F.batch_norm(x, None, None, P[pre + '.weight'], P[pre + '.bias'], True, 0.1, 1e-5)
+
+    def res(x, pre):
+        h = torch.relu(bn(F.conv2d(x, P[pre + '.conv.0.weight'], P[pre + '.conv.0.bias'], padding=1), pre + '.conv.1'))
+        h = bn(F.conv2d(h, P[pre + '.conv.3.weight'], P[pre + '.conv.3.bias'], padding=1), pre + '.conv.4')
+        return torch.relu(h + x)
+    x01 = (img + 1) / 2
+    n = img.shape[0]
+    e = P['encoder.embedding.weight'].t()[lab]
+    x = torch.cat([x01, e[:, :, None, None].expand(n, e.shape[1], *img.shape[2:])], 1)
+    for i in range(nstage):
+        q = f'encoder.blocks.{3 * i}'
+        x = torch.relu(bn(F.conv2d(x, P[q + '.weight'], P[q + '.bias'], stride=2, padding=1), f'encoder.blocks.{3 * i + 1}'))
+    for r in range(nres):
+        x = res(x, f'encoder.blocks.{3 * nstage + r}')
+    shape = x.shape[1:]
+    x = x.reshape(n, -1)
+    mu = F.linear(x, P['encoder.mu.weight'], P['encoder.mu.bias'])
+    logvar = F.linear(x, P['encoder.logvar.weight'], P['encoder.logvar.bias'])
+    z = mu + eps * torch.exp(0.5 * logvar)
+    x = torch.cat([z, P['decoder.embedding.weight'].t()[lab]], 1)
+    x = torch.relu(bn(F.linear(x, P['decoder.linear.0.weight'], P['decoder.linear.0.bias']), 'decoder.linear.1'))
+    x = x.reshape(n, *shape)
+    for r in range(nres):
+        x = res(x, f'decoder.blocks.{r}')
+    k = nres
+    for _ in range(nstage - 1):
+        q = f'decoder.blocks.{k}'
+        x = torch.relu(bn(F.conv_transpose2d(x, P[q + '.weight'], P[q + '.bias'], stride=2, padding=1), f'decoder.blocks.{k + 1}'))
+        k += 3
+    q = f'decoder.blocks.{k}'
+    logits = F.conv_transpose2d(x, P[q + '.weight'], P[q + '.bias'], stride=2, padding=1)
+    bce = F.binary_cross_entropy_with_logits(logits, x01, reduction='sum')
+    kld = 0.5 * torch.sum(mu.pow(2) + logvar.exp() - 1 - logvar)
+    return (bce + kld) / img.numel()
+
+
+@pytest.mark.parametrize('fixture,classes,channels', FIXTURES)
+def test_gradients_vs_fp64_restatement(fixture, classes, channels):
+    """Step-0 gradients of every parameter, both embedding tables included, through the autograd bridge."""
+    d = gu.load_npz(fixture)
+    sd = _init_state(d)
+    img, lab, eps = torch.from_numpy(d['img']), torch.from_numpy(d['label']), torch.from_numpy(d['noise/0/0'])
+    P = {k: v.double().clone().requires_grad_(True) for k, v in sd.items() if v.is_floating_point() and 'running' not in k}
+    ref = _ref_forward(P, img.double(), lab, eps.double())
+    ref.backward()
+    ref = ref.detach()
+    assert abs(float(ref) - float(d['losses'][0])) < 1e-5                      # the restatement is the reference's forward
+    m = _model(sd, classes, channels)
+    m.train(True)
+    out = m({'img': img.cuda(), 'label': lab.cuda(), 'eps': eps.cuda()})
+    assert abs(float(out['loss'].detach()) - float(ref)) < 1e-5
+    out['loss'].backward()
+    named = dict(m.named_parameters())
+    assert set(named) == set(P)
+    zero = _bias_before_bn(layout(d))
+    assert 'encoder.blocks.0.bias' in zero and 'decoder.linear.0.bias' in zero and 'encoder.mu.bias' not in zero
+    worst = (0.0, None)
+    for k, p in named.items():
+        rg = P[k].grad
+        assert p.grad is not None and rg is not None, k
+        err = float((p.grad.double().cpu() - rg).abs().max())
+        if k in zero:                     # exactly zero in exact arithmetic: fp32 rounding residue only (absolute floor)
+            assert float(rg.abs().max()) < 1e-12 and err < 1e-7, (k, err)
+            continue
+        worst = max(worst, (err / float(rg.abs().max()), k))
+        assert err < 5e-4 * float(rg.abs().max()) + 1e-7, (k, err, float(rg.abs().max()))
+    print('worst gradient error relative to max |g|:', worst)
+    present = torch.zeros(classes, dtype=torch.bool); present[lab] = True
+    for k in ('encoder.embedding.weight', 'decoder.embedding.weight'):
+        gk = named[k].grad.cpu()
+        assert float(gk[:, ~present].abs().max()) == 0.0 and float(gk[:, present].abs().sum(0).min()) > 0, k
+
+
+@pytest.mark.parametrize('fixture,classes,channels', FIXTURES)
+def test_cvae_train_steps_vs_reference(fixture, classes, channels):
+    """train_vae.py loop body x3 (clip_grad_norm_ 1, Adam 3e-4) from the fixture's weights with its noise."""
+    from mcgen_amd.trainer import VAETrainer
+    d = gu.load_npz(fixture)
+    img, lab = torch.from_numpy(d['img']).cuda(), torch.from_numpy(d['label']).cuda()
+    m = _model(_init_state(d), classes, channels)
+    tr = VAETrainer(m)
+    losses = [float(tr.train_iteration(img, lab, _noise(d, s))) for s in range(3)]
+    print('train losses', losses, 'reference', d['losses'])
+    assert abs(losses[0] - d['losses'][0]) < 1e-5, (losses, d['losses'])
+    assert max(abs(a - b) for a, b in zip(losses, d['losses'])) < 2e-3, (losses, d['losses'])
+    sd = m.state_dict()
+    zero = _bias_before_bn(layout(d))
+    if 'sd_delta/encoder.embedding.weight' in d:
+        for k, v in _final_state(d).items():
+            if not v.is_floating_point():
+                assert torch.equal(sd[k].cpu(), v), k
+            elif not k.endswith(('running_mean', 'running_var')):
+                assert float((sd[k].cpu() - v).abs().max()) < 2e-3, k
+    else:
+        for k, v in sd.items():
+            if not v.is_floating_point():
+                assert torch.equal(v.cpu(), torch.from_numpy(np.array(d['sd_final_int/' + k]))), k
+                continue
+            got, ref = gu.checksum(v.float().cpu()), d['digest/' + k]
+            if k in zero:
+                # a bias in front of a BatchNorm has an exactly-zero gradient: Adam turns rounding residue into steps of up
+                # to lr, different here and there -- only that bound holds (3 steps of 3e-4 per element)
+                assert np.abs(got - ref).max() < 2 * 3 * 3e-4 * v.numel(), (k, got, ref)
+                continue
+            assert np.abs(got - ref).max() < 2e-3 * max(float(ref[1]), 1.0), (k, got, ref)
+    # the embedding columns of absent modes never move; the present ones do
+    present = torch.zeros(classes, dtype=torch.bool)
+    present[torch.from_numpy(d['label'])] = True
+    for k in ('encoder.embedding.weight', 'decoder.embedding.weight'):
+        e0, e1 = _init_state(d)[k], sd[k].cpu()
+        assert torch.equal(e0[:, ~present], e1[:, ~present]), k
+        assert float((e0[:, present] - e1[:, present]).abs().max(0).values.min()) > 0, k
+    # eval-mode generate of the state trained here against the reference's generate of the state it trained.  Both trainings
+    # feed rounding residue of the exactly-zero bias gradients to Adam, so the states differ: the reference itself, trained
+    # in fp32 and in fp64 from this fixture's inputs on the CPU, generates images 1.5e-4 (cvae_small) and 7.3e-4
+    # (cvae_omniglot_small) apart, relative to the largest pixel; four times the larger gap is allowed.
+    m.train(False)
+    gen = m.generate(lab, torch.from_numpy(d['gen_z']).cuda())
+    print('generate after training here', _rel(gen, d['generated_eval']))
+    assert _rel(gen, d['generated_eval']) < 3e-3
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
+def test_cvae_full_size_digest(dtype):
+    """Config widths at batch 128 (7,793,411 parameters) against cvae_full_digest.npz: first loss, mu / img digests, every
+    parameter gradient digest of that step, two train_vae.py steps."""
+    from mcgen_amd.trainer import VAETrainer
+    d = gu.load_npz('cvae_full_digest.npz')
+    f32 = dtype == torch.float32
+
+    def build():
+        return _model(_init_state(d), 10, 3, [64, 128, 256], 128, dtype)
+    m = build()
+    assert sum(p.numel() for p in m.parameters()) == 7793411
+    img, _ = gu.synthetic_batch(128, 10, seed=int(d['img_seed']))
+    img, lab = img.cuda(), torch.from_numpy(d['label']).cuda()
+    m.train(True)
+    out = m({'img': img, 'label': lab, 'eps': _noise(d, 0)})
+    print('loss', float(out['loss'].detach()), float(d['losses'][0]))
+    assert abs(float(out['loss'].detach()) - float(d['losses'][0])) < (1e-5 if f32 else 1e-2)
+    for key, t in (('mu0_digest', out['mu']), ('img0_digest', out['img'])):
+        got, ref = gu.checksum(t.float().detach().cpu()), d[key]
+        print(key, got, ref)
+        assert np.abs(got - ref).max() < (2e-4 if f32 else 3e-2) * ref[1], (key, got, ref)
+    # bf16 pixels: MCVAE's 3e-2 does not carry over to these weights.  The activations pick up about 0.4 % of their range per
+    # layer and reach the logits at 1.6 % of theirs, as in MCVAE, but the procedural weights give logits up to +-14.5, and
+    # the sigmoid turns 1.6 % of that into up to a tenth of the image range.  The reference itself under bf16 autocast on
+    # the CPU (convolutions and Linears in bf16, BatchNorm in fp32 -- this engine's split) is 9.7e-2 away from its fp32
+    # images on this fixture's inputs; twice that is allowed.  (The digests above, which average, stay within 3e-2.)
+    print('img sample', _rel(out['img'][:4, :, ::4, ::4], d['img0_sample']))
+    assert _rel(out['img'][:4, :, ::4, ::4], d['img0_sample']) < (2e-4 if f32 else 2 * 9.7e-2)
+    out['loss'].backward()
+    named = dict(m.named_parameters())
+    assert set(map(str, d['grad_keys'])) == set(named)
+    zero = _bias_before_bn(layout(d))
+    worst = (0.0, None)
+    for k in map(str, d['grad_keys']):
+        gp = named[k].grad
+        assert gp is not None, k
+        got, ref = gu.checksum(gp.float().cpu()), d['grad0_digest/' + k]
+        numel = gp.numel()
+        if k in zero:                                            # exactly zero in exact arithmetic (a bias before a BatchNorm)
+            assert float(ref[1]) / numel < 1e-7 and float(got[1]) / numel < (1e-6 if f32 else 1e-4), (k, got, ref)
+            continue
+        err = float(np.abs(got - ref).max()) / float(ref[1])
+        worst = max(worst, (err, k))
+        assert err < (2e-3 if f32 else 1e-1), (k, got, ref)
+    print('worst gradient digest error (relative to sum |g|):', worst)
+    for k in ('encoder.embedding.weight', 'decoder.embedding.weight'):
+        assert float(named[k].grad[:, 9].abs().max()) == 0.0, k               # mode 9 is absent from the batch
+    tr = VAETrainer(build())
+    losses = [float(tr.train_iteration(img, lab, _noise(d, s))) for s in range(2)]
+    print('train losses', losses, 'reference', d['losses'])
+    assert abs(losses[0] - d['losses'][0]) < (1e-5 if f32 else 1e-2)
+    # The second forward is ill-conditioned in the reference itself: Adam's first step moves every weight by lr in a coherent
+    # direction, the largest logvar goes from 5.4 to 24.3 and the loss (about exp(max logvar) / (2 numel)) from 1.06 to 45 000.
+    # fp32: the reference run in fp32 and in fp64 on the CPU from this fixture's inputs gives 44999.676 and 44957.785, a gap
+    # of 41.9 (9.3e-4 of the loss), where the O(1) losses' bound of 2e-3 is below one fp32 ulp of the value (3.9e-3); four
+    # times that gap is allowed.  bf16: the reference's own train_vae.py step under bf16 autocast on the CPU (BatchNorm and
+    # the loss in fp32) ends at 171 674.5, its largest logvar at 25.63 instead of 24.29.  The loss is exponential in that
+    # logvar, so the bf16 bound is set on the logarithm: the reference's own gap, log(171674.5 / 44999.7) = 1.34.
+    if f32:
+        assert abs(losses[1] - d['losses'][1]) < 4 * 41.9, (losses, d['losses'])
+    else:
+        assert abs(np.log(losses[1] / float(d['losses'][1]))) < 1.34, (losses, d['losses'])
+
+
+def test_graphed_step_equals_eager_and_bf16_tracks_fp32():
+    from mcgen_amd.trainer import VAETrainer
+    d = gu.load_npz('cvae_omniglot_small.npz')
+    img, lab = torch.from_numpy(d['img']).cuda(), torch.from_numpy(d['label']).cuda()
+    eager = VAETrainer(_model(_init_state(d), 1623, 1))
+    le = [tr_loss.clone() for tr_loss in (eager.train_iteration(img, lab, _noise(d, s)) for s in range(3))]
+    graphed = VAETrainer(_model(_init_state(d), 1623, 1))
+    graphed.capture(img, lab)
+    lg = [graphed.train_iteration(img, lab, _noise(d, s)).clone() for s in range(3)]
+    assert all(torch.equal(a, b) for a, b in zip(le, lg)), (le, lg)
+    # every reduction of the step runs in a fixed order (no float atomics): the replayed graph leaves the eager step's state
+    # bit for bit
+    se, sg = eager.model.state_dict(), graphed.model.state_dict()
+    for k in se:
+        assert torch.equal(se[k], sg[k]), k
+    # a replay that draws its own noise keeps training
+    assert np.isfinite(float(graphed.train_iteration(img, lab)))
+    bf = VAETrainer(_model(_init_state(d), 1623, 1, dtype=torch.bfloat16))
+    lb = [float(bf.train_iteration(img, lab, _noise(d, s))) for s in range(3)]
+    print('bf16 losses', lb, 'fp32', [float(x) for x in le])
+    assert abs(lb[0] - float(le[0])) < 1e-2, (lb, le)
+    assert max(abs(a - float(b)) for a, b in zip(lb, le)) < 2e-2, (lb, le)      # three bf16 train steps: test_mcvae_gpu's bound
+    m = _model(_init_state(d), 1623, 1, dtype=torch.bfloat16)
+    m.train(True)
+    with torch.no_grad():
+        out = m({'img': img, 'label': lab, 'eps': _noise(d, 0)})
+    assert abs(float(out['loss']) - float(d['losses'][0])) < 1e-2
+    # bf16 pixels (see test_cvae_full_size_digest): the reference under bf16 autocast on the CPU is 4.2e-2 away from its own
+    # fp32 images on this fixture's inputs (4.4e-2 on cvae_small's); twice that is allowed
+    print('bf16 img', _rel(out['img'], d['img0']), 'mu', _rel(out['mu'], d['mu0']))
+    assert _rel(out['img'], d['img0']) < 2 * 4.2e-2
+
+
+def _run(args, cwd):
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1')
+    r = subprocess.run([sys.executable] + args, cwd=cwd, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    return r.stdout
+
+
+def test_driver_pipeline(tmp_path):
+    drv = os.path.join(ROOT, 'compat')
+    common = ['--data_name', 'CIFAR10', '--log_interval', '0.5']
+    out = _run([os.path.join(drv, 'train_vae.py'), '--model_name', 'cvae', '--control_name', 'None', '--num_epochs', '1',
+                '--synthetic_size', '192', '--batch', '64'] + common, tmp_path)
+    tag = '0_CIFAR10_label_cvae'
+    assert f'Experiment: {tag}' in out
+    assert (tmp_path / 'output' / 'model' / f'{tag}_best.pt').exists()
+    out = _run([os.path.join(drv, 'generate.py'), '--model_name', 'cvae', '--control_name', 'None', '--save_npy', 'True',
+                '--generate_per_mode', '2', '--synthetic_size', '192'] + common, tmp_path)
+    assert f'Experiment: {tag}' in out and 'Not exists model tag' not in out
+    a = np.load(tmp_path / 'output' / 'npy' / f'generated_{tag}.npy')
+    assert a.shape == (20, 3, 32, 32) and np.isfinite(a).all()

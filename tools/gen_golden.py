@@ -1126,6 +1126,101 @@ def fx_cpixelcnn_full():
 FIXTURES.update(cpixelcnn_small=fx_cpixelcnn_small, cpixelcnn_omniglot_small=fx_cpixelcnn_omniglot_small,
                 cpixelcnn_full=fx_cpixelcnn_full)
 
+
+# ---- CVAE (models/cvae.py): the conditional VAE baseline, label embeddings at the encoder input and the latent ----------
+def _set_cvae_cfg(hidden, latent, classes, channels=3, data_name='CIFAR10'):
+    cfg['model_name'] = 'cvae'; cfg['data_name'] = data_name; cfg['device'] = 'cpu'; cfg['classes_size'] = classes
+    cfg['data_shape'] = [channels, 32, 32]
+    cfg['vae'] = {'hidden_size': list(hidden), 'latent_size': latent, 'num_res_block': 2, 'embedding_size': 32}
+
+
+def _cvae_small(name, classes, channels, data_name, full_final):
+    """Widths [8, 16, 32], latent 16, embedding 32, B=8 with repeated and absent labels, procedural weights over the
+    reference's layout (stored), 3 train_vae.py steps with the recorded noise: the first forward's outputs, the losses, the
+    state after training (differences from the initial state, or digests only) and an eval-mode generate."""
+    import models
+    _set_cvae_cfg([8, 16, 32], 16, classes, channels, data_name)
+    torch.manual_seed(0)
+    model = models.cvae()
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    seed = 1357
+    sd0 = gu.procedural_state_generic(shapes, seed=seed)
+    model.load_state_dict(sd0)
+    model.train(True)
+    arrays = {'layout': _cgan_layout(shapes), 'sd_seed': np.array(seed)}
+    img, lab = gu.synthetic_batch(8, classes, seed=53, shape=(channels, 32, 32))
+    lab[1] = lab[0]; lab[5] = lab[0]                         # a label held by three samples; most modes are absent
+    lab[2] = classes - 1; lab[3] = 0
+    arrays['img'] = img.numpy(); arrays['label'] = lab.numpy()
+    first = _single_opt_steps(model, {'img': img, 'label': lab}, 600, 3, arrays)
+    arrays['mu0'] = first['mu'].detach().numpy(); arrays['logvar0'] = first['logvar'].detach().numpy()
+    arrays['img0'] = first['img'].detach().numpy()
+    for k, v in model.state_dict().items():
+        if not v.is_floating_point():
+            arrays['sd_final_int/' + k] = v.numpy().copy()
+        elif full_final:
+            arrays['sd_delta/' + k] = (v - sd0[k]).detach().numpy()
+        else:
+            arrays['digest/' + k] = gu.checksum(v)
+    model.train(False)
+    z = torch.randn(8, 16, generator=torch.Generator().manual_seed(7))
+    arrays['gen_z'] = z.numpy()
+    with torch.no_grad():
+        arrays['generated_eval'] = model.generate(lab, z).numpy()
+    save(name, **arrays)
+
+
+def fx_cvae_small():
+    _cvae_small('cvae_small.npz', 10, 3, 'CIFAR10', True)
+
+
+def fx_cvae_omniglot_small():
+    _cvae_small('cvae_omniglot_small.npz', 1623, 1, 'Omniglot', False)
+
+
+def fx_cvae_full():
+    """Config widths (hidden [64, 128, 256], latent 128, embedding 32; 7,793,411 parameters with 10 modes), B=128,
+    procedural weights: the first training forward's loss and mu / img digests, the digest of every parameter's gradient of
+    that step (before clip_grad_norm_), two train_vae.py steps' losses, the recorded noise."""
+    import models
+    _set_cvae_cfg([64, 128, 256], 128, 10)
+    torch.manual_seed(0)
+    model = models.cvae(); model.train(True)
+    assert sum(p.numel() for p in model.parameters()) == 7793411
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    seed = 9753
+    model.load_state_dict(gu.procedural_state_generic(shapes, seed=seed))
+    arrays = {'layout': _cgan_layout(shapes), 'sd_seed': np.array(seed)}
+    B = 128
+    img, _ = gu.synthetic_batch(B, 10, seed=3)
+    lab = torch.randint(0, 9, (B,), generator=torch.Generator().manual_seed(46))          # mode 9 absent
+    arrays['label'] = lab.numpy(); arrays['img_seed'] = np.array(3)
+    opt = torch.optim.Adam(model.parameters(), lr=3e-4)
+    losses = []
+    for step in range(2):
+        with _PatchedNoise(700 + step) as pn:
+            opt.zero_grad()
+            out = model({'img': img.clone(), 'label': lab})
+            out['loss'].backward()
+        arrays[f'noise/{step}/0'] = pn.drawn[0].numpy()
+        if step == 0:
+            arrays['mu0_digest'] = gu.checksum(out['mu']); arrays['img0_digest'] = gu.checksum(out['img'])
+            arrays['img0_sample'] = out['img'].detach().numpy()[:4, :, ::4, ::4].copy()
+            names = []
+            for k, p in model.named_parameters():
+                names.append(k)
+                arrays['grad0_digest/' + k] = gu.checksum(p.grad)
+                arrays['grad0_absmax/' + k] = np.array(float(p.grad.abs().max()))
+            arrays['grad_keys'] = np.array(names)
+        torch.nn.utils.clip_grad_norm_(model.parameters(), 1)
+        opt.step()
+        losses.append(out['loss'].item())
+    arrays['losses'] = np.array(losses, dtype=np.float64)
+    save('cvae_full_digest.npz', **arrays)
+
+
+FIXTURES.update(cvae_small=fx_cvae_small, cvae_omniglot_small=fx_cvae_omniglot_small, cvae_full=fx_cvae_full)
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--only', default=None)
