@@ -605,7 +605,9 @@ int mcgen_cross_entropy(const void* logits, const int64_t* target, float* loss_r
                         int dtype, int64_t pixels, int C, int Cp, void* stream);
 
 /* nearest-code search of VectorQuantization.forward (modules.py:20-25): idx[p] = argmin_c x[p, c] (first minimum);
- * x = |e_c|^2 - 2 <f_p, e_c> comes from one fused 1x1 convolution over the codebook */
+ * x = |e_c|^2 - 2 <f_p, e_c> comes from one fused 1x1 convolution over the codebook.  Non-finite rows follow torch.argmin:
+ * NaN counts as the smallest value (the first NaN's index is returned), a row of all +inf gives 0, and 0.0 ties with
+ * -0.0; the index is always in [0, C). */
 int mcgen_argmin_channels(const void* x, int64_t* idx, int dtype, int64_t pixels, int C, int Cp, void* stream);
 
 /* ---- VQ-VAE training (csrc/vq_ops.hip) ----------------------------------------------------------------------------

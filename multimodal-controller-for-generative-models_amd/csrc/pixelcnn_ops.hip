@@ -359,11 +359,17 @@ void argmin_kernel(const T* __restrict__ x, int64_t* __restrict__ idx, size_t pi
     const size_t p = blockIdx.x * (size_t)(blockDim.x >> 6) + (threadIdx.x >> 6);
     if (p >= pixels) return;
     const T* row = x + p * Cp;
+    // torch.argmin's order: NaN ranks below every number, equal values (and NaNs) are ranked by index.  A lane without a
+    // channel (C < 64) keeps bi = INT_MAX and so loses every tie; lane 0 always holds channel 0, so the result is in [0, C).
     float best = INFINITY; int bi = 0x7fffffff;
-    for (int c = lane; c < C; c += 64) { const float v = Elem<T>::to_f(row[c]); if (v < best) { best = v; bi = c; } }
+    for (int c = lane; c < C; c += 64) {
+        const float v = Elem<T>::to_f(row[c]);
+        if (bi == 0x7fffffff || v < best || (v != v && best == best)) { best = v; bi = c; }
+    }
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
-        if (ov < best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+        const bool onan = ov != ov, bnan = best != best;
+        if (onan ? (!bnan || oi < bi) : (!bnan && (ov < best || (ov == best && oi < bi)))) { best = ov; bi = oi; }
     }
     if (lane == 0) idx[p] = bi;
 }

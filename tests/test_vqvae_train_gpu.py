@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import golden_util as gu
+import pixel_ops_ref as R
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -81,20 +82,12 @@ def test_vq_step_kernel_matches_fp64(d, k):
     idx, q, gq, diff, counts, cs, em, e = runs[0]
     for a, b in zip(runs[0], runs[1]):
         assert torch.equal(a, b)                                            # bit-identical reruns: no float atomics
-    # fp64 restatement of modules.py:18-43
+    # fp64 restatement of modules.py:18-43 (pixel_ops_ref.vq_step)
     f64 = feat.float().double()
     assert torch.equal(idx.view(-1), codes)
-    onehot = torch.nn.functional.one_hot(codes, k).double()
-    cnt = onehot.sum(0)
+    r = R.vq_step(f64, codes, emb.float(), cs0.float(), mean0.float(), decay, 1 - decay, eps, commit)
+    cnt, q_ref, cs_ref, em_ref, e_ref, diff_ref, g_ref = (r[k] for k in ('counts', 'q', 'cs', 'em', 'e', 'diff', 'g'))
     assert torch.equal(counts.double(), cnt) and cnt[5] == 0 and cnt[3] > p // 2
-    e32 = emb.float().double()
-    q_ref = e32[:, codes].t()
-    cs_ref = cs0.float().double() * decay + (1 - decay) * cnt
-    em_ref = mean0.float().double() * decay + (1 - decay) * (f64.t() @ onehot)
-    n = cs_ref.sum()
-    e_ref = em_ref / ((cs_ref + eps) / (n + k * eps) * n)
-    diff_ref = ((q_ref - f64) ** 2).mean()
-    g_ref = commit * 2 * (f64 - q_ref) / (p * d)
     assert _rel(q.view(p, d), q_ref) == 0.0
     assert _rel(cs, cs_ref) < 1e-6 and _rel(em, em_ref) < 1e-6 and _rel(e, e_ref) < 1e-6
     assert abs(float(diff) - float(diff_ref)) <= 1e-6 * float(diff_ref)
