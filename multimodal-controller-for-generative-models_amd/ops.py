@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os as _os
 from dataclasses import dataclass
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -448,6 +448,185 @@ def conv_fused(segs: Sequence[Seg], wimg: Tensor, cout: int, *, bias: Optional[T
     return y, stats
 
 
+# ---- weight gradients: which kernel a layer gets, its pixel splits and the slab reductions ---------------
+MULTI_LOG = None         # tools: receives (map side, ksize, 128-pixel steps, tiles, splits) per layer of every wgrad_multi launch
+WGRAD_LOG = None         # tests: a list that receives which weight-gradient kernel family a call with default splits takes
+BATCH_LOG = None         # tools / tests: receives the layer count of every mcgen_wgrad_batch launch
+_deferred = None         # the open deferred_reduces context's queue (_ReduceJob and _PendingLayer entries, in call order)
+_MULTI = _flag('MCGEN_WGRAD_MULTI', '1') != '0'        # eligible 3x3 weight gradients of a pass as one mcgen_wgrad_multi launch
+_BATCH = _flag('MCGEN_WGRAD_BATCH', '1') != '0'        # the other layers of a pass: same-shape groups as one mcgen_wgrad_batch launch
+_WG_GROUP_MIN = 1 << 30 if _flag('MCGEN_WGRAD_GROUP', '1') == '0' else 4      # chunks from which a 1x1 gradient runs as chunk groups
+_WG_MAX_SPLITS = int(_flag('MCGEN_WGRAD_MAX_SPLITS', '128'))   # (64 left the thin image layers -- 2 blocks -- on half the chip)
+_WG_TARGET = int(_flag('MCGEN_WGRAD_TARGET', '256'))   # workgroups a weight-gradient launch aims for
+_WG_W1 = float(_flag('MCGEN_WG_W1', '0.55'))        # cost of a 1x1 layer's 128-pixel step relative to a 3x3 layer's (the same staging, a ninth of the MFMAs)
+_WG_FIX = float(_flag('MCGEN_WG_FIX', '5'))        # fixed cost of a workgroup (setup, the accumulator flush) in steps
+_CU_COUNT = {}
+
+
+def _cu_count(device) -> int:
+    n = _CU_COUNT.get(device)
+    if n is None:
+        n = _CU_COUNT[device] = torch.cuda.get_device_properties(device).multi_processor_count
+    return n
+
+
+def _default_splits(m_tiles: int, cout: int, nchunk: int, ksize: int, bf16: bool, h: int, w: int, n: int, c8: bool, paired: bool,
+                    cus: int) -> int:
+    """Pixel splits of a weight-gradient launch whose caller names none (`cus`: the device's CU count, read for c8 only)."""
+    # 1x1 gradients with >= 4 chunks run as chunk groups of 4 (wgrad.hip): a quarter of the workgroups per split
+    # (wgrad.hip: the ring form -- bf16, tiles inside one image -- comes first; chunk groups are for the small maps)
+    ring = bf16 and h * w >= 128 and w <= 64 and (n * h * w) % 128 == 0
+    grouped = ksize == 1 and nchunk >= _WG_GROUP_MIN and bf16 and not ring
+    blocks = ((pad16(cout) + 63) // 64) * ((nchunk + 3) // 4 if grouped else nchunk)
+    # enough workgroups to fill the chip matters more than the slab traffic (measured: 8x8 layers lose
+    # 20 % with 16 instead of 64 splits)
+    splits = max(1, min(m_tiles, (_WG_TARGET + blocks - 1) // blocks, _WG_MAX_SPLITS))
+    if c8:
+        # the image-layer kernel streams dy with every output channel in one workgroup (256-pixel steps): one per CU
+        splits = max(1, min(m_tiles // 2, cus))
+    if paired:
+        splits = max(2, splits + (splits & 1))
+    return splits
+
+
+def _plan_multi(layers, budget: int):
+    """Pixel splits of the layers of one mcgen_wgrad_multi launch: `layers` = [(m_tiles, blocks, ksize, side, paired)] (128-pixel
+    steps, workgroup tiles per split, 1 or 3, map side, two-half launch), `budget` = workgroups the launch may total (one per CU).
+    Pure integer / float arithmetic: tests/test_wgrad_plan_cpu.py pins it."""
+    # Cost model of one workgroup of a layer with `sp` pixel splits: fix + (m_tiles / sp) * w in units of a 3x3
+    # layer's 128-pixel step; the launch lasts as long as its slowest workgroup, so the splits are the smallest that
+    # bring every layer under a common time T, T as small as the CU budget allows.  Calibrated with
+    # tools/wgmulti_cost.py (one layer per launch, 16 .. 128 steps per workgroup): 3x3 4.0 us per step + 20 us fixed on
+    # every map size (so `side` does not enter), 1x1 2.15 us per step + 6 us: w(1x1) = 0.55, fix = 5 steps (3x3) / 1.5 (1x1).
+    # (The first version split in proportion to w * steps with w(1x1) = 0.35 and no fixed part: the generator's three
+    # shortcut layers got one workgroup per tile and ran 256 steps each while the 3x3 layers' workgroups were done after
+    # 86: 518 us for a pass that now takes 388; the discriminator's launches 143 -> 136 us.)
+    rows = [(m_tiles, blocks, 1.0 if ksize == 3 else _WG_W1, _WG_FIX if ksize == 3 else 0.3 * _WG_FIX, 2 if paired else 1)
+            for m_tiles, blocks, ksize, _side, paired in layers]
+
+    def need(m_tiles, w, fix, unit, t):
+        cap = max(unit, m_tiles // unit * unit)
+        if t <= fix:
+            return cap
+        sp = int(-(-m_tiles * w // (t - fix)))
+        sp = -(-sp // unit) * unit
+        return max(unit, min(cap, sp))
+    lo, hi = _WG_FIX, _WG_FIX + max(m_tiles * w for m_tiles, _, w, _, _ in rows) + 1.0
+    for _ in range(40):
+        mid = 0.5 * (lo + hi)
+        if sum(need(m_tiles, w, fix, unit, mid) * blocks for m_tiles, blocks, w, fix, unit in rows) <= budget:
+            hi = mid
+        else:
+            lo = mid
+    splits = [need(m_tiles, w, fix, unit, hi) for m_tiles, _, w, fix, unit in rows]
+    # hand the workgroups left over to the layers with the most work per workgroup
+    used = sum(sp * r[1] for sp, r in zip(splits, rows))
+    while True:
+        best = None
+        for i, (m_tiles, blocks, w, _, unit) in enumerate(rows):
+            if splits[i] + unit <= m_tiles // unit * unit and used + unit * blocks <= budget:
+                load = m_tiles / splits[i] * w
+                if best is None or load > best[0]:
+                    best = (load, i, unit, blocks)
+        if best is None:
+            return splits
+        splits[best[1]] += best[2]
+        used += best[2] * best[3]
+
+
+class _ReduceJob(NamedTuple):
+    """One slab reduction: the fields of mcgen_wreduce_t, as tensors where they are pointers (which keeps those alive)."""
+    slabs: Tensor
+    grad: Tensor
+    bias_slabs: Optional[Tensor]
+    bias_grad: Optional[Tensor]
+    bias_grad2: Optional[Tensor]
+    splits: int
+    Cout: int
+    Cin: int
+    ksize: int
+    Cout_w: int
+    row_perm: int
+    accumulate: int
+    alpha: float
+    row_scale: Optional[Tensor]
+    cin_slab: int
+    tapcols: int
+    tap0: int
+    ntap_out: int
+
+    def fill(self, a: _lib.WReduce):
+        """As one element of a mcgen_wgrad_reduce_batch table."""
+        a.slabs, a.grad, a.bias_slabs = _p(self.slabs), _f32(self.grad), _p(self.bias_slabs)
+        a.bias_grad = _f32(self.bias_grad) if self.bias_slabs is not None else None
+        a.bias_grad2 = _f32(self.bias_grad2) if self.bias_slabs is not None else None
+        a.splits, a.Cout, a.Cin, a.ksize, a.Cout_w = self.splits, self.Cout, self.Cin, self.ksize, self.Cout_w
+        a.row_perm, a.accumulate, a.alpha = self.row_perm, self.accumulate, self.alpha
+        a.row_scale, a.cin_slab = _f32(self.row_scale), self.cin_slab
+        a.tapcols, a.tap0, a.ntap_out = self.tapcols, self.tap0, self.ntap_out
+
+    def launch(self):
+        """On its own, now (outside a deferred_reduces context)."""
+        _timed(lambda: 'wgrad_reduce', 0.0,
+               lambda: check(_lib.load().mcgen_wgrad_reduce(
+                   _p(self.slabs), self.splits, _f32(self.grad), self.Cout, self.Cin, self.ksize, self.Cout_w, self.row_perm,
+                   self.alpha, self.accumulate, _p(self.bias_slabs), _f32(self.bias_grad), _f32(self.bias_grad2), _f32(self.row_scale),
+                   self.cin_slab, self.tapcols, self.tap0, self.ntap_out, _stream()), 'wgrad_reduce'),
+               lambda: _nbytes(self.grad), lambda: _nbytes(self.slabs, self.bias_slabs))
+
+
+class _PendingLayer:
+    """One weight-gradient layer between ops.wgrad's checks and its slab reduction.  `kind`: 'multi' = queued for the pass's
+    mcgen_wgrad_multi launch (`splits` comes from _plan_multi), 'batch' = queued for a same-shape mcgen_wgrad_batch launch,
+    'single' = launched by ops.wgrad itself (never queued)."""
+    __slots__ = ('kind', 'p', 'seg', 'dy', 'cout', 'cin', 'grad', 'bias_grad', 'bias_grad2', 'second', 'alpha', 'accumulate',
+                 'row_perm', 'row_scale', 'taps', 'm_tiles', 'blocks', 'splits', 'c8', 'slabs', 'bias_slabs')
+
+    def __init__(self, kind, p, seg, dy, cout, cin, grad, bias_grad, bias_grad2, second, alpha, accumulate, row_perm, row_scale, taps,
+                 c8, m_tiles, blocks, splits):
+        self.kind, self.p, self.seg, self.dy, self.cout, self.cin = kind, p, seg, dy, cout, cin
+        self.grad, self.bias_grad, self.bias_grad2, self.second = grad, bias_grad, bias_grad2, second
+        self.alpha, self.accumulate, self.row_perm, self.row_scale, self.taps = alpha, accumulate, row_perm, row_scale, taps
+        self.m_tiles, self.blocks, self.splits, self.c8 = m_tiles, blocks, splits, c8
+        self.slabs = self.bias_slabs = None
+
+    def alloc(self):
+        """Allocates the split-K slabs (and bias slabs) for `splits` and points the launch parameters at them; returns what
+        _timed wants of the layer: (flops, algorithmic bytes, slab bytes)."""
+        p, seg, ks, lib = self.p, self.seg, self.seg.ksize, _lib.load()
+        elems = int(lib.mcgen_wgrad_c8_slab_elems(C.byref(p)) if self.c8 else lib.mcgen_wgrad_slab_elems(C.byref(p)))
+        self.slabs = torch.empty((self.splits, elems), dtype=torch.float32, device=self.dy.device)
+        if self.bias_grad is not None:
+            self.bias_slabs = torch.empty((self.splits * 4, pad16(self.cout)), dtype=torch.float32, device=self.dy.device)
+        p.splits, p.slabs, p.bias_slabs = self.splits, _p(self.slabs), _p(self.bias_slabs)
+        # algorithmic bytes: x + dy read once, dW (+ db) written once; the split-K slabs are the implementation's
+        return (2.0 * p.N * p.H * p.W * self.cout * seg.x.shape[-1] * ks ** 2,
+                _nbytes(seg.x, self.dy) + 4 * (self.cout * self.cin * ks ** 2 + (self.cout if self.bias_grad is not None else 0)) * (2 if self.second is not None else 1),
+                _nbytes(self.slabs, self.bias_slabs))
+
+    def jobs(self):
+        """The layer's slab reduction(s): one, or one per half of a two-half launch, each over its half of the slabs."""
+        tail = (self.cout, self.cin, self.seg.ksize, pad16(self.cout), self.row_perm, int(self.accumulate), float(self.alpha),
+                self.row_scale, self.seg.x.shape[-1], int(self.c8)) + tuple(self.taps)
+        if self.second is None:
+            return [_ReduceJob(self.slabs, self.grad, self.bias_slabs, self.bias_grad, self.bias_grad2, self.splits, *tail)]
+        hs = self.splits // 2
+        b0, b1 = (self.bias_slabs[:hs * 4], self.bias_slabs[hs * 4:]) if self.bias_slabs is not None else (None, None)
+        return [_ReduceJob(self.slabs[:hs], self.grad, b0, self.bias_grad, self.bias_grad2, hs, *tail),
+                _ReduceJob(self.slabs[hs:], self.second[0], b1, self.second[1], self.second[2], hs, *tail)]
+
+
+def _alloc_table(grp):
+    """alloc() for every layer of one multi / batch launch -> (the launch's mcgen_wgrad_t table, flops, bytes, slab bytes)."""
+    arr = (_lib.Wgrad * len(grp))()
+    flops = nbytes = extra = 0.0
+    for a, q in zip(arr, grp):
+        f, b, e = q.alloc()
+        flops, nbytes, extra = flops + f, nbytes + b, extra + e
+        C.memmove(C.byref(a), C.byref(q.p), C.sizeof(_lib.Wgrad))
+    return arr, flops, nbytes, extra
+
+
 def wgrad(seg: Seg, dy: Tensor, cout: int, cin: int, grad: Tensor, *, dy_ups: bool = False,
           alpha: float = 1.0, accumulate: bool = False, row_perm: int = 1, splits: Optional[int] = None,
           bias_grad: Optional[Tensor] = None, bias_grad2: Optional[Tensor] = None, second=None,
@@ -474,27 +653,14 @@ def wgrad(seg: Seg, dy: Tensor, cout: int, cin: int, grad: Tensor, *, dy_ups: bo
     if tuple(dy.shape[:3]) != exp or dy.dtype != dtype:
         raise _lib.McgenError(f'dy must be {exp}+[C] {dtype}, got {tuple(dy.shape)} {dy.dtype}')
     m_tiles = (n * h * w + 127) // 128
-    nchunk = (seg.x.shape[-1] + 31) // 32
     explicit_splits = splits
     # the image-side layers (conv input = the 8-channel image tensor) have their own kernel and compact slabs (wgrad_c8.hip)
     c8 = bool(_lib.load().mcgen_wgrad_c8_ok(C.byref(p), _dt(dtype)))
     if WGRAD_LOG is not None:
         WGRAD_LOG.append('c8' if c8 else 'general')
     if splits is None:
-        # 1x1 gradients with >= 4 chunks run as chunk groups of 4 (wgrad.hip): a quarter of the workgroups per split
-        # (wgrad.hip: the ring form -- bf16, tiles inside one image -- comes first; chunk groups are for the small maps)
-        ring = dtype == torch.bfloat16 and h * w >= 128 and w <= 64 and (n * h * w) % 128 == 0
-        grouped = seg.ksize == 1 and nchunk >= _WG_GROUP_MIN and dtype == torch.bfloat16 and not ring
-        blocks = ((pad16(cout) + 63) // 64) * ((nchunk + 3) // 4 if grouped else nchunk)
-        # enough workgroups to fill the chip matters more than the slab traffic (measured: 8x8 layers lose
-        # 20 % with 16 instead of 64 splits)
-        target = _WG_TARGET if m_tiles >= _WG_BIG_TILES else _WG_TARGET_SMALL
-        splits = max(1, min(m_tiles, (target + blocks - 1) // blocks, _WG_MAX_SPLITS))
-        if c8:
-            # the image-layer kernel streams dy with every output channel in one workgroup (256-pixel steps): one per CU
-            splits = max(1, min(m_tiles // 2, _cu_count(dy.device)))
-        if second is not None:
-            splits = max(2, splits + (splits & 1))
+        splits = _default_splits(m_tiles, cout, (seg.x.shape[-1] + 31) // 32, seg.ksize, dtype == torch.bfloat16, h, w, n, c8,
+                                 second is not None, _cu_count(dy.device) if c8 else 0)
     if second is not None and ((n * h * w) % 256 != 0 or splits % 2):
         raise _lib.McgenError('wgrad: a two-half launch needs whole 128-pixel tiles per half and even splits')
     p.splits = splits
@@ -505,185 +671,50 @@ def wgrad(seg: Seg, dy: Tensor, cout: int, cin: int, grad: Tensor, *, dy_ups: bo
         raise _lib.McgenError('wgrad: bad tap window (and tap windows do not combine with two-half launches)')
     if grad.numel() != cout * cin * (ntap_out or seg.ksize * seg.ksize):
         raise _lib.McgenError(f'grad has {grad.numel()} elements, expected {cout * cin * (ntap_out or seg.ksize ** 2)}')
+    kind, blocks = 'single', 0
     if (_deferred is not None and _MULTI and explicit_splits is None and dtype == torch.bfloat16
             and lib.mcgen_wgrad_multi_ok(C.byref(p), _dt(dtype))):
         # The 3x3 layers of a backward pass share ONE launch (mcgen_wgrad_multi): queued here, launched when the pass's
         # deferred_reduces context closes -- its pixel splits are sized by the layer's share of the pass's FLOPs.
-        if not grad.is_contiguous():
-            raise _lib.McgenError('deferred wgrad reduce needs a contiguous gradient tensor')
-        _deferred.append(_PendingMulti(p, seg, dy, cout, cin, grad, bias_grad, bias_grad2, second, alpha, accumulate, row_perm,
-                                       row_scale, m_tiles, (pad16(cout) // 128) * (seg.x.shape[-1] // 64), (tap0, ntap_out)))
-        return
-    if (_deferred is not None and _BATCH and dtype == torch.bfloat16 and not c8 and second is None and explicit_splits is None
-            and not _SIDE and splits * _lib.WGRAD_MULTI_MAX <= 65535):
+        kind, blocks, splits = 'multi', (pad16(cout) // 128) * (seg.x.shape[-1] // 64), None
+    elif (_deferred is not None and _BATCH and dtype == torch.bfloat16 and not c8 and second is None and explicit_splits is None
+            and splits * _lib.WGRAD_MULTI_MAX <= 65535):
         # Layers the pass-wide kernel does not take (skinny channel counts, 4x4 maps ...) wait for the end of the pass too: those of
         # IDENTICAL shape share one launch of their kernel (mcgen_wgrad_batch: MCGlow has 16 flows per level)
+        kind = 'batch'
+    q = _PendingLayer(kind, p, seg, dy, cout, cin, grad, bias_grad, bias_grad2, second, alpha, accumulate, row_perm, row_scale,
+                      (tap0, ntap_out), c8, m_tiles, blocks, splits)
+    if kind != 'single':
         if not grad.is_contiguous():
             raise _lib.McgenError('deferred wgrad reduce needs a contiguous gradient tensor')
-        q = _PendingMulti(p, seg, dy, cout, cin, grad, bias_grad, bias_grad2, None, alpha, accumulate, row_perm, row_scale, m_tiles, 0,
-                          (tap0, ntap_out))
-        q.splits, q.batch = splits, True
         _deferred.append(q)
         return
-    elems = int(lib.mcgen_wgrad_c8_slab_elems(C.byref(p)) if c8 else lib.mcgen_wgrad_slab_elems(C.byref(p)))
-    # Inside a deferred_reduces() pass the split-K kernel goes to a side stream: it depends only on tensors that
-    # already exist, and nothing reads its slabs before the pass's batched reduce, so it overlaps the
-    # input-gradient chain that continues on the main stream.
-    side = _side_stream(dy.device) if (_deferred is not None and _SIDE) else None
-    if side is not None:
-        side.wait_stream(torch.cuda.current_stream())
-        _side_keep.extend((seg.x, dy, seg.scale, seg.shift, seg.code))      # keep alive until the join
-    with (torch.cuda.stream(side) if side is not None else _nullctx()):
-        slabs = torch.empty((splits, elems), dtype=torch.float32, device=dy.device)
-        p.slabs = _p(slabs)
-        bias_slabs = None
-        if bias_grad is not None:
-            bias_slabs = torch.empty((splits * 4, pad16(cout)), dtype=torch.float32, device=dy.device)
-        p.bias_slabs = _p(bias_slabs)
-        _timed(lambda: f'wgrad<{"bf16" if dtype == torch.bfloat16 else "f32"},{seg.ksize}>' + (
-            f' N{n} {h}x{w} {seg.x.shape[-1]}->{cout} s{splits}' if _PROF_SHAPES else ''),
-               2.0 * n * h * w * cout * seg.x.shape[-1] * seg.ksize ** 2,
-               lambda: check(lib.mcgen_wgrad(C.byref(p), _dt(dtype), _stream()), 'wgrad'),
-               # algorithmic bytes: x + dy read once, dW (+ db) written once; the split-K slabs are the implementation's
-               lambda: _nbytes(seg.x, dy) + 4 * (cout * cin * seg.ksize ** 2 + (cout if bias_grad is not None else 0)) * (2 if second is not None else 1),
-               lambda: _nbytes(slabs, bias_slabs))
-    if second is None:
-        parts = [(slabs, bias_slabs, grad, bias_grad, bias_grad2, splits)]
-    else:
-        hs = splits // 2
-        parts = [(slabs[:hs], bias_slabs[:hs * 4] if bias_slabs is not None else None, grad, bias_grad, bias_grad2, hs),
-                 (slabs[hs:], bias_slabs[hs * 4:] if bias_slabs is not None else None, second[0], second[1], second[2], hs)]
-    for sl, bs, gr, bg, bg2, ns in parts:
-        if _deferred is not None:
-            if not gr.is_contiguous():
-                raise _lib.McgenError('deferred wgrad reduce needs a contiguous gradient tensor')
-            _deferred.append((sl, gr, bs, bg, bg2, ns, cout, cin, seg.ksize, pad16(cout), row_perm, int(accumulate), float(alpha),
-                              row_scale, seg.x.shape[-1], int(c8), tap0, ntap_out))
+    flops, nbytes, extra = q.alloc()
+    _timed(lambda: f'wgrad<{"bf16" if dtype == torch.bfloat16 else "f32"},{seg.ksize}>' + (
+        f' N{n} {h}x{w} {seg.x.shape[-1]}->{cout} s{splits}' if _PROF_SHAPES else ''), flops,
+           lambda: check(lib.mcgen_wgrad(C.byref(p), _dt(dtype), _stream()), 'wgrad'), lambda: nbytes, lambda: extra)
+    for job in q.jobs():
+        if _deferred is None:
+            job.launch()
+        elif not job.grad.is_contiguous():
+            raise _lib.McgenError('deferred wgrad reduce needs a contiguous gradient tensor')
         else:
-            _timed(lambda: 'wgrad_reduce', 0.0,
-                   lambda: check(lib.mcgen_wgrad_reduce(_p(sl), ns, _f32(gr), cout, cin, seg.ksize, pad16(cout), row_perm,
-                                                        float(alpha), int(accumulate), _p(bs), _f32(bg), _f32(bg2), _f32(row_scale),
-                                                        seg.x.shape[-1], int(c8), tap0, ntap_out, _stream()), 'wgrad_reduce'),
-                   lambda: _nbytes(gr), lambda: _nbytes(sl, bs))
-
-
-MULTI_LOG = None         # tools: receives (map side, ksize, 128-pixel steps, tiles, splits) per layer of every wgrad_multi launch
-WGRAD_LOG = None         # tests: a list that receives which weight-gradient kernel family a call with default splits takes
-_deferred = None
-_MULTI = _flag('MCGEN_WGRAD_MULTI', '1') != '0'        # eligible 3x3 weight gradients of a pass as one mcgen_wgrad_multi launch
-_BATCH = _flag('MCGEN_WGRAD_BATCH', '1') != '0'        # the other layers of a pass: same-shape groups as one mcgen_wgrad_batch launch
-BATCH_LOG = None                                       # tools / tests: receives the layer count of every mcgen_wgrad_batch launch
-_CU_COUNT = {}
-
-
-def _cu_count(device) -> int:
-    n = _CU_COUNT.get(device)
-    if n is None:
-        n = _CU_COUNT[device] = torch.cuda.get_device_properties(device).multi_processor_count
-    return n
-
-
-class _PendingMulti:
-    """One queued layer of a mcgen_wgrad_multi launch (see ops.wgrad)."""
-    __slots__ = ('p', 'seg', 'dy', 'cout', 'cin', 'grad', 'bias_grad', 'bias_grad2', 'second', 'alpha', 'accumulate', 'row_perm',
-                 'row_scale', 'm_tiles', 'blocks', 'splits', 'slabs', 'bias_slabs', 'taps', 'batch')
-
-    def __init__(self, p, seg, dy, cout, cin, grad, bias_grad, bias_grad2, second, alpha, accumulate, row_perm, row_scale, m_tiles, blocks,
-                 taps=(0, 0)):
-        self.taps = taps
-        self.batch = False            # True: a layer of a same-shape batch (mcgen_wgrad_batch), splits already chosen
-        self.p, self.seg, self.dy, self.cout, self.cin = p, seg, dy, cout, cin
-        self.grad, self.bias_grad, self.bias_grad2, self.second = grad, bias_grad, bias_grad2, second
-        self.alpha, self.accumulate, self.row_perm, self.row_scale = alpha, accumulate, row_perm, row_scale
-        self.m_tiles, self.blocks = m_tiles, blocks
-
-    def jobs(self):
-        """The slab-reduce job(s) of the layer, in deferred_reduces' tuple form."""
-        cw, ks, cs = pad16(self.cout), self.seg.ksize, self.seg.x.shape[-1]
-        tail = (self.cout, self.cin, ks, cw, self.row_perm, int(self.accumulate), float(self.alpha), self.row_scale, cs, 0) + tuple(self.taps)
-        if self.second is None:
-            return [(self.slabs, self.grad, self.bias_slabs, self.bias_grad, self.bias_grad2, self.splits) + tail]
-        hs = self.splits // 2
-        b0 = self.bias_slabs[:hs * 4] if self.bias_slabs is not None else None
-        b1 = self.bias_slabs[hs * 4:] if self.bias_slabs is not None else None
-        return [(self.slabs[:hs], self.grad, b0, self.bias_grad, self.bias_grad2, hs) + tail,
-                (self.slabs[hs:], self.second[0], b1, self.second[1], self.second[2], hs) + tail]
-
-
-_WG_W1 = float(_flag('MCGEN_WG_W1', '0.55'))        # cost of a 1x1 layer's 128-pixel step relative to a 3x3 layer's (the same staging, a ninth of the MFMAs)
-_WG_W16 = float(_flag('MCGEN_WG_W16', '1.0'))      # ... of a step on 16x16 maps, on 8x8 maps (more halo per step)
-_WG_W8 = float(_flag('MCGEN_WG_W8', '1.0'))
-_WG_FIX = float(_flag('MCGEN_WG_FIX', '5'))        # fixed cost of a workgroup (setup, the accumulator flush) in steps
+            _deferred.append(job)
 
 
 def _launch_multi(pend):
-    """Size the queued layers' pixel splits by their share of the pass's work (128-pixel steps x workgroup tiles), one
-    workgroup per CU over the whole launch, allocate the slabs and launch mcgen_wgrad_multi (<= MCGEN_WGRAD_MULTI_MAX layers each)."""
+    """Size the queued layers' pixel splits by their share of the pass's work (_plan_multi: one workgroup per CU over the
+    whole launch), allocate the slabs and launch mcgen_wgrad_multi (<= MCGEN_WGRAD_MULTI_MAX layers each)."""
     lib = _lib.load()
-    dev = pend[0].dy.device
+    budget = _cu_count(pend[0].dy.device)
     for base in range(0, len(pend), _lib.WGRAD_MULTI_MAX):
         grp = pend[base:base + _lib.WGRAD_MULTI_MAX]
-        budget = _cu_count(dev)
-        # Cost model of one workgroup of layer q with `sp` pixel splits: fix(q) + (m_tiles / sp) * w(q) in units of a 3x3
-        # layer's 128-pixel step; the launch lasts as long as its slowest workgroup, so the splits are the smallest that
-        # bring every layer under a common time T, T as small as the CU budget allows.  Calibrated with
-        # tools/wgmulti_cost.py (one layer per launch, 16 .. 128 steps per workgroup): 3x3 4.0 us per step + 20 us fixed on
-        # every map size, 1x1 2.15 us per step + 6 us: w(1x1) = 0.55, fix = 5 steps (3x3) / 1.5 (1x1).  (The first version
-        # split in proportion to w * steps with w(1x1) = 0.35 and no fixed part: the generator's three shortcut layers got one
-        # workgroup per tile and ran 256 steps each while the 3x3 layers' workgroups were done after 86: 518 us for a pass
-        # that now takes 388; the discriminator's launches 143 -> 136 us.)
-        def wq(q):
-            side = q.p.H
-            w = 1.0 if q.seg.ksize == 3 else _WG_W1
-            return w * (_WG_W8 if side <= 8 else (_WG_W16 if side <= 16 else 1.0))
-
-        def need(q, t):
-            unit = 2 if q.second is not None else 1
-            cap = max(unit, q.m_tiles // unit * unit)
-            fix = _WG_FIX if q.seg.ksize == 3 else 0.3 * _WG_FIX
-            if t <= fix:
-                return cap
-            sp = int(-(-q.m_tiles * wq(q) // (t - fix)))
-            sp = -(-sp // unit) * unit
-            return max(unit, min(cap, sp))
-        lo, hi = _WG_FIX, _WG_FIX + max(q.m_tiles * wq(q) for q in grp) + 1.0
-        for _ in range(40):
-            mid = 0.5 * (lo + hi)
-            if sum(need(q, mid) * q.blocks for q in grp) <= budget:
-                hi = mid
-            else:
-                lo = mid
-        for q in grp:
-            q.splits = need(q, hi)
-        # hand the workgroups left over to the layers with the most work per workgroup
-        used = sum(q.splits * q.blocks for q in grp)
-        while True:
-            best = None
-            for q in grp:
-                unit = 2 if q.second is not None else 1
-                if q.splits + unit <= q.m_tiles // unit * unit and used + unit * q.blocks <= budget:
-                    load = q.m_tiles / q.splits * wq(q)
-                    if best is None or load > best[0]:
-                        best = (load, q, unit)
-            if best is None:
-                break
-            best[1].splits += best[2]
-            used += best[2] * best[1].blocks
+        plan = _plan_multi([(q.m_tiles, q.blocks, q.seg.ksize, q.p.H, q.second is not None) for q in grp], budget)
+        for q, sp in zip(grp, plan):
+            q.splits = sp
         if MULTI_LOG is not None:
             MULTI_LOG.append([(q.p.H, q.seg.ksize, q.m_tiles, q.blocks, q.splits) for q in grp])
-        arr = (_lib.Wgrad * len(grp))()
-        flops = nbytes = extra = 0.0
-        for a, q in zip(arr, grp):
-            elems = int(lib.mcgen_wgrad_slab_elems(C.byref(q.p)))
-            q.slabs = torch.empty((q.splits, elems), dtype=torch.float32, device=dev)
-            q.bias_slabs = (torch.empty((q.splits * 4, pad16(q.cout)), dtype=torch.float32, device=dev)
-                            if q.bias_grad is not None else None)
-            q.p.splits, q.p.slabs, q.p.bias_slabs = q.splits, _p(q.slabs), _p(q.bias_slabs)
-            C.memmove(C.byref(a), C.byref(q.p), C.sizeof(_lib.Wgrad))
-            n, hh, ww = q.p.N, q.p.H, q.p.W
-            flops += 2.0 * n * hh * ww * q.cout * q.seg.x.shape[-1] * q.seg.ksize ** 2
-            nbytes += _nbytes(q.seg.x, q.dy) + 4 * (q.cout * q.cin * q.seg.ksize ** 2 + (q.cout if q.bias_grad is not None else 0)) * (2 if q.second is not None else 1)
-            extra += _nbytes(q.slabs, q.bias_slabs)
+        arr, flops, nbytes, extra = _alloc_table(grp)
         _timed(lambda: 'wgrad_multi<bf16>', flops,
                lambda: check(lib.mcgen_wgrad_multi(arr, len(grp), _lib.BF16, _stream()), 'wgrad_multi'),
                lambda: nbytes, lambda: extra)
@@ -701,55 +732,14 @@ def _launch_batches(pend):
     for grp_all in groups.values():
         for base in range(0, len(grp_all), _lib.WGRAD_MULTI_MAX):
             grp = grp_all[base:base + _lib.WGRAD_MULTI_MAX]
-            dev = grp[0].dy.device
-            arr = (_lib.Wgrad * len(grp))()
-            flops = nbytes = extra = 0.0
-            for a, q in zip(arr, grp):
-                elems = int(lib.mcgen_wgrad_slab_elems(C.byref(q.p)))
-                q.slabs = torch.empty((q.splits, elems), dtype=torch.float32, device=dev)
-                q.bias_slabs = (torch.empty((q.splits * 4, pad16(q.cout)), dtype=torch.float32, device=dev)
-                                if q.bias_grad is not None else None)
-                q.p.slabs, q.p.bias_slabs = _p(q.slabs), _p(q.bias_slabs)
-                C.memmove(C.byref(a), C.byref(q.p), C.sizeof(_lib.Wgrad))
-                flops += 2.0 * q.p.N * q.p.H * q.p.W * q.cout * q.seg.x.shape[-1] * q.seg.ksize ** 2
-                nbytes += _nbytes(q.seg.x, q.dy) + 4 * (q.cout * q.cin * q.seg.ksize ** 2 + (q.cout if q.bias_grad is not None else 0))
-                extra += _nbytes(q.slabs, q.bias_slabs)
+            arr, flops, nbytes, extra = _alloc_table(grp)
             ks = grp[0].seg.ksize
             if BATCH_LOG is not None:
                 BATCH_LOG.append(len(grp))
-            if len(grp) == 1:
-                _timed(lambda: f'wgrad<bf16,{ks}>', flops,
-                       lambda: check(lib.mcgen_wgrad(C.byref(grp[0].p), _lib.BF16, _stream()), 'wgrad'), lambda: nbytes, lambda: extra)
-            else:
-                _timed(lambda: f'wgrad<bf16,{ks}>', flops,
-                       lambda: check(lib.mcgen_wgrad_batch(arr, len(grp), _lib.BF16, _stream()), 'wgrad_batch'), lambda: nbytes, lambda: extra)
-
-
-_SIDE = _flag('MCGEN_SIDE_STREAM', '0') == '1'     # measured slower on MI355X (16.7 vs 15.7 ms/step): opt-in only
-_side_streams = {}
-_side_keep = []
-
-
-def _side_stream(device):
-    s = _side_streams.get(device)
-    if s is None:
-        s = _side_streams[device] = torch.cuda.Stream(device=device)
-    return s
-
-
-class _nullctx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
-_WG_GROUP_MIN = 1 << 30 if _flag('MCGEN_WGRAD_GROUP', '1') == '0' else 4      # chunks from which a 1x1 gradient runs as chunk groups
-_WG_MAX_SPLITS = int(_flag('MCGEN_WGRAD_MAX_SPLITS', '128'))   # (64 left the thin image layers -- 2 blocks -- on half the chip)
-_WG_TARGET = int(_flag('MCGEN_WGRAD_TARGET', '256'))   # workgroups a weight-gradient launch aims for
-_WG_TARGET_SMALL = int(_flag('MCGEN_WGRAD_TARGET_SMALL', '256'))
-_WG_BIG_TILES = int(_flag('MCGEN_WGRAD_BIG_TILES', '256'))
+            _timed(lambda: f'wgrad<bf16,{ks}>', flops,
+                   lambda: (check(lib.mcgen_wgrad(C.byref(grp[0].p), _lib.BF16, _stream()), 'wgrad') if len(grp) == 1 else
+                            check(lib.mcgen_wgrad_batch(arr, len(grp), _lib.BF16, _stream()), 'wgrad_batch')),
+                   lambda: nbytes, lambda: extra)
 
 
 class deferred_reduces:
@@ -764,33 +754,24 @@ class deferred_reduces:
 
     def __exit__(self, et, ev, tb):
         global _deferred
-        jobs, _deferred = _deferred, self._outer
-        pend = [j for j in jobs if isinstance(j, _PendingMulti) and not j.batch]
-        same = [j for j in jobs if isinstance(j, _PendingMulti) and j.batch]
-        if et is None and same:
-            _launch_batches(same)
-        if et is None and (pend or same):
-            if pend:
-                _launch_multi(pend)
-            jobs = [t for j in jobs for t in (j.jobs() if isinstance(j, _PendingMulti) else [j])]
-        elif pend or same:
-            jobs = [j for j in jobs if not isinstance(j, _PendingMulti)]
-        if _SIDE and _side_keep:
-            for s in _side_streams.values():                 # join: the slabs are complete before they are reduced
-                torch.cuda.current_stream().wait_stream(s)
-            if self._outer is None:
-                _side_keep.clear()
-        if et is None and jobs:
-            arr = (_lib.WReduce * len(jobs))()
-            for a, (slabs, grad, bs, bg, bg2, splits, cout, cin, ks, cout_w, row_perm, acc, alpha, rscale, cin_slab, tapcols, tap0, ntap_out) in zip(arr, jobs):
-                a.slabs, a.grad, a.bias_slabs = _p(slabs), _f32(grad), _p(bs)
-                a.bias_grad, a.bias_grad2 = _f32(bg) if bs is not None else None, _f32(bg2) if bs is not None else None
-                a.splits, a.Cout, a.Cin, a.ksize, a.Cout_w = splits, cout, cin, ks, cout_w
-                a.row_perm, a.accumulate, a.alpha = row_perm, acc, alpha
-                a.row_scale, a.cin_slab, a.tapcols, a.tap0, a.ntap_out = _f32(rscale), cin_slab, tapcols, tap0, ntap_out
-            _timed(lambda: 'wgrad_reduce', 0.0,
-                   lambda: check(_lib.load().mcgen_wgrad_reduce_batch(arr, len(jobs), _stream()), 'wgrad_reduce_batch'),
-                   lambda: sum(_nbytes(j[1]) for j in jobs), lambda: sum(_nbytes(j[0], j[2]) for j in jobs))
+        queue, _deferred = _deferred, self._outer
+        if et is not None or not queue:
+            return False
+        kinds = {'multi': [], 'batch': []}
+        for q in queue:
+            if isinstance(q, _PendingLayer):
+                kinds[q.kind].append(q)
+        if kinds['batch']:
+            _launch_batches(kinds['batch'])
+        if kinds['multi']:
+            _launch_multi(kinds['multi'])
+        jobs = [j for q in queue for j in (q.jobs() if isinstance(q, _PendingLayer) else (q,))]
+        arr = (_lib.WReduce * len(jobs))()
+        for a, j in zip(arr, jobs):
+            j.fill(a)
+        _timed(lambda: 'wgrad_reduce', 0.0,
+               lambda: check(_lib.load().mcgen_wgrad_reduce_batch(arr, len(jobs), _stream()), 'wgrad_reduce_batch'),
+               lambda: sum(_nbytes(j.grad) for j in jobs), lambda: sum(_nbytes(j.slabs, j.bias_slabs) for j in jobs))
         return False
 
 

@@ -1441,6 +1441,62 @@ def test_wgrad_multi_matches_the_per_layer_kernels():
     assert float((res[0][1] - res[1][1]).abs().max()) <= 2e-5 * float(res[1][1].abs().max()) + 1e-6
 
 
+def test_one_pass_queues_every_weight_gradient_route():
+    """One ops.deferred_reduces context with a layer on every route of ops.wgrad, at the smallest shapes that reach each: three layers
+    of the pass-wide launch (plain, two-half, tap window: 256 pixels = 2 steps, so the planner gives each its 2 splits), two
+    same-shape skinny layers in one batched launch, a skinny layer alone in its group (the plain kernel), an image layer (c8)
+    and an fp32 layer that launch at once -- and ONE slab reduction for all of them.  Every gradient and bias gradient against
+    torch.nn.grad.conv2d_weight on the operands as the kernels read them."""
+    ops = _ops()
+    g = torch.Generator().manual_seed(4243)
+    bf, f32 = torch.bfloat16, torch.float32
+    # name, dtype, N, H, Cin, Cout, halves, taps, bias
+    spec = [('multi', bf, 4, 8, 64, 128, False, None, True), ('multi paired', bf, 4, 8, 64, 128, True, None, True),
+            ('skinny a', bf, 4, 8, 8, 16, False, None, True), ('skinny b', bf, 4, 8, 8, 16, False, None, True),
+            ('skinny alone', bf, 4, 8, 8, 32, False, None, True), ('image layer', bf, 1, 32, 3, 128, False, None, True),
+            ('multi tap window', bf, 4, 8, 64, 128, False, (3, 2), False), ('fp32', f32, 4, 8, 64, 128, False, None, True)]
+    prob = []
+    for name, dtype, n, h, ci, co, halves, taps, bias in spec:
+        x, dy = _rnd(g, n, ci, h, h), _rnd(g, n, co, h, h) * 0.1
+        image = name == 'image layer'                          # (conv input = the raw image: no prologue)
+        code = None if image else (torch.rand(n, ci, generator=g) < 0.5).float()
+        a = _q(x, dtype) if image else _q(torch.relu(_q(x, dtype)) * code[:, :, None, None], dtype)
+        dyf = _q(dy, dtype)
+        parts = (slice(0, n // 2), slice(n // 2, n)) if halves else (slice(None),)
+        refs = []
+        for sl in parts:
+            gw = torch.nn.grad.conv2d_weight(a[sl], (co, ci, 3, 3), dyf[sl], padding=1)
+            if taps is not None:
+                gw = gw.reshape(co, ci, 9)[:, :, taps[0]:taps[0] + taps[1]]
+            refs.append((gw, dyf[sl].sum((0, 2, 3))))
+        seg = ops.Seg(_nhwc(ops, x, dtype)) if image else ops.Seg(_nhwc(ops, x, dtype), code=code.cuda(), relu=True)
+        prob.append((name, dtype, seg, _nhwc(ops, dy, dtype), co, ci, halves, taps, bias, refs))
+    outs = []
+    ops._PROF, ops.MULTI_LOG, ops.BATCH_LOG, ops.WGRAD_LOG = [], [], [], []
+    try:
+        with ops.deferred_reduces():
+            for name, dtype, seg, dyt, co, ci, halves, taps, bias, refs in prob:
+                gs = [torch.zeros((co, ci, taps[1]) if taps is not None else (co, ci, 3, 3), device='cuda') for _ in refs]
+                bs = [torch.zeros((co,), device='cuda') if bias else None for _ in refs]
+                ops.wgrad(seg, dyt, co, ci, gs[0], bias_grad=bs[0], second=(gs[1], bs[1], None) if halves else None, taps=taps)
+                outs.append((gs, bs))
+        torch.cuda.synchronize()
+        names = sorted(r[0] for r in ops._PROF)
+        multi, batch, family = list(ops.MULTI_LOG), list(ops.BATCH_LOG), list(ops.WGRAD_LOG)
+    finally:
+        ops._PROF = ops.MULTI_LOG = ops.BATCH_LOG = ops.WGRAD_LOG = None
+    assert family == ['general'] * 5 + ['c8'] + ['general'] * 2, family
+    assert batch == [2, 1], batch                                         # the same-shape pair together, the third alone
+    assert multi == [[(8, 3, 2, 1, 2)] * 3], multi                         # (side, ksize, steps, tiles, splits) per layer
+    # image layer, fp32 layer (at once); the batched pair, the lone skinny layer, the pass-wide launch, one reduce (on exit)
+    assert names == ['wgrad<bf16,3>'] * 3 + ['wgrad<f32,3>', 'wgrad_multi<bf16>', 'wgrad_reduce'], names
+    for (name, dtype, *_, bias, refs), (gs, bs) in zip(prob, outs):
+        for hi, ((gr, br), gt, bt) in enumerate(zip(refs, gs, bs)):
+            _assert_close(gt, gr, dtype, f'{name} half {hi}')
+            if bias:
+                _assert_close(bt, br, dtype, f'{name} half {hi} bias')
+
+
 @pytest.mark.parametrize('dtype', DTYPES)
 def test_grouped_batchnorm_pass_equals_separate_passes(dtype):
     """mcgen_seg_t.group_n + mcgen_bn_finalize_groups: two training-mode BatchNorm batches pushed through

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Prints how ops._launch_multi split the layers of the headline step's weight-gradient launches (one eager iteration).
-usage (GPU box): [MCGEN_TUNING=1 MCGEN_WG_*=..] python tools/multi_splits.py"""
+usage (GPU box): [MCGEN_TUNING=1 MCGEN_WG_W1=.. MCGEN_WG_FIX=..] python tools/multi_splits.py
+(ops._plan_multi is the arithmetic alone: it runs without a GPU on any list of layers)"""
 import os
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
