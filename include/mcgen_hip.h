@@ -31,7 +31,7 @@ extern "C" {
 enum { MCGEN_F32 = 0, MCGEN_BF16 = 1 };
 
 const char* mcgen_last_error(void);
-int mcgen_abi_version(void);      /* 9: mcgen_conv_t.y_group (paired output layout of the image head), mcgen_onehot_rep, MCGEN_WREDUCE_MAX 32, mcgen_dtail_hinge_fused, mcgen_wgrad_c8_ok + tapcols slabs (mcgen_wgrad_reduce gained an argument), mcgen_mc_gather_batch(n_label, scale, n_half), mcgen_conv_t.wsel / wsel_stride / order / yperm + mcgen_prep_t.kmap / rmap (per-mode dense weight sets), mcgen_prep_weight_batch_codes, mcgen_wgrad_batch, mcgen_bn_finalize_batch, mcgen_gated_fwd_batch, mcgen_wreduce_t.tap0 / ntap_out; 8: mcgen_adam / mcgen_sn_fix_pair_adam take lr_dev (learning rate read on the device at execution time); 7: + mcgen_conv_form, mcgen_sn_power_iter_rounds, the MCGlow *_batch entry points, mcgen_sn_fix_pair_adam(advance_step); 6: + mcgen_wgrad_multi (5: + mcgen_conv_t.bias2, mcgen_sn_power_iter_snap; 4: compacted activations between forward-only launches) */
+int mcgen_abi_version(void);      /* 9 (additions since, without a bump: the baseline models' entry points, mcgen_conv_plan): mcgen_conv_t.y_group (paired output layout of the image head), mcgen_onehot_rep, MCGEN_WREDUCE_MAX 32, mcgen_dtail_hinge_fused, mcgen_wgrad_c8_ok + tapcols slabs (mcgen_wgrad_reduce gained an argument), mcgen_mc_gather_batch(n_label, scale, n_half), mcgen_conv_t.wsel / wsel_stride / order / yperm + mcgen_prep_t.kmap / rmap (per-mode dense weight sets), mcgen_prep_weight_batch_codes, mcgen_wgrad_batch, mcgen_bn_finalize_batch, mcgen_gated_fwd_batch, mcgen_wreduce_t.tap0 / ntap_out; 8: mcgen_adam / mcgen_sn_fix_pair_adam take lr_dev (learning rate read on the device at execution time); 7: + mcgen_conv_form, mcgen_sn_power_iter_rounds, the MCGlow *_batch entry points, mcgen_sn_fix_pair_adam(advance_step); 6: + mcgen_wgrad_multi (5: + mcgen_conv_t.bias2, mcgen_sn_power_iter_snap; 4: compacted activations between forward-only launches) */
 
 /* One K-segment of a fused convolution: the input tensor and the prologue that
  * is applied while the tile is staged into LDS:
@@ -142,7 +142,27 @@ typedef struct {
     int32_t yperm_stride, reserved_;
 } mcgen_conv_t;
 
-/* number of M tiles (rows of `stats`) the launch of `p` will use.  Depends on the shape / mode fields only -- callers ask
+/* What mcgen_conv_fused will do with `p`: the launcher it hands `p` to and, for the launchers inside conv_fused.hip, the
+ * tile and the launch geometry.  mcgen_conv_fused makes this same plan and launches what it says, so the plan cannot
+ * disagree with the launch.  (An addition: the ABI version stays 9.) */
+enum { MCGEN_ROUTE_TILED = 0,      /* the table of (bm, bn, pipe) forms                                          */
+       MCGEN_ROUTE_MC, MCGEN_ROUTE_GK, MCGEN_ROUTE_GK_PP,      /* K-major: w_layout 1; w_layout 2; its software-pipelined form */
+       MCGEN_ROUTE_SKINNY, MCGEN_ROUTE_SMAP, MCGEN_ROUTE_PX1, MCGEN_ROUTE_C8, MCGEN_ROUTE_HEAD };   /* kernels in files of their own */
+typedef struct {
+    int32_t route;      /* MCGEN_ROUTE_*                                                                        */
+    int32_t form;       /* what mcgen_conv_form reports (0..5)                                                  */
+    int32_t bm, bn, pipe;           /* the tile and pipe code for routes inside conv_fused.hip, else 0           */
+    int32_t m_tiles;                /* rows of `stats`                                                           */
+    int32_t grid_x, grid_y, threads, lds_bytes, a_bytes, grouped;   /* launch geometry for routes inside conv_fused.hip
+                                       (grouped: the dma3g kernel); 0 for the five kernels that live in their own files */
+} mcgen_conv_plan_t;
+/* Fills `out`; returns non-zero, with the same mcgen_last_error text, exactly where mcgen_conv_fused would refuse `p`.
+ * Reads the shape / mode fields and whether buffer pointers are set, never p->stats; makes no HIP call, so it also
+ * answers on a machine without a GPU and before `stats` is allocated. */
+int mcgen_conv_plan(const mcgen_conv_t* p, int dtype, mcgen_conv_plan_t* out);
+/* The three queries below read the same route decision without validating `p` (they answer for a descriptor whose
+ * buffers are not set yet, and for one mcgen_conv_fused would refuse).
+ * number of M tiles (rows of `stats`) the launch of `p` will use.  Depends on the shape / mode fields only -- callers ask
  * BEFORE they allocate `stats`, so no kernel's eligibility may depend on p->stats (or any other buffer pointer being set) */
 int mcgen_conv_m_tiles(const mcgen_conv_t* p, int dtype);
 /* the (pixels x channels) output tile the launcher will pick for `p` (names the kernel instantiation) */

@@ -30,6 +30,11 @@ class Conv(C.Structure):
                 ('yperm', C.c_void_p), ('yperm_stride', C.c_int32), ('reserved_', C.c_int32)]
 
 
+class ConvPlan(C.Structure):                               # mcgen_conv_plan_t
+    _fields_ = [(k, C.c_int32) for k in ('route', 'form', 'bm', 'bn', 'pipe', 'm_tiles',
+                                         'grid_x', 'grid_y', 'threads', 'lds_bytes', 'a_bytes', 'grouped')]
+
+
 class Wgrad(C.Structure):
     _fields_ = [('seg', Seg), ('dy', C.c_void_p),
                 ('N', C.c_int32), ('H', C.c_int32), ('W', C.c_int32),
@@ -140,6 +145,7 @@ _vp, _i, _f, _d, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_int64
 SYMBOLS = {
     'mcgen_last_error': (C.c_char_p, []),
     'mcgen_abi_version': (_i, []),
+    'mcgen_conv_plan': (_i, [C.POINTER(Conv), _i, C.POINTER(ConvPlan)]),
     'mcgen_conv_m_tiles': (_i, [C.POINTER(Conv), _i]),
     'mcgen_conv_tile': (_i, [C.POINTER(Conv), _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'mcgen_conv_form': (_i, [C.POINTER(Conv), _i]),

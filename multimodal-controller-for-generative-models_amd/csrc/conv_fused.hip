@@ -2277,47 +2277,69 @@ static int patch_pixels(const mcgen_conv_t* p, int BM) {
     return best;
 }
 
-// raises the dynamic-LDS limit of `kern` once per process (per instantiation: `raised` is the caller's static)
-static int raise_lds(const void* kern, int lds, int* raised) {
-    if (lds > 64 * 1024 && lds > *raised) {
-        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return mcgen_fail("conv_fused: cannot raise LDS limit to %d: %s", lds, hipGetErrorString(e));
-        *raised = lds;
-    }
-    return 0;
-}
+// ---- launch sizing: one function per form for what differs, size_tile() for what they share --------------------------
+// One launch of a form in this file, sized without a HIP call: what mcgen_conv_plan reports and launch_sized() runs.
+struct Sized {
+    const void* kern;       // the kernel symbol
+    int* raised;            // its dynamic-LDS limit as raised so far in this process (nullptr: set on every launch)
+    const char* name;       // names the launch in a launch failure
+    int grid_x, grid_y, threads, lds, a_bytes, subw, grouped;
+};
+typedef int (*size_fn)(const mcgen_conv_t*, Sized*);
 
-template <typename T, int BM, int BN, int WM, int WN>
-static int launch_cfg(const mcgen_conv_t* p, hipStream_t st) {
-    using C = ConvCfg<T, BM, BN, WM, WN>;
+template <typename... A> static const void* sym(void (*k)(A...)) { return reinterpret_cast<const void*>(k); }
+
+// What every form shares: the window of `PP` pixels against the staging plan (0: the form has checked its own), the grid,
+// and the LDS of the launch -- the form's own `main_bytes`, the epilogue's staging (`fast_px`: pixels per pass of the pp
+// form's merged epilogue, 0 elsewhere) or the statistics reduction, whichever is largest, within the CU's 160 KB.
+template <typename C, int BM, int BN>
+static int size_tile(const mcgen_conv_t* p, const char* who, int PP, int main_bytes, int fast_px, Sized* z) {
+    MCGEN_CHECK(PP * 4 <= C::NI * C::NT, "%s: patch of %d pixels exceeds the staging plan", who, PP);
     const long Mtot = (long)p->N * p->H * p->W;
-    const int mt = (int)((Mtot + BM - 1) / BM);
-    const int nt = (p->Cout_w + BN - 1) / BN;
-    const int PP = patch_pixels(p, BM);
-    MCGEN_CHECK(PP * 4 <= C::NI * C::NT, "conv_fused: patch of %d pixels exceeds the staging plan", PP);
-    int a_bytes = round_up(PP * C::APITCH, 32);
-    int main_bytes = a_bytes + C::BBYTES;
-    int epi_bytes = C::PPX * C::EP * 4 + (p->ycmap ? YTAB_BYTES : 0);
-    int red_bytes = C::PROWS * BN * 2 * 4;
-    int lds = main_bytes > epi_bytes ? main_bytes : epi_bytes;
+    z->grid_x = (int)((Mtot + BM - 1) / BM);
+    z->grid_y = (p->Cout_w + BN - 1) / BN;
+    z->threads = C::NT;
+    const int ytab = p->ycmap ? YTAB_BYTES : 0;
+    const int epi_bytes = C::PPX * C::EP * 4 + ytab, epi_fast = fast_px * C::EP * 4 + ytab, red_bytes = C::PROWS * BN * 2 * 4;
+    int lds = main_bytes;
+    if (epi_bytes > lds) lds = epi_bytes;
+    if (epi_fast > lds) lds = epi_fast;
     if (red_bytes > lds) lds = red_bytes;
-    MCGEN_CHECK(lds <= 160 * 1024, "conv_fused: tile %dx%d needs %d bytes of LDS", BM, BN, lds);
-    auto kern = conv_fused_kernel<T, BM, BN, WM, WN>;
-    static int raised = 0;
-    if (int rc = raise_lds(reinterpret_cast<const void*>(kern), lds, &raised)) return rc;
-    hipLaunchKernelGGL(kern, dim3(mt, nt), dim3(C::NT), lds, st, *p, a_bytes);
-    MCGEN_LAUNCH_CHECK("conv_fused");
+    MCGEN_CHECK(lds <= 160 * 1024, "%s: tile %dx%d needs %d bytes of LDS", who, BM, BN, lds);
+    z->lds = lds;
+    return 0;
+}
+
+// raises the kernel's dynamic-LDS limit once per process and launches
+static int launch_sized(const Sized& z, const mcgen_conv_t* p, hipStream_t st) {
+    int every = 0;
+    int* raised = z.raised ? z.raised : &every;
+    if (z.lds > 64 * 1024 && z.lds > *raised) {
+        hipError_t e = hipFuncSetAttribute(z.kern, hipFuncAttributeMaxDynamicSharedMemorySize, z.lds);
+        if (e != hipSuccess) return mcgen_fail("conv_fused: cannot raise LDS limit to %d: %s", z.lds, hipGetErrorString(e));
+        *raised = z.lds;
+    }
+    int a_bytes = z.a_bytes, subw = z.subw;
+    void* args[] = {const_cast<mcgen_conv_t*>(p), &a_bytes, &subw};      // (p, a_bytes[, subw: the cp form])
+    (void)hipLaunchKernel(z.kern, dim3(z.grid_x, z.grid_y), dim3(z.threads), args, z.lds, st);
+    MCGEN_LAUNCH_CHECK(z.name);
     return 0;
 }
 
 template <typename T, int BM, int BN, int WM, int WN>
-static int launch_dma(const mcgen_conv_t* p, hipStream_t st) {
+static int size_cfg(const mcgen_conv_t* p, Sized* z) {
     using C = ConvCfg<T, BM, BN, WM, WN>;
-    const long Mtot = (long)p->N * p->H * p->W;
-    const int mt = (int)((Mtot + BM - 1) / BM);
-    const int nt = (p->Cout_w + BN - 1) / BN;
+    static int raised = 0;
+    *z = {sym(conv_fused_kernel<T, BM, BN, WM, WN>), &raised, "conv_fused"};
     const int PP = patch_pixels(p, BM);
-    MCGEN_CHECK(PP * 4 <= C::NI * C::NT, "conv_fused: patch of %d pixels exceeds the staging plan", PP);
+    z->a_bytes = round_up(PP * C::APITCH, 32);
+    return size_tile<C, BM, BN>(p, "conv_fused", PP, z->a_bytes + C::BBYTES, 0, z);
+}
+
+template <typename T, int BM, int BN, int WM, int WN>
+static int size_dma(const mcgen_conv_t* p, Sized* z) {
+    using C = ConvCfg<T, BM, BN, WM, WN>;
+    const int PP = patch_pixels(p, BM);
     int a_bytes = round_up(PP * C::APITCH, 1024);
     // pure 1x1 launches with several chunks: the grouped form, when its three side-by-side windows fit the LDS budget
     // (K-deep ones only: at 8 chunks and fewer the plain form measured as fast or faster)
@@ -2325,81 +2347,46 @@ static int launch_dma(const mcgen_conv_t* p, hipStream_t st) {
     const bool grouped = p->nseg == 1 && p->seg[0].ksize == 1 && p->seg[0].C >= 12 * MCGEN_CK &&
                          (a3 > a_bytes ? a3 : a_bytes) + 6 * C::BBYTES <= 96 * 1024;
     if (grouped && a3 > a_bytes) a_bytes = a3;
-    int lds = a_bytes + 2 * (BN <= 16 ? 9 : 3) * C::BBYTES;      // ring: two slots of a group's taps (conv_dma3_kernel: TPS)
-    const int epi_bytes = C::PPX * C::EP * 4 + (p->ycmap ? YTAB_BYTES : 0), red_bytes = C::PROWS * BN * 2 * 4;
-    if (epi_bytes > lds) lds = epi_bytes;
-    if (red_bytes > lds) lds = red_bytes;
-    MCGEN_CHECK(lds <= 160 * 1024, "conv_fused: tile %dx%d needs %d bytes of LDS", BM, BN, lds);
-    if (grouped) {
-        auto kg = conv_dma3g_kernel<T, BM, BN, WM, WN>;
-        static int raisedg = 0;
-        if (int rc = raise_lds(reinterpret_cast<const void*>(kg), lds, &raisedg)) return rc;
-        hipLaunchKernelGGL(kg, dim3(mt, nt), dim3(C::NT), lds, st, *p, a_bytes);
-        MCGEN_LAUNCH_CHECK("conv_fused(dma3g)");
-        return 0;
-    }
-    auto kern = conv_dma3_kernel<T, BM, BN, WM, WN>;
-    static int raised = 0;
-    if (int rc = raise_lds(reinterpret_cast<const void*>(kern), lds, &raised)) return rc;
-    hipLaunchKernelGGL(kern, dim3(mt, nt), dim3(C::NT), lds, st, *p, a_bytes);
-    MCGEN_LAUNCH_CHECK("conv_fused(dma3)");
-    return 0;
+    static int raised = 0, raisedg = 0;
+    if (grouped) *z = {sym(conv_dma3g_kernel<T, BM, BN, WM, WN>), &raisedg, "conv_fused(dma3g)"};
+    else *z = {sym(conv_dma3_kernel<T, BM, BN, WM, WN>), &raised, "conv_fused(dma3)"};
+    z->a_bytes = a_bytes;
+    z->grouped = grouped;
+    // ring: two slots of a group's taps (conv_dma3_kernel: TPS)
+    return size_tile<C, BM, BN>(p, "conv_fused", PP, a_bytes + 2 * (BN <= 16 ? 9 : 3) * C::BBYTES, 0, z);
 }
 
 template <typename T, int BM, int BN, int WM, int WN>
-static int launch_dma1(const mcgen_conv_t* p, hipStream_t st) {
+static int size_dma1(const mcgen_conv_t* p, Sized* z) {
     using C = ConvCfg<T, BM, BN, WM, WN>;
-    const long Mtot = (long)p->N * p->H * p->W;
-    const int mt = (int)((Mtot + BM - 1) / BM);
-    const int nt = (p->Cout_w + BN - 1) / BN;
+    static int raised = 0;
+    *z = {sym(conv_dma1_kernel<T, BM, BN, WM, WN>), &raised, "conv_fused(dma1)"};
     const int PP = patch_pixels(p, BM);
-    MCGEN_CHECK(PP * 4 <= C::NI * C::NT, "conv_fused: patch of %d pixels exceeds the staging plan", PP);
-    const int a_bytes = round_up(PP * C::APITCH, 1024);
-    int lds = a_bytes + 3 * C::BBYTES;
-    const int epi_bytes = C::PPX * C::EP * 4 + (p->ycmap ? YTAB_BYTES : 0), red_bytes = C::PROWS * BN * 2 * 4;
-    if (epi_bytes > lds) lds = epi_bytes;
-    if (red_bytes > lds) lds = red_bytes;
-    MCGEN_CHECK(lds <= 160 * 1024, "conv_fused: tile %dx%d needs %d bytes of LDS", BM, BN, lds);
-    auto kern = conv_dma1_kernel<T, BM, BN, WM, WN>;
-    static int raised = 0;
-    if (int rc = raise_lds(reinterpret_cast<const void*>(kern), lds, &raised)) return rc;
-    hipLaunchKernelGGL(kern, dim3(mt, nt), dim3(C::NT), lds, st, *p, a_bytes);
-    MCGEN_LAUNCH_CHECK("conv_fused(dma1)");
-    return 0;
+    z->a_bytes = round_up(PP * C::APITCH, 1024);
+    return size_tile<C, BM, BN>(p, "conv_fused", PP, z->a_bytes + 3 * C::BBYTES, 0, z);
 }
 
 template <typename T, int BM, int BN, int WM, int WN>
-static int launch_cp(const mcgen_conv_t* p, hipStream_t st) {
+static int size_cp(const mcgen_conv_t* p, Sized* z) {
     using C = ConvCfg<T, BM, BN, WM, WN>;
-    const long Mtot = (long)p->N * p->H * p->W;
-    const int mt = (int)((Mtot + BM - 1) / BM);
-    const int nt = (p->Cout_w + BN - 1) / BN;
+    static int raised = 0;
+    *z = {sym(conv_cp_kernel<T, BM, BN, WM, WN>), &raised, "conv_fused(cp)"};
     const int PP1 = mcgen_patch_pixels(BM, p->H, p->W, 1);
-    const int subw = round_up(PP1 * C::APITCH, 32);                 // one chunk's window of a 1x1 segment
+    z->subw = round_up(PP1 * C::APITCH, 32);                        // one chunk's window of a 1x1 segment
     int a_bytes = 0;
     for (int s = 0; s < p->nseg; ++s) {
         const int ks = p->seg[s].ksize;
         const int PP = mcgen_patch_pixels(BM, p->H, p->W, ks);
         MCGEN_CHECK(PP * 4 <= (ks == 3 ? C::NI : (BM * 4 + C::NT - 1) / C::NT) * C::NT, "conv_fused(cp): patch of %d pixels exceeds the staging plan", PP);
-        const int need = (ks == 3) ? PP * C::APITCH : 8 * subw;
+        const int need = (ks == 3) ? PP * C::APITCH : 8 * z->subw;
         if (need > a_bytes) a_bytes = need;
     }
-    a_bytes = round_up(a_bytes, 1024);
-    int lds = a_bytes + 2 * 9 * C::BBYTES;
-    const int epi_bytes = C::PPX * C::EP * 4 + (p->ycmap ? YTAB_BYTES : 0), red_bytes = C::PROWS * BN * 2 * 4;
-    if (epi_bytes > lds) lds = epi_bytes;
-    if (red_bytes > lds) lds = red_bytes;
-    MCGEN_CHECK(lds <= 160 * 1024, "conv_fused(cp): tile %dx%d needs %d bytes of LDS", BM, BN, lds);
-    auto kern = conv_cp_kernel<T, BM, BN, WM, WN>;
-    static int raised = 0;
-    if (int rc = raise_lds(reinterpret_cast<const void*>(kern), lds, &raised)) return rc;
-    hipLaunchKernelGGL(kern, dim3(mt, nt), dim3(C::NT), lds, st, *p, a_bytes, subw);
-    MCGEN_LAUNCH_CHECK("conv_fused(cp)");
-    return 0;
+    z->a_bytes = round_up(a_bytes, 1024);
+    return size_tile<C, BM, BN>(p, "conv_fused(cp)", 0, z->a_bytes + 2 * 9 * C::BBYTES, 0, z);
 }
 
-// K-major, mode-compacted launches (conv_mc_kernel).  Tile: 256 x 256 where the map has the pixels for it, else
-// 128 x 256 / 128 x 128; always inside one image.
+// K-major, mode-compacted launches (conv_mc_kernel, conv_gk_kernel).  Tile: 256 x 256 where the map has the pixels for
+// it, else 128 x 256 / 128 x 128; always inside one image.
 static bool mc_tile(const mcgen_conv_t* p, int* bm, int* bn) {
     const long M = (long)p->N * p->H * p->W;
     const int HW = p->H * p->W;
@@ -2411,102 +2398,34 @@ static bool mc_tile(const mcgen_conv_t* p, int* bm, int* bn) {
     return true;
 }
 
+// conv_mc_kernel (w_layout 1: two windows, compacted while staged) and conv_gk_kernel (w_layout 2) on the same three tiles
 template <int BM, int BN, int WM, int WN>
-static int launch_mc(const mcgen_conv_t* p, hipStream_t st) {
+static int size_kmajor(const mcgen_conv_t* p, bool mc, Sized* z) {
     using C = ConvCfg<bf16_t, BM, BN, WM, WN>;
-    const long Mtot = (long)p->N * p->H * p->W;
-    MCGEN_CHECK(Mtot % BM == 0 && p->H * p->W >= BM, "conv_fused(mc): tiles of %d pixels must lie inside one %dx%d image", BM, p->H, p->W);
-    MCGEN_CHECK(!p->ycmap || p->Cout_w <= BN, "conv_fused(mc): compacted output needs all channels in one tile");
-    const int mt = (int)(Mtot / BM);
-    const int nt = (p->Cout_w + BN - 1) / BN;
-    const int PP = patch_pixels(p, BM);
-    MCGEN_CHECK(PP * 4 <= C::NI * C::NT, "conv_fused(mc): patch of %d pixels exceeds the staging plan", PP);
-    const int a_bytes = round_up(PP * C::APITCH, 16);
-    int lds = 2 * a_bytes + 2 * 3 * 32 * BN * 2;
-    const int epi_bytes = C::PPX * C::EP * 4 + (p->ycmap ? YTAB_BYTES : 0), red_bytes = C::PROWS * BN * 2 * 4;
-    if (epi_bytes > lds) lds = epi_bytes;
-    if (red_bytes > lds) lds = red_bytes;
-    MCGEN_CHECK(lds <= 160 * 1024, "conv_fused(mc): tile %dx%d needs %d bytes of LDS", BM, BN, lds);
-    // window loads of the next dense chunk prefetched across the K step (tuning builds can switch it off)
+    const char* who = mc ? "conv_fused(mc)" : "conv_fused(gk)";
+    static int raised[2] = {0, 0};
+    *z = {mc ? sym(conv_mc_kernel<BM, BN, WM, WN, false>) : sym(conv_gk_kernel<BM, BN, WM, WN>), &raised[mc], who};
+#ifdef MCGEN_TUNING
+    // window loads of the next dense chunk prefetched across the K step: measured and lost, tuning builds can switch it on
     static const bool prefetch = env_long("MCGEN_MC_PREFETCH", 0) != 0;
-    static int raised = 0, raised0 = 0;
-    if (prefetch) {
-        auto kern = conv_mc_kernel<BM, BN, WM, WN, true>;
-        if (int rc = raise_lds(reinterpret_cast<const void*>(kern), lds, &raised)) return rc;
-        hipLaunchKernelGGL(kern, dim3(mt, nt), dim3(C::NT), lds, st, *p, a_bytes);
-    } else {
-        auto kern = conv_mc_kernel<BM, BN, WM, WN, false>;
-        if (int rc = raise_lds(reinterpret_cast<const void*>(kern), lds, &raised0)) return rc;
-        hipLaunchKernelGGL(kern, dim3(mt, nt), dim3(C::NT), lds, st, *p, a_bytes);
-    }
-    MCGEN_LAUNCH_CHECK("conv_fused(mc)");
-    return 0;
-}
-
-static int dispatch_mc(const mcgen_conv_t* p, int dtype, hipStream_t st) {
-    MCGEN_CHECK(dtype == MCGEN_BF16, "conv_fused: K-major (mode-compacted) launches are bf16");
-    for (int s = 0; s < p->nseg; ++s) {
-        MCGEN_CHECK(p->seg[s].cmap && p->seg[s].cmap_stride >= 2 * p->seg[s].C + 32, "conv_fused: K-major launch: segment %d has no compaction map", s);
-        MCGEN_CHECK(p->seg[s].C <= 2048, "conv_fused(mc): at most 2048 channels per segment");
-    }
-    MCGEN_CHECK(p->Cout_w % 8 == 0 && p->Cout_w >= 64, "conv_fused(mc): at least 64 output channels");
-    int bm = 0, bn = 0;
-    MCGEN_CHECK(mc_tile(p, &bm, &bn), "conv_fused(mc): no tile of a %dx%d map lies inside one image", p->H, p->W);
-    if (bm == 256 && bn == 256) return launch_mc<256, 256, 2, 4>(p, st);
-    if (bm == 128 && bn == 256) return launch_mc<128, 256, 2, 4>(p, st);
-    return launch_mc<128, 128, 2, 2>(p, st);
-}
-
-template <int BM, int BN, int WM, int WN, int R, bool GK> static bool pp_fits_(const mcgen_conv_t* p);
-template <typename T, int BM, int BN, int WM, int WN, int R, bool GK> static int launch_pp(const mcgen_conv_t* p, hipStream_t st);
-
-template <int BM, int BN, int WM, int WN>
-static int launch_gk(const mcgen_conv_t* p, hipStream_t st) {
-    using C = ConvCfg<bf16_t, BM, BN, WM, WN>;
+    static int raised_pf = 0;
+    if (mc && prefetch) *z = {sym(conv_mc_kernel<BM, BN, WM, WN, true>), &raised_pf, who};
+#endif
     const long Mtot = (long)p->N * p->H * p->W;
-    MCGEN_CHECK(Mtot % BM == 0 && p->H * p->W >= BM, "conv_fused(gk): tiles of %d pixels must lie inside one %dx%d image", BM, p->H, p->W);
-    MCGEN_CHECK(!p->ycmap || p->Cout_w <= BN, "conv_fused(gk): compacted output needs all channels in one tile");
-    const int mt = (int)(Mtot / BM);
-    const int nt = (p->Cout_w + BN - 1) / BN;
+    MCGEN_CHECK(Mtot % BM == 0 && p->H * p->W >= BM, "%s: tiles of %d pixels must lie inside one %dx%d image", who, BM, p->H, p->W);
+    MCGEN_CHECK(!p->ycmap || p->Cout_w <= BN, "%s: compacted output needs all channels in one tile", who);
     const int PP = patch_pixels(p, BM);
-    MCGEN_CHECK(PP * 4 <= C::NI * C::NT, "conv_fused(gk): patch of %d pixels exceeds the staging plan", PP);
-    const int a_bytes = round_up(PP * C::APITCH, 1024);
-    int lds = a_bytes + 2 * 3 * 32 * BN * 2;
-    const int epi_bytes = C::PPX * C::EP * 4 + (p->ycmap ? YTAB_BYTES : 0), red_bytes = C::PROWS * BN * 2 * 4;
-    if (epi_bytes > lds) lds = epi_bytes;
-    if (red_bytes > lds) lds = red_bytes;
-    MCGEN_CHECK(lds <= 160 * 1024, "conv_fused(gk): tile %dx%d needs %d bytes of LDS", BM, BN, lds);
-    auto kern = conv_gk_kernel<BM, BN, WM, WN>;
-    static int raised = 0;
-    if (int rc = raise_lds(reinterpret_cast<const void*>(kern), lds, &raised)) return rc;
-    hipLaunchKernelGGL(kern, dim3(mt, nt), dim3(C::NT), lds, st, *p, a_bytes);
-    MCGEN_LAUNCH_CHECK("conv_fused(gk)");
-    return 0;
-}
-
-static int dispatch_gk(const mcgen_conv_t* p, int dtype, hipStream_t st) {
-    MCGEN_CHECK(dtype == MCGEN_BF16, "conv_fused: K-major launches are bf16");
-    for (int s = 0; s < p->nseg; ++s) {
-        const mcgen_seg_t& g = p->seg[s];
-        const int cw = g.Cw > 0 ? g.Cw : g.C;
-        MCGEN_CHECK(cw % 8 == 0 && cw <= 2048 && g.C <= cw + 32, "conv_fused(gk): segment %d: bad channel counts C=%d Cw=%d", s, g.C, cw);
-        MCGEN_CHECK(g.cmap || g.C == cw, "conv_fused(gk): segment %d: compacted channels need the map that orders them", s);
-        MCGEN_CHECK(!g.cmap || g.cmap_stride >= 2 * cw + 32, "conv_fused(gk): segment %d: map stride too small", s);
-        MCGEN_CHECK(!g.cmap || g.code == nullptr, "conv_fused(gk): segment %d: the code of a compacted segment rides in its scale / shift rows", s);
-    }
-    MCGEN_CHECK(p->Cout_w % 8 == 0 && p->Cout_w >= 64, "conv_fused(gk): at least 64 output channels");
-    int bm = 0, bn = 0;
-    MCGEN_CHECK(mc_tile(p, &bm, &bn), "conv_fused(gk): no tile of a %dx%d map lies inside one image", p->H, p->W);
-    // the big tile's 3x3 launches with a mapped first segment: the software-pipelined form (tuning builds: MCGEN_PP bit 2 off)
-    static const long pp_mode = env_long("MCGEN_PP", 7);
-    if (bm == 256 && bn == 256 && (pp_mode & 4) && pp_fits_<256, 256, 2, 4, 5, true>(p)) return launch_pp<bf16_t, 256, 256, 2, 4, 5, true>(p, st);
-    if (bm == 256 && bn == 256) return launch_gk<256, 256, 2, 4>(p, st);
-    if (bm == 128 && bn == 256) return launch_gk<128, 256, 2, 4>(p, st);
-    return launch_gk<128, 128, 2, 2>(p, st);
+    z->a_bytes = round_up(PP * C::APITCH, mc ? 16 : 1024);
+    return size_tile<C, BM, BN>(p, who, PP, (mc ? 2 : 1) * z->a_bytes + 2 * 3 * 32 * BN * 2, 0, z);
 }
 
 // "pp" form (conv_pp_kernel): 3x3 first segment with whole 32-channel chunks, further segments 1x1, tile inside one image,
 // window of two or three items per thread, two windows + ring + table within the CU's LDS.
+template <typename C, int R>
+static int pp_main_bytes(const mcgen_conv_t* p, int PP, int* a_bytes) {
+    *a_bytes = round_up(PP * C::APITCH, 1024);
+    return 2 * *a_bytes + R * C::BBYTES + p->seg[0].C * 8 + 16;
+}
 template <int BM, int BN, int WM, int WN, int R, bool GK>
 static bool pp_fits_(const mcgen_conv_t* p) {
     using C = ConvCfg<bf16_t, BM, BN, WM, WN>;
@@ -2516,55 +2435,36 @@ static bool pp_fits_(const mcgen_conv_t* p) {
     for (int s = 1; s < p->nseg; ++s) if (p->seg[s].ksize != 1 || (!GK && p->seg[s].cmap)) return false;
     const int PP = mcgen_patch_pixels(BM, p->H, p->W, 3);
     if (PP * 4 > PP_NIW_MAX * C::NT || PP * 4 <= C::NT) return false;
-    const int a_bytes = round_up(PP * C::APITCH, 1024);
-    const int lds = 2 * a_bytes + R * C::BBYTES + p->seg[0].C * 8 + 16;
-    return lds <= 160 * 1024;
+    int a_bytes = 0;
+    return pp_main_bytes<C, R>(p, PP, &a_bytes) <= 160 * 1024;
 }
 template <int BM, int BN, int WM, int WN, int R>
 static bool pp_fits(const mcgen_conv_t* p) { return pp_fits_<BM, BN, WM, WN, R, false>(p); }
 template <typename T, int BM, int BN, int WM, int WN, int R, bool GK>
-static int launch_pp(const mcgen_conv_t* p, hipStream_t st) {
+static int size_pp(const mcgen_conv_t* p, Sized* z) {
     static_assert(sizeof(T) == 2, "the pp form is bf16");
     using C = ConvCfg<bf16_t, BM, BN, WM, WN>;
-    const long Mtot = (long)p->N * p->H * p->W;
-    const int mt = (int)(Mtot / BM);
-    const int nt = (p->Cout_w + BN - 1) / BN;
-    const int PP = mcgen_patch_pixels(BM, p->H, p->W, 3);
-    const int a_bytes = round_up(PP * C::APITCH, 1024);
-    int lds = 2 * a_bytes + R * C::BBYTES + p->seg[0].C * 8 + 16;
-    const int epi_bytes = C::PPX * C::EP * 4 + (p->ycmap ? YTAB_BYTES : 0), red_bytes = C::PROWS * BN * 2 * 4;
-    const int epi_fast = (BM / PP_EPI_PASSES(BM, BN)) * C::EP * 4 + (p->ycmap ? YTAB_BYTES : 0);      // the merged passes of the fast epilogue
-    if (epi_bytes > lds) lds = epi_bytes;
-    if (epi_fast > lds) lds = epi_fast;
-    if (red_bytes > lds) lds = red_bytes;
-    MCGEN_CHECK(lds <= 160 * 1024, "conv_fused(pp): tile %dx%d needs %d bytes of LDS", BM, BN, lds);
     void (*kern)(const mcgen_conv_t, const int) = p->W == 32 ? conv_pp_kernel<BM, BN, WM, WN, R, 5, GK> : conv_pp_kernel<BM, BN, WM, WN, R, 4, GK>;
+    static int raised[2] = {0, 0};
+    int* r = &raised[p->W == 32];
 #ifdef MCGEN_TUNING
     static const long abl = env_long("MCGEN_PP_ABL", 0);
     if (abl == 2 && p->W == 32) kern = conv_pp_kernel<BM, BN, WM, WN, R, 5, GK, 2>;
+    r = nullptr;                // (LDS limit per kernel symbol; tuning builds switch symbols, so they set it on every launch)
 #endif
-    // (LDS limit per kernel symbol; tuning builds switch symbols, so they set it on every launch)
-#ifdef MCGEN_TUNING
-    int raised_now = 0;
-    if (int rc = raise_lds(reinterpret_cast<const void*>(kern), lds, &raised_now)) return rc;
-#else
-    static int raised[2] = {0, 0};
-    if (int rc = raise_lds(reinterpret_cast<const void*>(kern), lds, &raised[p->W == 32])) return rc;
-#endif
-    hipLaunchKernelGGL(kern, dim3(mt, nt), dim3(C::NT), lds, st, *p, a_bytes);
-    MCGEN_LAUNCH_CHECK("conv_fused(pp)");
-    return 0;
+    *z = {sym(kern), r, "conv_fused(pp)"};
+    const int main_bytes = pp_main_bytes<C, R>(p, mcgen_patch_pixels(BM, p->H, p->W, 3), &z->a_bytes);
+    return size_tile<C, BM, BN>(p, "conv_fused(pp)", 0, main_bytes, BM / PP_EPI_PASSES(BM, BN), z);      // (the merged passes of the fast epilogue)
 }
 
-typedef int (*launch_fn)(const mcgen_conv_t*, hipStream_t);
-struct CfgEntry { int BM, BN, pipe; launch_fn fn; };
+struct CfgEntry { int BM, BN, pipe; size_fn fn; };
 
 static const CfgEntry* f32_table(int* n) {
     using T = float;
     static const CfgEntry t[] = {
-        {128, 16, 0, launch_cfg<T, 128, 16, 4, 1>},
-        {64, 64, 0, launch_cfg<T, 64, 64, 2, 2>},
-        {128, 128, 0, launch_cfg<T, 128, 128, 2, 2>},
+        {128, 16, 0, size_cfg<T, 128, 16, 4, 1>},
+        {64, 64, 0, size_cfg<T, 64, 64, 2, 2>},
+        {128, 128, 0, size_cfg<T, 128, 128, 2, 2>},
     };
     *n = (int)(sizeof(t) / sizeof(t[0]));
     return t;
@@ -2574,38 +2474,70 @@ static const CfgEntry* f32_table(int* n) {
 static const CfgEntry* bf16_table(int* n) {
     using T = bf16_t;
     static const CfgEntry t[] = {
-        {256, 256, 5, launch_dma<T, 256, 256, 2, 4>}, {128, 256, 5, launch_dma<T, 128, 256, 2, 4>},
-        {128, 128, 5, launch_dma<T, 128, 128, 2, 2>}, {64, 128, 5, launch_dma<T, 64, 128, 2, 2>},
-        {64, 64, 11, launch_dma<T, 64, 64, 4, 2>},    {256, 16, 5, launch_dma<T, 256, 16, 8, 1>},
-        {64, 16, 12, launch_cp<T, 64, 16, 4, 1>},     {128, 16, 12, launch_cp<T, 128, 16, 4, 1>},
-        {256, 256, 20, launch_pp<T, 256, 256, 2, 4, 5, false>}, {256, 128, 20, launch_pp<T, 256, 128, MCGEN_PP128_WM, 8 / MCGEN_PP128_WM, 5, false>},
-        {128, 256, 20, launch_pp<T, 128, 256, 2, 4, 5, false>},
-        {128, 64, 5, launch_dma<T, 128, 64, 2, 2>},
+        {256, 256, 5, size_dma<T, 256, 256, 2, 4>}, {128, 256, 5, size_dma<T, 128, 256, 2, 4>},
+        {128, 128, 5, size_dma<T, 128, 128, 2, 2>}, {64, 128, 5, size_dma<T, 64, 128, 2, 2>},
+        {64, 64, 11, size_dma<T, 64, 64, 4, 2>},    {256, 16, 5, size_dma<T, 256, 16, 8, 1>},
+        {64, 16, 12, size_cp<T, 64, 16, 4, 1>},     {128, 16, 12, size_cp<T, 128, 16, 4, 1>},
+        {256, 256, 20, size_pp<T, 256, 256, 2, 4, 5, false>}, {256, 128, 20, size_pp<T, 256, 128, MCGEN_PP128_WM, 8 / MCGEN_PP128_WM, 5, false>},
+        {128, 256, 20, size_pp<T, 128, 256, 2, 4, 5, false>},
+        {128, 64, 5, size_dma<T, 128, 64, 2, 2>},
 #ifdef MCGEN_TUNING
-        {128, 256, 4, launch_dma1<T, 128, 256, 1, 4>}, {128, 256, 14, launch_dma1<T, 128, 256, 2, 4>},
-        {256, 128, 15, launch_dma<T, 256, 128, 4, 1>}, {256, 128, 16, launch_dma<T, 256, 128, 2, 2>},
-        {64, 128, 4, launch_dma1<T, 64, 128, 1, 4>},   {128, 128, 4, launch_dma1<T, 128, 128, 1, 4>},
-        {256, 128, 5, launch_dma<T, 256, 128, 4, 2>}, {64, 64, 5, launch_dma<T, 64, 64, 2, 2>},
-        {128, 16, 5, launch_dma<T, 128, 16, 4, 1>},   {64, 16, 5, launch_dma<T, 64, 16, 4, 1>},
-        {64, 64, 12, launch_cp<T, 64, 64, 2, 2>},     {32, 64, 12, launch_cp<T, 32, 64, 1, 2>},
-        {64, 128, 9, launch_dma<T, 64, 128, 4, 4>},   {64, 64, 9, launch_dma<T, 64, 64, 4, 4>},
-        {256, 64, 5, launch_dma<T, 256, 64, 4, 2>},   {128, 64, 15, launch_dma<T, 128, 64, 4, 2>},
-        {256, 64, 15, launch_dma<T, 256, 64, 2, 2>},  {128, 64, 16, launch_dma<T, 128, 64, 2, 1>},
+        {128, 256, 4, size_dma1<T, 128, 256, 1, 4>}, {128, 256, 14, size_dma1<T, 128, 256, 2, 4>},
+        {256, 128, 15, size_dma<T, 256, 128, 4, 1>}, {256, 128, 16, size_dma<T, 256, 128, 2, 2>},
+        {64, 128, 4, size_dma1<T, 64, 128, 1, 4>},   {128, 128, 4, size_dma1<T, 128, 128, 1, 4>},
+        {256, 128, 5, size_dma<T, 256, 128, 4, 2>}, {64, 64, 5, size_dma<T, 64, 64, 2, 2>},
+        {128, 16, 5, size_dma<T, 128, 16, 4, 1>},   {64, 16, 5, size_dma<T, 64, 16, 4, 1>},
+        {64, 64, 12, size_cp<T, 64, 64, 2, 2>},     {32, 64, 12, size_cp<T, 32, 64, 1, 2>},
+        {64, 128, 9, size_dma<T, 64, 128, 4, 4>},   {64, 64, 9, size_dma<T, 64, 64, 4, 4>},
+        {256, 64, 5, size_dma<T, 256, 64, 4, 2>},   {128, 64, 15, size_dma<T, 128, 64, 4, 2>},
+        {256, 64, 15, size_dma<T, 256, 64, 2, 2>},  {128, 64, 16, size_dma<T, 128, 64, 2, 1>},
 #endif
     };
     *n = (int)(sizeof(t) / sizeof(t[0]));
     return t;
 }
 
-static int dispatch(const mcgen_conv_t* p, int dtype, const TilePick& t, hipStream_t st) {
-    int n = 0;
-    const CfgEntry* tab = dtype == MCGEN_BF16 ? bf16_table(&n) : f32_table(&n);
-    for (int i = 0; i < n; ++i)
-        if (tab[i].BM == t.BM && tab[i].BN == t.BN && tab[i].pipe == t.pipe) return tab[i].fn(p, st);
-    return mcgen_fail("conv_fused: no instantiation for tile %dx%d pipe=%d dtype=%d", t.BM, t.BN, t.pipe, dtype);
-}
+// ---- the route: which launcher, on which tile -----------------------------------------------------------------------
+struct Route { int route; TilePick t; int m_tiles; };
 
-static int validate(const mcgen_conv_t* p) {
+// THE route decision of a fused convolution -- mcgen_conv_fused, mcgen_conv_plan and the three queries all read this one.
+// Reads the shape / mode fields only (never p->stats: callers size `stats` from m_tiles), and never refuses: what a
+// route does not accept is check_route's business.  `t` is the tile of the tiled forms (pick_tile) or of the K-major
+// ones (mc_tile; 0 x 0 when the map has none) whichever kernel runs: mcgen_conv_tile reports it.
+static Route pick_route(const mcgen_conv_t* p, int dtype) {
+    Route r = {MCGEN_ROUTE_TILED, {0, 0, 0}, 0};
+    if (p->w_layout == 0) r.t = pick_tile(p, dtype);
+    else if (!mc_tile(p, &r.t.BM, &r.t.BN)) r.t = {0, 0, 0};
+    int bm = r.t.BM;                                    // pixels per row of `stats`
+    if (p->y_group != 0) {
+        r.route = MCGEN_ROUTE_HEAD;                     // the paired output layout is the image head's
+    } else if (p->w_layout != 0) {
+        // the big tile's 3x3 launches with a mapped first segment: the software-pipelined form (tuning builds: MCGEN_PP bit 2 off)
+        static const long pp_mode = env_long("MCGEN_PP", 7);
+        const bool pp = p->w_layout == 2 && bm == 256 && r.t.BN == 256 && (pp_mode & 4) && pp_fits_<256, 256, 2, 4, 5, true>(p);
+        r.route = p->w_layout == 1 ? MCGEN_ROUTE_MC : pp ? MCGEN_ROUTE_GK_PP : MCGEN_ROUTE_GK;
+    } else if (p->wsel || p->order) {                   // per-mode weight sets: the image head, else the pp form of the table
+        if (p->wsel && mcgen_conv_head_ok(p, dtype)) r.route = MCGEN_ROUTE_HEAD;
+    } else if (mcgen_conv_skinny_ok(p, dtype)) {
+        r.route = MCGEN_ROUTE_SKINNY;
+    } else if (mcgen_conv_smap_ok(p, dtype)) {
+        r.route = MCGEN_ROUTE_SMAP;
+    } else if (const int px1 = mcgen_conv_px1_bm(p, dtype)) {
+        r.route = MCGEN_ROUTE_PX1;
+        bm = px1;
+    } else if (mcgen_conv_c8_ok(p, dtype)) {
+        r.route = MCGEN_ROUTE_C8;
+    } else if (mcgen_conv_head_ok(p, dtype)) {
+        r.route = MCGEN_ROUTE_HEAD;
+    }
+    // (skinny / c8 / head write no statistics: they keep the tiled answer; the whole-image kernel writes one row per image)
+    const long Mtot = (long)p->N * p->H * p->W;
+    r.m_tiles = r.route == MCGEN_ROUTE_SMAP ? p->N : bm > 0 ? (int)((Mtot + bm - 1) / bm) : 0;
+    return r;
+}
+static int route_form(const Route& r) { return r.route >= MCGEN_ROUTE_SKINNY ? r.route - MCGEN_ROUTE_SKINNY + 1 : 0; }
+
+static int validate(const mcgen_conv_t* p, bool launching) {
     MCGEN_CHECK(p && p->nseg >= 1 && p->nseg <= 2, "conv_fused: nseg must be 1 or 2");
     MCGEN_CHECK(p->N > 0 && ilog2_exact(p->H) >= 0 && ilog2_exact(p->W) >= 0, "conv_fused: H and W must be powers of two (got %dx%d)", p->H, p->W);
     MCGEN_CHECK(p->W <= 64 && p->H * p->W >= 1, "conv_fused: W up to 64 supported");
@@ -2622,7 +2554,8 @@ static int validate(const mcgen_conv_t* p) {
     if (p->pool) MCGEN_CHECK(p->H >= 2 && p->W >= 2, "conv_fused: pooling needs H, W >= 2");
     MCGEN_CHECK(p->stats_mode >= 0 && p->stats_mode <= 2, "conv_fused: bad stats_mode");
     MCGEN_CHECK(p->stats_mode != 2 || (p->gate_x && p->gmean && p->grstd), "conv_fused: stats_mode 2 needs gate_x, gmean, grstd");
-    MCGEN_CHECK(p->stats_mode == 0 || p->stats, "conv_fused: stats_mode set without a stats buffer");
+    // (the plan is asked before `stats` exists: its height is what the caller wants to know)
+    MCGEN_CHECK(!launching || p->stats_mode == 0 || p->stats, "conv_fused: stats_mode set without a stats buffer");
     MCGEN_CHECK(p->w_layout >= 0 && p->w_layout <= 2, "conv_fused: unknown weight layout %d", p->w_layout);
     if (p->wsel || p->order) {
         MCGEN_CHECK(p->w_layout == 0 && (p->y_group == 0 || !p->order), "conv_fused: per-mode weight sets (wsel / order) go with the chunked weight image (w_layout 0)");
@@ -2645,69 +2578,51 @@ static int validate(const mcgen_conv_t* p) {
     return 0;
 }
 
-}  // namespace
-
-extern "C" int mcgen_conv_m_tiles(const mcgen_conv_t* p, int dtype) {
-    if (!p) return 0;
-    if (p->w_layout != 0) {
-        int bm = 0, bn = 0;
-        if (!mc_tile(p, &bm, &bn)) return 0;
-        return (int)(((long)p->N * p->H * p->W + bm - 1) / bm);
+static int check_mc(const mcgen_conv_t* p, int dtype, const TilePick& t) {
+    MCGEN_CHECK(dtype == MCGEN_BF16, "conv_fused: K-major (mode-compacted) launches are bf16");
+    for (int s = 0; s < p->nseg; ++s) {
+        MCGEN_CHECK(p->seg[s].cmap && p->seg[s].cmap_stride >= 2 * p->seg[s].C + 32, "conv_fused: K-major launch: segment %d has no compaction map", s);
+        MCGEN_CHECK(p->seg[s].C <= 2048, "conv_fused(mc): at most 2048 channels per segment");
     }
-    if (mcgen_conv_smap_ok(p, dtype)) return p->N;              // whole-image kernel: one statistics row per image
-    if (const int bm = mcgen_conv_px1_bm(p, dtype)) return (int)((long)p->N * p->H * p->W / bm);
-    const TilePick t = pick_tile(p, dtype);
-    const long Mtot = (long)p->N * p->H * p->W;
-    return (int)((Mtot + t.BM - 1) / t.BM);
-}
-
-extern "C" int mcgen_conv_tile(const mcgen_conv_t* p, int dtype, int* bm, int* bn) {
-    if (!p || !bm || !bn) return mcgen_fail("conv_tile: null pointer");
-    if (p->w_layout != 0) {
-        MCGEN_CHECK(mc_tile(p, bm, bn), "conv_tile: no K-major tile for a %dx%d map", p->H, p->W);
-        return 0;
-    }
-    const TilePick t = pick_tile(p, dtype);
-    *bm = t.BM; *bn = t.BN;
+    MCGEN_CHECK(p->Cout_w % 8 == 0 && p->Cout_w >= 64, "conv_fused(mc): at least 64 output channels");
+    MCGEN_CHECK(t.BM > 0, "conv_fused(mc): no tile of a %dx%d map lies inside one image", p->H, p->W);
     return 0;
 }
 
-extern "C" int mcgen_conv_form(const mcgen_conv_t* p, int dtype) {
-    if (!p || p->w_layout != 0 || p->order) return 0;
-    if (p->wsel) return mcgen_conv_head_ok(p, dtype) ? 5 : 0;
-    if (mcgen_conv_skinny_ok(p, dtype)) return 1;
-    if (mcgen_conv_smap_ok(p, dtype)) return 2;
-    if (mcgen_conv_px1_bm(p, dtype)) return 3;
-    if (mcgen_conv_c8_ok(p, dtype)) return 4;
-    if (mcgen_conv_head_ok(p, dtype)) return 5;
+static int check_gk(const mcgen_conv_t* p, int dtype, const TilePick& t) {
+    MCGEN_CHECK(dtype == MCGEN_BF16, "conv_fused: K-major launches are bf16");
+    for (int s = 0; s < p->nseg; ++s) {
+        const mcgen_seg_t& g = p->seg[s];
+        const int cw = g.Cw > 0 ? g.Cw : g.C;
+        MCGEN_CHECK(cw % 8 == 0 && cw <= 2048 && g.C <= cw + 32, "conv_fused(gk): segment %d: bad channel counts C=%d Cw=%d", s, g.C, cw);
+        MCGEN_CHECK(g.cmap || g.C == cw, "conv_fused(gk): segment %d: compacted channels need the map that orders them", s);
+        MCGEN_CHECK(!g.cmap || g.cmap_stride >= 2 * cw + 32, "conv_fused(gk): segment %d: map stride too small", s);
+        MCGEN_CHECK(!g.cmap || g.code == nullptr, "conv_fused(gk): segment %d: the code of a compacted segment rides in its scale / shift rows", s);
+    }
+    MCGEN_CHECK(p->Cout_w % 8 == 0 && p->Cout_w >= 64, "conv_fused(gk): at least 64 output channels");
+    MCGEN_CHECK(t.BM > 0, "conv_fused(gk): no tile of a %dx%d map lies inside one image", p->H, p->W);
     return 0;
 }
 
-extern "C" int mcgen_conv_fused(const mcgen_conv_t* p, int dtype, void* stream) {
-    if (int rc = validate(p)) return rc;
+// what the route pick_route chose does not accept (p has passed validate)
+static int check_route(const mcgen_conv_t* p, int dtype, const Route& r) {
+    const TilePick& t = r.t;
     if (p->y_group != 0) {
         MCGEN_CHECK(mcgen_conv_head_ok(p, dtype), "conv_fused: the paired output layout (y_group) is built for the image head only "
                     "(bf16, one 3x3 segment to <= 8 channels of pitch 8 on 32x32 maps, N %% y_group == 0)");
-        return mcgen_conv_head(p, reinterpret_cast<hipStream_t>(stream));
+        return 0;
     }
-    if (p->w_layout == 1) return dispatch_mc(p, dtype, reinterpret_cast<hipStream_t>(stream));
-    if (p->w_layout == 2) return dispatch_gk(p, dtype, reinterpret_cast<hipStream_t>(stream));
+    if (p->w_layout == 1) return check_mc(p, dtype, t);
+    if (p->w_layout == 2) return check_gk(p, dtype, t);
     for (int s = 0; s < p->nseg; ++s) MCGEN_CHECK(p->seg[s].cmap == nullptr, "conv_fused: a compaction map needs a K-major launch (w_layout 1 or 2)");
-    if (p->wsel && mcgen_conv_head_ok(p, dtype)) return mcgen_conv_head(p, reinterpret_cast<hipStream_t>(stream));
+    if (r.route != MCGEN_ROUTE_TILED) return 0;
     if (p->wsel || p->order) {
-        const TilePick tw = pick_tile(p, dtype);
-        MCGEN_CHECK(dtype == MCGEN_BF16 && tw.pipe == 20, "conv_fused: per-mode weight sets need the software-pipelined bf16 form "
+        MCGEN_CHECK(dtype == MCGEN_BF16 && t.pipe == 20, "conv_fused: per-mode weight sets need the software-pipelined bf16 form "
                     "(3x3 first segment of 64 .. 512 channels in whole chunks, 16x16 / 32x32 maps, >= 65536 pixels)");
-        if (p->ycmap) MCGEN_CHECK(tw.BM <= p->H * p->W && p->Cout_w <= tw.BN, "conv_fused: compacted output: the %dx%d tile must hold all %d channels", tw.BM, tw.BN, p->Cout_w);
-        if (p->yperm) MCGEN_CHECK(tw.BM <= p->H * p->W && p->Cout_w == tw.BN, "conv_fused: yperm: the %dx%d tile must hold exactly the %d channels", tw.BM, tw.BN, p->Cout_w);
-        return dispatch(p, dtype, tw, reinterpret_cast<hipStream_t>(stream));
+        if (p->ycmap) MCGEN_CHECK(t.BM <= p->H * p->W && p->Cout_w <= t.BN, "conv_fused: compacted output: the %dx%d tile must hold all %d channels", t.BM, t.BN, p->Cout_w);
+        if (p->yperm) MCGEN_CHECK(t.BM <= p->H * p->W && p->Cout_w == t.BN, "conv_fused: yperm: the %dx%d tile must hold exactly the %d channels", t.BM, t.BN, p->Cout_w);
+        return 0;
     }
-    if (mcgen_conv_skinny_ok(p, dtype)) return mcgen_conv_skinny(p, reinterpret_cast<hipStream_t>(stream));
-    if (mcgen_conv_smap_ok(p, dtype)) return mcgen_conv_smap(p, reinterpret_cast<hipStream_t>(stream));
-    if (mcgen_conv_px1_bm(p, dtype)) return mcgen_conv_px1(p, reinterpret_cast<hipStream_t>(stream));
-    if (mcgen_conv_c8_ok(p, dtype)) return mcgen_conv_c8(p, reinterpret_cast<hipStream_t>(stream));
-    if (mcgen_conv_head_ok(p, dtype)) return mcgen_conv_head(p, reinterpret_cast<hipStream_t>(stream));
-    const TilePick t = pick_tile(p, dtype);
     if (p->ycmap) MCGEN_CHECK(dtype == MCGEN_BF16 && t.BM <= p->H * p->W && p->Cout_w <= t.BN,
                               "conv_fused: compacted output: the %dx%d tile must lie inside one image and hold all %d channels", t.BM, t.BN, p->Cout_w);
     // pooling / whole-row tiles need at least two rows per tile
@@ -2717,8 +2632,75 @@ extern "C" int mcgen_conv_fused(const mcgen_conv_t* p, int dtype, void* stream) 
         MCGEN_CHECK(p->seg[s].group_n == 0 || p->seg[s].group_n % ti == 0,
                     "conv_fused: a tile of %d images would straddle BatchNorm groups of %d images", ti, p->seg[s].group_n);
     }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (dtype != MCGEN_F32 && dtype != MCGEN_BF16) return mcgen_fail("conv_fused: unknown dtype %d", dtype);
-    return dispatch(p, dtype, t, st);
+    return 0;
+}
+
+// sizes the launch of a route inside this file
+static int size_route(const mcgen_conv_t* p, int dtype, const Route& r, Sized* z) {
+    const TilePick& t = r.t;
+    if (r.route == MCGEN_ROUTE_GK_PP) return size_pp<bf16_t, 256, 256, 2, 4, 5, true>(p, z);
+    if (r.route == MCGEN_ROUTE_MC || r.route == MCGEN_ROUTE_GK) {
+        const bool mc = r.route == MCGEN_ROUTE_MC;
+        if (t.BM == 256 && t.BN == 256) return size_kmajor<256, 256, 2, 4>(p, mc, z);
+        if (t.BM == 128 && t.BN == 256) return size_kmajor<128, 256, 2, 4>(p, mc, z);
+        return size_kmajor<128, 128, 2, 2>(p, mc, z);
+    }
+    int n = 0;
+    const CfgEntry* tab = dtype == MCGEN_BF16 ? bf16_table(&n) : f32_table(&n);
+    for (int i = 0; i < n; ++i)
+        if (tab[i].BM == t.BM && tab[i].BN == t.BN && tab[i].pipe == t.pipe) return tab[i].fn(p, z);
+    return mcgen_fail("conv_fused: no instantiation for tile %dx%d pipe=%d dtype=%d", t.BM, t.BN, t.pipe, dtype);
+}
+
+// validate, route, size: everything mcgen_conv_fused decides before it touches HIP (`z` stays zero for the five kernels in
+// files of their own, which size themselves)
+static int make_plan(const mcgen_conv_t* p, int dtype, bool launching, Route* r, Sized* z) {
+    if (int rc = validate(p, launching)) return rc;
+    *r = pick_route(p, dtype);
+    *z = {};
+    if (int rc = check_route(p, dtype, *r)) return rc;
+    return r->route < MCGEN_ROUTE_SKINNY ? size_route(p, dtype, *r, z) : 0;
+}
+
+}  // namespace
+
+extern "C" int mcgen_conv_plan(const mcgen_conv_t* p, int dtype, mcgen_conv_plan_t* out) {
+    MCGEN_CHECK(out, "conv_plan: null pointer");
+    *out = {};
+    Route r;
+    Sized z;
+    if (int rc = make_plan(p, dtype, false, &r, &z)) return rc;
+    const bool here = r.route < MCGEN_ROUTE_SKINNY;
+    *out = {r.route, route_form(r), here ? r.t.BM : 0, here ? r.t.BN : 0, here ? r.t.pipe : 0, r.m_tiles,
+            z.grid_x, z.grid_y, z.threads, z.lds, z.a_bytes, z.grouped};
+    return 0;
+}
+
+extern "C" int mcgen_conv_m_tiles(const mcgen_conv_t* p, int dtype) { return p ? pick_route(p, dtype).m_tiles : 0; }
+
+extern "C" int mcgen_conv_tile(const mcgen_conv_t* p, int dtype, int* bm, int* bn) {
+    if (!p || !bm || !bn) return mcgen_fail("conv_tile: null pointer");
+    const Route r = pick_route(p, dtype);
+    MCGEN_CHECK(r.t.BM > 0, "conv_tile: no K-major tile for a %dx%d map", p->H, p->W);
+    *bm = r.t.BM; *bn = r.t.BN;
+    return 0;
+}
+
+extern "C" int mcgen_conv_form(const mcgen_conv_t* p, int dtype) { return p ? route_form(pick_route(p, dtype)) : 0; }
+
+extern "C" int mcgen_conv_fused(const mcgen_conv_t* p, int dtype, void* stream) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    Route r;
+    Sized z;
+    if (int rc = make_plan(p, dtype, true, &r, &z)) return rc;
+    switch (r.route) {
+        case MCGEN_ROUTE_SKINNY: return mcgen_conv_skinny(p, st);
+        case MCGEN_ROUTE_SMAP: return mcgen_conv_smap(p, st);
+        case MCGEN_ROUTE_PX1: return mcgen_conv_px1(p, st);
+        case MCGEN_ROUTE_C8: return mcgen_conv_c8(p, st);
+        case MCGEN_ROUTE_HEAD: return mcgen_conv_head(p, st);
+    }
+    return launch_sized(z, p, st);
 }
 #endif  // MCGEN_KERNELS_ONLY

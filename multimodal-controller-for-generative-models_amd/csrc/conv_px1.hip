@@ -214,7 +214,8 @@ static int p1_pxf(const mcgen_conv_t* p, int dtype) {
     const mcgen_seg_t& g = p->seg[0];
     if (g.ksize != 1 || g.ups || g.group_n || g.cmap || g.C != P1_K) return 0;
     if (p->Cout != 512 || p->Cout_w != 512 || p->Cy != 512 || p->pool || p->tanh_out || p->ycmap) return 0;
-    // (no test of p->stats here: mcgen_conv_m_tiles asks before the caller has allocated it; mcgen_conv_fused validates it)
+    // (no test of p->stats here: pick_route in conv_fused.hip -- the one place that orders the kernels -- is asked, through
+    // mcgen_conv_plan, before the caller has allocated it; mcgen_conv_fused validates it)
     if (p->stats_mode == 2 && !(p->gate_x && p->gmean && p->grstd)) return 0;
     const int hw = p->H * p->W;
     return hw == 256 ? 8 : hw == 64 ? 2 : hw == 16 ? 1 : 0;

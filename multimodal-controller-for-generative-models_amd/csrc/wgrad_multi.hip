@@ -285,48 +285,18 @@ static __device__ __forceinline__ void wgrad_big_body(const mcgen_wgrad_t& p, co
         __syncthreads();                                                   // the affine rows and step 0's code row(s) are in LDS
         write_x(0);
         if (cnt > 1) load_x(1);
-#ifdef WB_LATE
-        // Waves 4-7 (the second wave of every SIMD) multiply FIRST and stage step i + 1 behind their MFMAs, while their SIMD
-        // partner stages first: one wave's prologue VALU under the other's matrix work.  Their window loads of step i + 2 then
-        // leave at the END of step i and have the whole multiply phase of step i + 1 to land (they are waited for in front of
-        // the late write_x, not at the barrier); only the dy DMA -- which everyone reads behind the next barrier -- goes out early.
-        // (Not for steps of more than four images: there waves 4-7 carry code-row DMAs that the early waves read.)
-        const bool late = (wa != 0) && TI <= 4;
-#endif
         for (int i = 0; i < cnt; ++i) {
-#ifdef WB_LATE
-            if (late) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NIX) : "memory");   // (this wave's x loads of step i + 1 stay in flight)
-            else
-#endif
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // dy of step i has landed (and this thread's x of step i + 1)
             __syncthreads();                                               // step i published; the buffers of step i - 1 are free
-            // Staging of step i + 1 (window prologue + LDS stores, dy DMA, register loads of step i + 2).  Waves 4-7 (the second
-            // wave of every SIMD) run it in the MIDDLE of the step's multiply loop instead of in front of it: all eight waves
-            // leave the barrier together, and with the same program they would all spend the next ~1 us in the prologue's VALU
-            // work with the matrix pipe idle -- now one wave of each SIMD multiplies while its partner stages (any point of the
-            // step is legal: the buffers of step i + 1 were last read before the barrier, and are next read behind the next one).
-            auto stage_next = [&]() {
-                if (i + 1 < cnt) {
-#ifndef WB_ABL_NO_XWRITE
-                    write_x(i + 1);
-#endif
-#ifndef WB_ABL_NO_DMA
-                    dma_dy(i + 1);
-#endif
-#ifndef WB_ABL_NO_XLOAD
-                    if (i + 2 < cnt) load_x(i + 2);
-#endif
-                }
-            };
-#if defined(WB_STAGGER)
-            const bool late = wa != 0;
-#elif !defined(WB_LATE)
-            const bool late = false;
-#endif
-            if (!late) stage_next();
-#ifdef WB_LATE
-            else if (i + 1 < cnt) dma_dy(i + 1);
-#endif
+            // Staging of step i + 1 (window prologue + LDS stores, dy DMA, register loads of step i + 2): every wave runs it right
+            // behind the barrier, in front of the step's multiply loop.  (Any point of the step is legal: the buffers of step
+            // i + 1 were last read before the barrier, and are next read behind the next one.  Splitting the waves of a SIMD into
+            // one that stages first and one that multiplies first was measured and lost: DESIGN.md 4.6.4.)
+            if (i + 1 < cnt) {
+                write_x(i + 1);
+                dma_dy(i + 1);
+                if (i + 2 < cnt) load_x(i + 2);
+            }
             __builtin_amdgcn_sched_barrier(0);                             // (the staging block's temporaries die before the fragments come alive)
             const char* A = ldsA + (i & 1) * WB_ABUF + aoff;
             const char* D = ldsD + (i & 1) * WB_DBUF;
@@ -347,19 +317,11 @@ static __device__ __forceinline__ void wgrad_big_body(const mcgen_wgrad_t& p, co
             auto rd_a = [&](int ks, int j) {
                 const int g0 = (G::winpos(32 * ks) - HALO0) * WB_XPITCH, g1 = (G::winpos(32 * ks + 16) - HALO0) * WB_XPITCH;
                 const int tap = ((j / KS) * PC + (j % KS)) * WB_XPITCH;
-#ifdef WB_ABL_NO_FRAG
-                bf16x8 z; for (int e = 0; e < 8; ++e) z[e] = (bf16_t)(float)(lane + ks + j);
-                asm volatile("" : "+v"(z));
-                return z;
-#else
                 return wb_frag(A + g0 + tap, A + g1 + tap);
-#endif
             };
             // (two named buffers picked by the compile-time parity of the tap counter: a rotating `next -> current` copy costs
             // four v_mov per tap -- measured 3.1 VALU per MFMA with it)
-#ifndef WB_DEPTH
-#define WB_DEPTH 1
-#endif
+            constexpr int WB_DEPTH = 1;                                    // window fragments read ahead of their MFMAs
             constexpr int NTT = (WB_BM / 32) * NTAP;                       // taps per step, in loop order
             auto rd_t = [&](int t) { return rd_a(t / NTAP, t % NTAP); };
             bf16x8 afb[WB_DEPTH + 1];
@@ -367,15 +329,6 @@ static __device__ __forceinline__ void wgrad_big_body(const mcgen_wgrad_t& p, co
             for (int t = 0; t < WB_DEPTH && t < NTT; ++t) afb[t] = rd_t(t);
 #pragma unroll
             for (int ks = 0; ks < WB_BM / 32; ++ks) {
-#ifdef WB_STAGGER
-                if (ks == WB_STAGGER) {
-                    if (late) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        stage_next();
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-#endif
                 bf16x8 df[4];
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
@@ -384,25 +337,11 @@ static __device__ __forceinline__ void wgrad_big_body(const mcgen_wgrad_t& p, co
                 for (int j = 0; j < NTAP; ++j) {
                     const int t = ks * NTAP + j;                           // compile-time: the loops are fully unrolled
                     if (t + WB_DEPTH < NTT) afb[(t + WB_DEPTH) % (WB_DEPTH + 1)] = rd_t(t + WB_DEPTH);
-#ifdef WB_ABL_NO_MFMA
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) asm volatile("" :: "v"(df[c]), "v"(afb[t % (WB_DEPTH + 1)]));
-#else
 #pragma unroll
                     for (int c = 0; c < 4; ++c) acc[j][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df[c], afb[t % (WB_DEPTH + 1)], acc[j][c], 0, 0, 0);
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-#ifdef WB_LATE
-            if (late && i + 1 < cnt) {
-                __builtin_amdgcn_sched_barrier(0);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // x of step i + 1 (loaded a step ago) and this step's dy DMA
-                write_x(i + 1);
-                if (i + 2 < cnt) load_x(i + 2);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#endif
         }
         // ---- slab[z][chunk][tap][co][32]: lane holds D[co = 4 lg + r][ci = l15] of (tap j, co fragment c)
         const int nchunk = (sg.C + MCGEN_CK - 1) / MCGEN_CK;
@@ -558,9 +497,6 @@ static __device__ __forceinline__ void wgrad_big_body(const mcgen_wgrad_t& p, co
 __global__ __launch_bounds__(WB_NT, 1)
 void wgrad_multi_kernel(const WgMulti a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef WB_CLOCK
-    const unsigned long long wbc0 = __builtin_amdgcn_s_memtime(), wbr0 = __builtin_amdgcn_s_memrealtime();
-#endif
     int l = 0;
 #pragma unroll
     for (int k = 1; k < MCGEN_WGRAD_MULTI_MAX; ++k) l += (k < a.n && (int)blockIdx.x >= a.first[k]) ? 1 : 0;
@@ -569,14 +505,11 @@ void wgrad_multi_kernel(const WgMulti a) {
     const int gx = p.Cout_w / WB_CO, gy = p.seg.C / WB_CI;
     const int bx = local % gx, by = (local / gx) % gy, bz = local / (gx * gy);
     const int lgw = 31 - __builtin_clz(p.W);
-#ifndef WB_M32
-#define WB_M32 0
-#endif
     if (p.seg.ksize == 3) {
         switch (lgw) {
-            case 5: wgrad_big_body<5, 5, 3, WB_M32 != 0>(p, bx, by, bz, p.splits, smem); break;
-            case 4: wgrad_big_body<4, 4, 3, WB_M32 != 0>(p, bx, by, bz, p.splits, smem); break;
-            default: wgrad_big_body<3, 3, 3, WB_M32 != 0>(p, bx, by, bz, p.splits, smem); break;
+            case 5: wgrad_big_body<5, 5, 3>(p, bx, by, bz, p.splits, smem); break;
+            case 4: wgrad_big_body<4, 4, 3>(p, bx, by, bz, p.splits, smem); break;
+            default: wgrad_big_body<3, 3, 3>(p, bx, by, bz, p.splits, smem); break;
         }
     } else {
         switch (lgw) {
@@ -586,13 +519,6 @@ void wgrad_multi_kernel(const WgMulti a) {
             default: wgrad_big_body<2, 2, 1>(p, bx, by, bz, p.splits, smem); break;
         }
     }
-#ifdef WB_CLOCK
-    // diagnostic build only: shader clock of this workgroup = d(s_memtime) / d(s_memrealtime) x 100 MHz
-    if ((blockIdx.x & 63) == 5 && threadIdx.x == 0) {
-        const unsigned long long c = __builtin_amdgcn_s_memtime() - wbc0, r = __builtin_amdgcn_s_memrealtime() - wbr0;
-        printf("wgclk block %d cycles %llu realtime %llu -> %.3f GHz\n", (int)blockIdx.x, c, r, (double)c / (double)r * 0.1);
-    }
-#endif
 }
 
 }  // namespace

@@ -242,14 +242,24 @@ def mc_apply(x: Tensor, code: Tensor, channels_last: bool = True) -> Tensor:
     return y
 
 
+def _conv_plan(p: '_lib.Conv', dtype: torch.dtype) -> '_lib.ConvPlan':
+    """What mcgen_conv_fused will do with `p` (mcgen_conv_plan: the launch makes this same plan): the launcher, its tile, the
+    rows of `stats`.  Raises where the launch would refuse `p`; asked before `stats` exists."""
+    plan = _lib.ConvPlan()
+    check(_lib.load().mcgen_conv_plan(C.byref(p), _dt(dtype), C.byref(plan)), 'conv_fused')
+    return plan
+
+
 def tile_images(n: int, h: int, w: int, cout: int, dtype: torch.dtype) -> int:
     """Images per output tile of a fused convolution over an [n, h, w] map with `cout` output channels, as the
     launcher's tile policy picks it (1 when a tile lies inside one image)."""
     p = _lib.Conv()
-    p.nseg, p.N, p.H, p.W, p.Cout, p.Cout_w = 1, n, h, w, cout, pad16(cout)
-    bm, bn = C.c_int(), C.c_int()
-    check(_lib.load().mcgen_conv_tile(C.byref(p), _dt(dtype), C.byref(bm), C.byref(bn)), 'conv_tile')
-    return max(1, bm.value // (h * w))
+    p.nseg, p.N, p.H, p.W, p.Cout, p.Cout_w, p.Cy = 1, n, h, w, cout, pad16(cout), pad8(cout)
+    # a plain 8-channel 1x1 segment: no kernel outside the tile table takes it, so the plan names the policy's tile
+    # (the buffers are placeholders that nothing dereferences: the plan only asks whether they are set)
+    p.seg[0].C, p.seg[0].ksize = 8, 1
+    p.seg[0].x = p.w = p.y = 1
+    return max(1, _conv_plan(p, dtype).bm // (h * w))
 
 
 def cmap_stride(c: int) -> int:
@@ -418,31 +428,29 @@ def conv_fused(segs: Sequence[Seg], wimg: Tensor, cout: int, *, bias: Optional[T
         p.ycmap, p.ycmap_stride = _p(ycmap), ycmap.shape[1]
     stats = None
     lib = _lib.load()
+    plan = _conv_plan(p, dtype)          # one question per launch: rows of `stats`, the profile name, the test logs
     if stats_mode:
-        tiles = lib.mcgen_conv_m_tiles(C.byref(p), _dt(dtype))
-        stats = torch.empty((tiles, 2, pad16(cout) if (ycmap is not None or yperm is not None) else cy), dtype=torch.float32, device=y.device)
+        stats = torch.empty((plan.m_tiles, 2, pad16(cout) if (ycmap is not None or yperm is not None) else cy), dtype=torch.float32, device=y.device)
         p.stats = _p(stats)
     kflops = 2.0 * n * h * w * cout * sum(s.ksize * s.ksize * s.x.shape[-1] for s in segs)
 
     def _name():
-        bm, bn = C.c_int(), C.c_int()
-        lib.mcgen_conv_tile(C.byref(p), _dt(dtype), C.byref(bm), C.byref(bn))
-        form = lib.mcgen_conv_form(C.byref(p), _dt(dtype))
-        base = f'conv_fused<{"bf16" if dtype == torch.bfloat16 else "f32"},{bm.value},{bn.value}{(",mc", ",gk")[kmajor - 1] if kmajor else ""}>'
-        if form:
-            base = ('conv_skinny<bf16>', 'conv_smap<bf16>', 'conv_px1<bf16>', 'conv_c8<bf16>', 'conv_head<bf16>')[form - 1]
+        base = f'conv_fused<{"bf16" if dtype == torch.bfloat16 else "f32"},{plan.bm},{plan.bn}{(",mc", ",gk")[kmajor - 1] if kmajor else ""}>'
+        if plan.form:
+            base = ('conv_skinny<bf16>', 'conv_smap<bf16>', 'conv_px1<bf16>', 'conv_c8<bf16>', 'conv_head<bf16>')[plan.form - 1]
         if _PROF_SHAPES:
             base += f' N{n} {h}x{w} ' + '+'.join(f'{s.x.shape[-1]}k{s.ksize}' for s in segs) + f'->{cout}' + \
                 ('g' if gate_x is not None else '') + ('p' if pool else '') + (f's{stats_mode}' if stats_mode else '')
         return base
     if TILE_LOG is not None:
-        bm, bn = C.c_int(), C.c_int()
-        check(lib.mcgen_conv_tile(C.byref(p), _dt(dtype), C.byref(bm), C.byref(bn)), 'conv_tile')
+        bm, bn = C.c_int(plan.bm), C.c_int(plan.bn)
+        if plan.form:       # a kernel in a file of its own has no tile: the log keeps naming the tile policy's pick
+            check(lib.mcgen_conv_tile(C.byref(p), _dt(dtype), C.byref(bm), C.byref(bn)), 'conv_tile')
         TILE_LOG.append((bm.value, bn.value))
     if FORM_LOG is not None:
         FORM_LOG.append(kmajor)
     if KERNEL_LOG is not None:
-        KERNEL_LOG.append(int(lib.mcgen_conv_form(C.byref(p), _dt(dtype))))
+        KERNEL_LOG.append(int(plan.form))
     _timed(_name, kflops, lambda: check(lib.mcgen_conv_fused(C.byref(p), _dt(dtype), _stream()), 'conv_fused'),
            lambda: _nbytes(wimg, y, res, gate_x, *[s.x for s in segs]))
     return y, stats
