@@ -3,7 +3,6 @@ train_pixelcnn driver's model-name / control handling.  CPU only."""
 import ctypes
 import json
 import os
-import re
 import subprocess
 import sys
 
@@ -87,12 +86,11 @@ def test_library_exports_cpixelcnn_kernels():
     lib = _lib.load()
     assert lib.mcgen_abi_version() == 9
     raw = ctypes.CDLL(_lib.LIB_PATH)
-    header = open(os.path.join(ROOT, 'include', 'mcgen_hip.h')).read()
     names = ('mcgen_cpx_gate_stats', 'mcgen_cpx_gated_fwd', 'mcgen_cpx_gated_bwd_stats', 'mcgen_cpx_gated_bwd_apply',
              'mcgen_cpx_embed_bwd', 'mcgen_cpx_gather_rows', 'mcgen_cpx_sample_row', 'mcgen_cpx_sample_col',
              'mcgen_cpx_code_embed_bwd')
     for name in names:
-        assert hasattr(raw, name) and name in _lib.SYMBOLS and re.search(rf'\b{name}\(', header), name
+        assert hasattr(raw, name) and name in _lib.SYMBOLS and name in _lib.HEADER.functions, name
     # host-side argument checks, before any launch
     assert lib.mcgen_cpx_gate_stats(None, 1, 0, None) != 0
     assert b'cpx_gate_stats' in lib.mcgen_last_error()

@@ -22,8 +22,7 @@ def test_library_exports_every_declared_symbol():
         import __graft_entry__
         __graft_entry__.build()
     lib = _lib.load()                                   # binds every name in SYMBOLS (AttributeError if missing)
-    header = open(os.path.join(ROOT, 'include', 'mcgen_hip.h')).read()
-    declared = set(re.findall(r'\b(mcgen_[a-z0-9_]+)\s*\(', header))
+    declared = set(_lib.HEADER.functions)               # every prototype of include/mcgen_hip.h
     assert declared, 'no declarations found'
     assert declared == set(_lib.SYMBOLS), declared ^ set(_lib.SYMBOLS)
     raw = ctypes.CDLL(_lib.LIB_PATH)

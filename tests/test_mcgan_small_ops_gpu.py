@@ -18,8 +18,6 @@ dtype, the accumulation length and the magnitudes of the terms:
 Buffers a kernel writes only in part start as NaN where it must not write, and must still be NaN afterwards.  Every
 layer in a packed table is followed by a NaN gap, in the weights, the u / v state, the gradients and Adam's p, m, v, so a
 read past a layer's end turns into a NaN in its result."""
-import os
-import re
 import types
 import zlib
 
@@ -28,6 +26,7 @@ import torch
 
 import golden_util as gu
 import small_ops_ref as R
+from mcgen_amd._lib import CONSTANTS
 
 pytestmark = pytest.mark.gpu
 
@@ -35,16 +34,8 @@ U32 = 2.0 ** -24
 U16 = 2.0 ** -8
 U64 = 2.0 ** -53
 NAN = float('nan')
-_HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'mcgen_hip.h')
-
-
-def _cap(name):
-    with open(_HEADER) as f:
-        return int(re.search(rf'#define\s+{name}\s+(\d+)', f.read()).group(1))
-
-
-BN_FIN_MAX = _cap('MCGEN_BN_FIN_MAX')      # mcgen_bn_finalize_batch: layers per launch
-BN_RUN_MAX = _cap('MCGEN_BN_RUN_MAX')      # mcgen_bn_running_batch: layers per launch (more run as several launches)
+BN_FIN_MAX = CONSTANTS['MCGEN_BN_FIN_MAX']      # mcgen_bn_finalize_batch: layers per launch
+BN_RUN_MAX = CONSTANTS['MCGEN_BN_RUN_MAX']      # mcgen_bn_running_batch: layers per launch (more run as several launches)
 # thresholds that live only in csrc/small_ops.hip
 SN_RS = 32              # sn_k1_wtu / sn_k3_wv / sn_c3_kernel: row slices per layer
 SN_CS = 32              # sn_c1_kernel: column slices per layer; each slice walks its columns 64 at a time

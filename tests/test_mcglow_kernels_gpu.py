@@ -13,12 +13,12 @@ first).  Tolerances are derived from the output dtype and the length of the accu
 Where a row has padding, destination buffers start as NaN.  Padded channels must come out exactly 0 where the op writes
 them, and channels outside the op's target range must still be NaN afterwards.  Inputs carry NaN in every channel the
 op must not read, so a read of one shows up as a NaN in the result."""
-import os
-import re
 import types
 
 import pytest
 import torch
+
+from mcgen_amd._lib import CONSTANTS
 
 pytestmark = pytest.mark.gpu
 
@@ -27,12 +27,6 @@ U16 = 2.0 ** -8
 NAN = float('nan')
 CIFAR_WIDTHS = [(12, 16), (6, 8), (24, 24), (48, 48)]     # (logical channels, NHWC row pitch)
 DTYPES = [torch.float32, torch.bfloat16]
-_HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'mcgen_hip.h')
-
-
-def _cap(name):
-    with open(_HEADER) as f:
-        return int(re.search(rf'#define\s+{name}\s+(\d+)', f.read()).group(1))
 
 
 def _ops():
@@ -230,7 +224,7 @@ def test_invconv_weight_batch_matches_single():
     from oracle import mcglow_oracle as G
     gen = torch.Generator().manual_seed(7)
     cs = [12, 24, 48, 6, 3, 53, 64, 1]
-    n = _n_jobs(_cap('MCGEN_GLOW_BATCH_MAX'))
+    n = _n_jobs(CONSTANTS['MCGEN_GLOW_BATCH_MAX'])
     prms = [_lu_params(cs[i % len(cs)], gen) for i in range(n)]
     ics = [types.SimpleNamespace(**{k: v.cuda() for k, v in p.items()}) for p in prms]
     ws = _ops().invconv_weight_batch(ics)
@@ -246,7 +240,7 @@ def test_actnorm_affine_batch_matches_single():
     (into NaN-filled buffers) writes the same bits."""
     gen = torch.Generator().manual_seed(8)
     widths = CIFAR_WIDTHS + [(3, 8), (32, 32), (130, 136)]
-    n = _n_jobs(_cap('MCGEN_GLOW_BATCH_MAX'))
+    n = _n_jobs(CONSTANTS['MCGEN_GLOW_BATCH_MAX'])
     ans, cps = [], []
     for i in range(n):
         c, cp = widths[i % len(widths)]
@@ -288,7 +282,7 @@ def test_glow_param_logdet_single_and_batch():
     launch (include/mcgen_hip.h), a different order of additions from a loop of single launches, so they are compared
     through the reference, not bit for bit."""
     gen = torch.Generator().manual_seed(9)
-    n = _cap('MCGEN_GLOW_PLD_MAX') + 6
+    n = CONSTANTS['MCGEN_GLOW_PLD_MAX'] + 6
     cs = [12, 24, 48, 64, 3, 300]
     items = []
     for i in range(n):
@@ -347,7 +341,7 @@ def test_glow_deferred_matches_single():
     _pcs_ref and test_invconv_bwd."""
     ops = _ops()
     gen = torch.Generator().manual_seed(10)
-    n = _n_jobs(_cap('MCGEN_GLOW_BATCH_MAX'))
+    n = _n_jobs(CONSTANTS['MCGEN_GLOW_BATCH_MAX'])
     dfr = ops.GlowDeferred()
     an, pcs, icb = [], [], []
     an_w = [(12, 16, 37), (48, 56, 300), (130, 136, 5), (6, 8, 1), (24, 24, 64)]

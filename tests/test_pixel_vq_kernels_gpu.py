@@ -24,13 +24,12 @@ scalars are passed as their fp32 value.  Tolerances are derived, not observed:
 Destination buffers and row padding start as NaN; padded outputs the op writes must be exactly 0.  Inputs carry NaN in
 every channel or buffer the op must not read."""
 import math
-import os
-import re
 
 import pytest
 import torch
 
 import pixel_ops_ref as R
+from mcgen_amd._lib import CONSTANTS
 
 pytestmark = pytest.mark.gpu
 
@@ -43,15 +42,7 @@ INF = float('inf')
 DTYPES = [torch.float32, torch.bfloat16]
 TANH_ULP = 2                # assumed, see the module docstring
 LOG1P_ULP = 2               # assumed, see the module docstring
-_HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'mcgen_hip.h')
-
-
-def _cap(name):
-    with open(_HEADER) as f:
-        return int(re.search(rf'#define\s+{name}\s+(\d+)', f.read()).group(1))
-
-
-GATED_MAX = _cap('MCGEN_GATED_MAX')
+GATED_MAX = CONSTANTS['MCGEN_GATED_MAX']
 # thresholds that live only in the kernel sources and the wrappers
 GRID_ITEMS = 4096 * 256     # grid_for: 4096 blocks of 256 threads; the grid-stride loops take a second trip above this
 VQ_PC = 128                 # vq_ops.hip: pixels per statistics chunk
