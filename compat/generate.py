@@ -2,7 +2,8 @@
 """Driver counterpart of the reference's src/generate.py:40-107: resume <model_tag>_best.pt (and, for MCPixelCNN, the
 VQ-VAE's <ae_tag>_best.pt), then generate classes_size x generate_per_mode samples in eval mode, in chunks of
 sample_per_iter = 1000.  MCPixelCNN draws its code maps with `model.sample` (every pixel of every layer computed once,
-pixelcnn_sampler.py) and decodes them with `ae.decode_code`; MCGAN / CGAN / MCVAE / CVAE / MCGlow call `model.generate`.
+pixelcnn_sampler.py) and decodes them with `ae.decode_code`; MCGAN / CGAN / MCVAE / CVAE / MCGlow / CGlow call
+`model.generate`.
   --save_npy True:  output/npy/generated_<model_tag>.npy, scaled (x + 1) / 2 * 255, plus (save_img) one grid of
                     save_per_mode samples per mode (generate.py:60-84);
   otherwise:        grids of 10 / 50 / 100 modes x save_per_mode samples (generate.py:85-104).

@@ -2,7 +2,8 @@
 """Driver counterpart of the reference's src/train_glow.py for the MI355X path: train_vae.py's structure plus the
 data-dependent ActNorm initialisation on `num_init_batches` (8) concatenated batches BEFORE the resume / data-parallel
 wrap (train_glow.py:37,60-67) and the reconstruction through `model.reverse` in test() (:156-158).  Shared parts and
-the differences from the reference: compat/_single.py."""
+the differences from the reference: compat/_single.py.
+--model_name mcglow or cglow (the conditional baseline, models/cglow.py; with --control_name None, on one GPU)."""
 from itertools import islice
 
 import torch
@@ -35,11 +36,24 @@ class GlowDriver(Driver):
         return dict(output, **{k: v for k, v in rec.items() if k not in output}) if isinstance(rec, dict) else output
 
 
+MODELS = ('mcglow', 'cglow')
+
+
+def apply_control():
+    """train_glow.py:24-27: --control_name None gives the baseline an empty control (tag <seed>_<data>_<subset>_cglow); any
+    other control name keeps the MC form parse() gave it."""
+    if cfg.get('control_name') == 'None':
+        cfg['control'], cfg['control_name'] = {}, ''
+
+
 def main():
     extra = parse({'pivot_metric': 'Loss', 'metric_name': {'train': ['Loss'], 'test': ['Loss']}, 'show': False,
                    'num_init_batches': 8})
-    if cfg['model_name'] != 'mcglow':
+    apply_control()
+    if cfg['model_name'] not in MODELS:
         raise ValueError('Not valid model name')
+    if cfg['model_name'] == 'cglow' and int(cfg['world_size']) > 1:
+        raise ValueError('CGlow training runs on one GPU: multi-GPU CGlow is not supported; run with --world_size 1')
     GlowDriver(extra).main()
 
 

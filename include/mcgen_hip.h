@@ -789,6 +789,26 @@ int mcgen_cvae_latent_fwd(const void* ml, int ldm, const float* eps, const float
 int mcgen_cvae_latent_bwd(const void* dzrow, int ldz, const float* mu, const float* logvar, const float* eps, float inv_numel,
                           void* dml, float* de, int dtype, int N, int L, int E, int Cq, void* stream);
 
+/* ---- CGlow label-conditioned prior (csrc/cglow_ops.hip) ---------------------------------------------------------------
+ * The last block of the reference's CGlow (models/cglow.py:231-235, 254-258) takes its prior from two ZeroConv2d modules,
+ * prior (3x3, on zeros) and embedding (1x1, on the one-hot label): per sample n and channel co, for every pixel,
+ *   h[n][co] = b_p[co] * exp(3 s_p[co]) + (w_e[co][label_n] + b_e[co]) * exp(3 s_e[co]),   [mean | log_sd] = h.
+ * b_p, s_p, b_e, s_e fp32 [C2]; w_e fp32 [C2, M]; int64 labels; a label outside [0, M) gives a zero embedding row and no
+ * gradient.  Every reduction is fixed-order (pixels, then samples, ascending) with no float atomics.
+ * mcgen_cglow_prior: out [N, HW, Cp] (compute dtype) = [h[n] (C2) | 0] at every pixel: the `prior` operand of
+ * mcgen_gaussian_logp / _logp_bwd / _sample.  Cp <= 8192. */
+int mcgen_cglow_prior(const float* b_p, const float* s_p, const float* w_e, const float* b_e, const float* s_e,
+                      const int64_t* label, void* out, int dtype, int N, int HW, int C2, int M, int Cp, void* stream);
+/* From dprior [N, HW, Cp] (compute dtype; mcgen_gaussian_logp_bwd's dprior), dh[n][co] = sum_p dprior[n][p][co] in fp32:
+ *   db_p = sum_n dh rp,  ds_p = 3 sum_n dh b_p rp,  db_e = sum_n dh re,  ds_e = 3 sum_n dh (w_e[co][label_n] + b_e) re,
+ *   dw_e[co][m] = sum_{n: label_n == m} dh[n][co] re   (rp = exp(3 s_p), re = exp(3 s_e); mcgen_cgan_embed_bwd),
+ *   dw_p (optional, dw_p_elems floats) = 0: the prior's convolution only ever reads zeros.
+ * All outputs are overwritten.  workspace: 2 * N * C2 floats.  Three launches. */
+int mcgen_cglow_prior_bwd(const void* dprior, const float* b_p, const float* s_p, const float* w_e, const float* b_e,
+                          const float* s_e, const int64_t* label, float* workspace, float* db_p, float* ds_p, float* dw_p,
+                          int64_t dw_p_elems, float* dw_e, float* db_e, float* ds_e, int dtype, int N, int HW, int C2, int M,
+                          int Cp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

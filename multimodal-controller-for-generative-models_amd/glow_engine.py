@@ -1,5 +1,5 @@
-"""MCGlow on the HIP kernels: likelihood forward (with the data-dependent ActNorm initialisation) and the
-reverse / sampling pass.  Reference chains: Flow.forward / reverse (mcglow.py:188-201), Block.forward /
+"""MCGlow (GlowEngine) and the CGlow baseline (CGlowEngine, at the end) on the HIP kernels: likelihood forward (with the
+data-dependent ActNorm initialisation) and the reverse / sampling pass.  Reference chains: Flow.forward / reverse (mcglow.py:188-201), Block.forward /
 reverse (mcglow.py:219-265), MCGlow.forward / loss_fn / reverse (mcglow.py:283-325).
 
 Per flow:  ActNorm is folded into the prologue of the invertible 1x1 convolution (fused conv, 1x1);
@@ -23,12 +23,20 @@ Tensor = torch.Tensor
 
 
 class GlowEngine(EngineBase):
+    _has_mc = True            # the coupling networks carry MultimodalControllers (their codes gate two convolutions)
+    _label_prior = False      # the last block's prior depends on the label (CGlowEngine)
+
     def __init__(self, model, dtype: torch.dtype = torch.float32):
         super().__init__(model, dtype)
         self.assume_initialized = False   # set by a graph capture: skip the host read of ActNorm.initialized
         self._const = {}
         self._pass = None                          # per-pass batches (ActNorm vectors, codes): _begin_pass
         self._dfr = None                           # deferred parameter-gradient reductions of a backward pass
+
+    @staticmethod
+    def _layers(net):
+        """(conv0, an1, mc1, conv1, an5, mc2, zc) of an AffineCoupling.net: the one place that knows its layout."""
+        return net[0].module, net[1].module, net[3], net[4].module, net[5].module, net[7], net[8].module
 
     def _full(self, value: float, n: int, device) -> Tensor:
         key = (value, n, str(device))
@@ -52,7 +60,9 @@ class GlowEngine(EngineBase):
         """Fill self._I with every weight image of the pass: {(id(module), tag): image}; self._rs with exp(3 * scale) of
         every ZeroConv2d.  Forward also computes the LU weights (self._wmat) the backward reuses."""
         m, dt = self.m, self.dtype
-        zcs = [f.coupling.net[8].module for b in m.blocks for f in b.flows] + [b.prior for b in m.blocks]
+        # (a label-conditioned last prior takes no convolution: its kernel reads bias and scale itself)
+        zcs = ([self._layers(f.coupling.net)[6] for b in m.blocks for f in b.flows] +
+               [b.prior for b in m.blocks if b.split or not self._label_prior])
         if not backward:
             rs = torch._foreach_exp(torch._foreach_mul([z.scale.detach().reshape(-1) for z in zcs], 3.0))
             self._rs = {id(z): r for z, r in zip(zcs, rs)}
@@ -70,8 +80,7 @@ class GlowEngine(EngineBase):
 
         for blk, (c, cp) in zip(m.blocks, self._block_dims()):
             for flow in blk.flows:
-                net = flow.coupling.net
-                conv0, an1, conv1, an5, zc = net[0].module, net[1].module, net[4].module, net[5].module, net[8].module
+                conv0, an1, _, conv1, an5, _, zc = self._layers(flow.coupling.net)
                 hid, ic, rs = conv0.out_channels, flow.invconv, self._rs[id(zc)]
                 if not backward:
                     wmat = self._wmat[id(ic)]
@@ -84,6 +93,8 @@ class GlowEngine(EngineBase):
                     add((id(conv1), 'b'), conv1.weight, row_scale=an5.scale.detach().reshape(-1))
                     add((id(conv0), 'b'), conv0.weight, row_scale=an1.scale.detach().reshape(-1), rows_img=c)
                     add((id(ic), 'b'), self._wmat[id(ic)], ksize=1, col_scale=flow.actnorm.scale.detach().reshape(-1), k_img=cp)
+            if not blk.split and self._label_prior:
+                continue
             pz, prs = blk.prior, self._rs[id(blk.prior)]
             if not backward:
                 add((id(pz), 'f'), pz.conv.weight, row_scale=prs, k_img=(pad8(c // 2) if blk.split else cp))
@@ -119,14 +130,22 @@ class GlowEngine(EngineBase):
         bz = getattr(self, '_bz', {}).get(id(zc)) if getattr(self, '_I', None) else None
         return img, (bz if bz is not None else zc.conv.bias.detach() * rs)
 
+    def _last_prior(self, blk, like: Tensor, c: int, label) -> Tensor:
+        """[mean | log_sd] of the last block (no split): prior(zeros), 2c channels over the pixels of `like`."""
+        wz, bz = self._zero_conv_image(blk.prior, like.shape[-1])
+        prior, _ = ops.conv_fused([Seg(torch.zeros_like(like))], wz, 2 * c, bias=bz)
+        return prior
+
+    def _last_prior_bwd(self, blk, rec, dprior: Tensor, c: int):
+        self._zero_conv_bwd(blk.prior, None, rec['prior'], dprior, 2 * c, c, False)
+
     def _coupling_net(self, cp_net, x: Tensor, c: int, codes, train: bool, saved=None):
         """AffineCoupling.net on the first c/2 channels of x -> [log_s | t] (c channels)."""
         net = cp_net
         dt = self.dtype
         n, h, w, cp = x.shape
         count = n * h * w
-        conv0, an1, mc1, conv1, an5, mc2, zc = (net[0].module, net[1].module, net[3], net[4].module, net[5].module,
-                                                 net[7], net[8].module)
+        conv0, an1, mc1, conv1, an5, mc2, zc = self._layers(net)
         need1 = train and not self.assume_initialized and int(an1.initialized) == 0
         # the image is zero over the input channels >= c/2: the coupling net reads only the first half of x
         w0img = self._img((id(conv0), 'f'), lambda: ops.prep_weight_ex(conv0.weight.detach(), dt, k_img=cp))
@@ -168,6 +187,8 @@ class GlowEngine(EngineBase):
         return ops.glow_coupling(out, hz, c, logdet, reverse=False, accumulate=True)
 
     def _codes(self, net, indicator, label):
+        if not self._has_mc:
+            return None, None
         cached = self._pass.get('codes') if self._pass else None
         if cached is not None:
             return cached[id(net[3])], cached[id(net[7])]
@@ -186,11 +207,11 @@ class GlowEngine(EngineBase):
         ans, cps, lds = [], [], []
         for blk, (c, cp) in zip(m.blocks, self._block_dims()):
             for flow in blk.flows:
-                net = flow.coupling.net
-                hid = net[0].module.out_channels
-                ans += [flow.actnorm, net[1].module, net[5].module]; cps += [cp, hid, hid]
+                conv0, an1, _, _, an5, _, _ = self._layers(flow.coupling.net)
+                hid = conv0.out_channels
+                ans += [flow.actnorm, an1, an5]; cps += [cp, hid, hid]
         self._pass['an'] = {id(an): v for an, v in zip(ans, ops.actnorm_affine_batch(ans, cps))}
-        if label is not None:
+        if label is not None and self._has_mc:
             mcs = [mc for blk in m.blocks for f in blk.flows for mc in (f.coupling.net[3], f.coupling.net[7])]
             if getattr(self, '_code_batch', None) is None or [id(x) for x in self._code_batch.mcs] != [id(x) for x in mcs]:
                 self._code_batch = ops.CodeBatch(mcs)
@@ -252,12 +273,11 @@ class GlowEngine(EngineBase):
                     brec.update(x=x, keep=keep, prior=prior)
                 x, c = keep, half
             else:
-                wz, bz = self._zero_conv_image(blk.prior, cp)
-                prior, _ = ops.conv_fused([Seg(torch.zeros_like(x))], wz, 2 * c, bias=bz)
+                prior = self._last_prior(blk, x, c, label)
                 ops.gaussian_logp(x, 0, prior, c, logp)
                 zs.append(ops.to_nchw(x, c))
                 if tape is not None:
-                    brec.update(x=x, prior=prior)
+                    brec.update(x=x, prior=prior, label=label)
             if tape is not None:
                 tape.append(brec)
         n_pixel = float(img[0].numel())
@@ -295,7 +315,7 @@ class GlowEngine(EngineBase):
         n, h, w, cp = out.shape
         ld_coef = g0 * n * h * w
         net = flow.coupling.net
-        conv0, an1, conv1, an5, zc = net[0].module, net[1].module, net[4].module, net[5].module, net[8].module
+        conv0, an1, _, conv1, an5, _, zc = self._layers(net)
         hid = conv0.out_channels
         dev = out.device
         ones = self._full(1.0, hid, dev)
@@ -369,7 +389,7 @@ class GlowEngine(EngineBase):
                 ops.copy_channels(dk, 0, dy, 0, half)
             else:
                 dprior = ops.gaussian_logp_bwd(x, 0, rec['prior'], c, dy, 0, g0, False)
-                self._zero_conv_bwd(blk.prior, None, rec['prior'], dprior, 2 * c, c, False)
+                self._last_prior_bwd(blk, rec, dprior, c)
             for flow, frec in reversed(list(zip(blk.flows, rec['flows']))):
                 dy = self._flow_backward(flow, frec, dy, c, g0)
             dkeep = ops.glow_unsqueeze(dy, c)
@@ -402,10 +422,35 @@ class GlowEngine(EngineBase):
                 if reconstruct:
                     ops.copy_channels(eps, 0, inp, 0, c)
                 else:
-                    wz, bz = self._zero_conv_image(blk.prior, inp.shape[-1])
-                    prior, _ = ops.conv_fused([Seg(torch.zeros_like(inp))], wz, 2 * c, bias=bz)
-                    ops.gaussian_sample(eps, prior, inp, 0, c)
+                    ops.gaussian_sample(eps, self._last_prior(blk, inp, c, label), inp, 0, c)
             for flow in reversed(list(blk.flows)):
                 inp = self._flow_reverse(flow, inp, c, indicator, label)
             x = ops.glow_unsqueeze(inp, c)
         return torch.clamp(ops.to_nchw(x, m.data_shape[0]), -.5, .5) * 2
+
+
+class CGlowEngine(GlowEngine):
+    """CGlow, the reference's non-MC baseline (cglow.py): the same flow with plain coupling networks (no Wrapper, no
+    MultimodalController: `code=None` everywhere) and, in the last block, the label-conditioned prior
+    prior(zeros) + embedding(one_hot(label)) (cglow.py:231-235, 254-258) from ops.cglow_prior instead of a convolution over
+    zeros.  The embeddings of the split blocks exist in the reference but are never used: they get no gradient."""
+    _has_mc = False
+    _label_prior = True
+
+    @staticmethod
+    def _layers(net):
+        return net[0], net[1], None, net[3], net[4], None, net[6]
+
+    @staticmethod
+    def _prior_params(blk):
+        p, e = blk.prior, blk.embedding
+        return p.conv.bias, p.scale, e.conv.weight, e.conv.bias, e.scale
+
+    def _last_prior(self, blk, like: Tensor, c: int, label) -> Tensor:
+        _, h, w, _ = like.shape
+        return ops.cglow_prior(*(t.detach() for t in self._prior_params(blk)), label, h, w, self.dtype)
+
+    def _last_prior_bwd(self, blk, rec, dprior: Tensor, c: int):
+        b_p, s_p, w_e, b_e, s_e = self._prior_params(blk)
+        ops.cglow_prior_bwd(dprior, *(t.detach() for t in (b_p, s_p, w_e, b_e, s_e)), rec['label'], self._grad(b_p), self._grad(s_p),
+                            self._grad(blk.prior.conv.weight), self._grad(w_e), self._grad(b_e), self._grad(s_e))

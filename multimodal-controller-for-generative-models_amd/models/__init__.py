@@ -8,3 +8,4 @@ from .classifier import classifier, Classifier  # noqa: F401
 from .cgan import cgan, CGAN  # noqa: F401
 from .cpixelcnn import cpixelcnn, ConditionalGatedPixelCNN  # noqa: F401
 from .cvae import cvae, CVAE  # noqa: F401
+from .cglow import cglow, CGlow  # noqa: F401

@@ -1966,3 +1966,47 @@ def cvae_latent_bwd(dzrow: Tensor, mu: Tensor, logvar: Tensor, eps: Tensor, inv_
     check(_lib.load().mcgen_cvae_latent_bwd(_p(dzrow), ldz, _f32(mu), _f32(logvar), _f32(eps), float(inv_numel), _p(dml), _f32(de),
                                             _dt(dzrow.dtype), n, latent, e, cq, _stream()), 'cvae_latent_bwd')
     return dml, de
+
+
+# ---- CGlow label-conditioned prior (glow_engine.py: CGlowEngine) --------------------------------------------------------
+def _cglow_params(b_p: Tensor, s_p: Tensor, w_e: Tensor, b_e: Tensor, s_e: Tensor, label: Tensor, what: str):
+    """(C2, M) of the last block's ZeroConv2d pair: prior bias / scale, embedding weight [C2, M(, 1, 1)] / bias / scale, all
+    contiguous fp32 with C2 entries per vector."""
+    c2 = b_p.numel()
+    if w_e.dim() not in (2, 4) or w_e.shape[0] != c2 or w_e.numel() != c2 * w_e.shape[1] or c2 % 2:
+        raise _lib.McgenError(f'{what}: the embedding weight must be [{c2}, M(, 1, 1)] with an even channel count, got {tuple(w_e.shape)}')
+    if any(t.numel() != c2 for t in (s_p, b_e, s_e)):
+        raise _lib.McgenError(f'{what}: prior / embedding biases and scales must hold {c2} entries each')
+    if label.dim() != 1:
+        raise _lib.McgenError(f'{what}: labels must be a vector')
+    return c2, w_e.shape[1]
+
+
+def cglow_prior(b_p: Tensor, s_p: Tensor, w_e: Tensor, b_e: Tensor, s_e: Tensor, label: Tensor, h: int, w: int,
+                dtype: torch.dtype) -> Tensor:
+    """[N, h, w, pad8(C2)] in `dtype`: prior(zeros) + embedding(one_hot(label)) of CGlow's last block (cglow.py:231-235),
+    b_p exp(3 s_p) + (w_e[:, label] + b_e) exp(3 s_e) at every pixel, pad channels zero.  One launch (mcgen_cglow_prior)."""
+    c2, m = _cglow_params(b_p, s_p, w_e, b_e, s_e, label, 'cglow_prior')
+    n, cp = label.numel(), pad8(c2)
+    out = torch.empty((n, h, w, cp), dtype=dtype, device=b_p.device)
+    check(_lib.load().mcgen_cglow_prior(_f32(b_p), _f32(s_p), _f32(w_e), _f32(b_e), _f32(s_e), _p(_labels64(label)), _p(out),
+                                        _dt(dtype), n, h * w, c2, m, cp, _stream()), 'cglow_prior')
+    return out
+
+
+def cglow_prior_bwd(dprior: Tensor, b_p: Tensor, s_p: Tensor, w_e: Tensor, b_e: Tensor, s_e: Tensor, label: Tensor,
+                    db_p: Tensor, ds_p: Tensor, dw_p: Optional[Tensor], dw_e: Tensor, db_e: Tensor, ds_e: Tensor):
+    """Backward of cglow_prior from dprior [N, H, W, Cp] (gaussian_logp_bwd's): overwrites the gradients of the prior's bias /
+    scale, the embedding's weight / bias / scale, and zeroes dw_p (prior.conv.weight reads only zeros).  Fixed summation order
+    (pixels, then samples, ascending); three launches (mcgen_cglow_prior_bwd)."""
+    c2, m = _cglow_params(b_p, s_p, w_e, b_e, s_e, label, 'cglow_prior_bwd')
+    n, cp = dprior.shape[0], dprior.shape[-1]
+    if label.numel() != n or cp < c2:
+        raise _lib.McgenError(f'cglow_prior_bwd: {label.numel()} labels, {c2} channels for a gradient of shape {tuple(dprior.shape)}')
+    if dw_e.numel() != w_e.numel() or any(t.numel() != c2 for t in (db_p, ds_p, db_e, ds_e)):
+        raise _lib.McgenError('cglow_prior_bwd: every gradient must have its parameter\'s size')
+    ws = torch.empty(2 * n * c2, dtype=torch.float32, device=dprior.device)
+    check(_lib.load().mcgen_cglow_prior_bwd(_p(dprior), _f32(b_p), _f32(s_p), _f32(w_e), _f32(b_e), _f32(s_e), _p(_labels64(label)),
+                                            _f32(ws), _f32(db_p), _f32(ds_p), _f32(dw_p), 0 if dw_p is None else dw_p.numel(),
+                                            _f32(dw_e), _f32(db_e), _f32(ds_e), _dt(dprior.dtype), n, dprior.numel() // (n * cp),
+                                            c2, m, cp, _stream()), 'cglow_prior_bwd')

@@ -819,7 +819,12 @@ class _FlatTrainer:
 
 
 class GlowTrainer(_FlatTrainer):
-    """train_glow.py:108-121 on the HIP path (see _FlatTrainer)."""
+    """train_glow.py:108-121 on the HIP path (see _FlatTrainer).  MCGlow or the CGlow baseline (one GPU)."""
+
+    def __init__(self, model, *a, world_size=1, **k):
+        if world_size > 1 and model._engine_cls._label_prior:
+            raise ValueError('CGlow training runs on one GPU: multi-GPU CGlow is not supported; run with world_size 1')
+        super().__init__(model, *a, world_size=world_size, **k)
 
     def _compute(self, img, label, noise):
         eng = self.model._engine()

@@ -1221,6 +1221,91 @@ def fx_cvae_full():
 
 FIXTURES.update(cvae_small=fx_cvae_small, cvae_omniglot_small=fx_cvae_omniglot_small, cvae_full=fx_cvae_full)
 
+
+# ---- CGlow (models/cglow.py): the conditional Glow baseline, a label-conditioned prior in the last block ------------------
+def _cglow_small(name, channels, classes, steps, step_file=None):
+    """CGlow [channels,32,32], K=2, L=3, hidden 32, B=4 with a repeated label, the last mode and most modes absent.  The
+    zero-initialised ZeroConv2d weights, biases and scales (coupling nets, priors, embeddings) are perturbed from a seeded
+    generator first -- at the all-zero initialisation the scale gradients vanish identically -- and the perturbed state is
+    stored.  Then: ActNorm data init (first forward), `steps` train_glow.py steps with the gradients of the first one (before
+    clip_grad_norm_), eval loss, reverse(reconstruct) and sampling from fixed z.  Later states are stored as the tensors
+    that changed: sd_init/ whole, sd_final_delta/ as differences from the initialised state.  `step_file` takes the first
+    step's gradients and the final differences where one file would be too large."""
+    import models
+    cfg['model_name'] = 'cglow'; cfg['device'] = 'cpu'; cfg['classes_size'] = classes
+    cfg['data_shape'] = [channels, 32, 32]
+    cfg['glow'] = {'hidden_size': 32, 'K': 2, 'L': 3, 'affine': True, 'conv_lu': True}
+    torch.manual_seed(0); np.random.seed(0)
+    model = models.cglow(); model.train(True)
+    g = torch.Generator().manual_seed(97)
+    with torch.no_grad():
+        for mod in model.modules():
+            if mod.__class__.__name__ == 'ZeroConv2d':
+                for t in (mod.conv.weight, mod.conv.bias, mod.scale):
+                    t.add_(0.02 * torch.randn(t.shape, generator=g))
+    sd0 = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    arrays = np_state(sd0, 'sd/')
+    arrays['layout'] = _cgan_layout({k: tuple(v.shape) for k, v in sd0.items()})
+    img, lab = gu.synthetic_batch(4, classes, seed=57, shape=(channels, 32, 32))
+    lab[0] = 1; lab[1] = classes - 1; lab[2] = 1; lab[3] = 0
+    arrays['img'] = img.numpy(); arrays['label'] = lab.numpy()
+    with _PatchedNoise(400) as pn, torch.no_grad():                       # train_glow.py:60-67 data-dependent init
+        model({'img': img.clone(), 'label': lab})
+    arrays['noise/init/0'] = pn.drawn[0].numpy()
+    sdi = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    arrays.update(np_state({k: v for k, v in sdi.items() if not torch.equal(v, sd0[k])}, 'sd_init/'))
+    opt = torch.optim.Adam(model.parameters(), lr=3e-4)
+    losses = []
+    for s in range(steps):
+        with _PatchedNoise(500 + s) as pn:
+            opt.zero_grad()
+            out = model({'img': img.clone(), 'label': lab})
+            out['loss'].backward()
+        arrays[f'noise/{s}/0'] = pn.drawn[0].numpy()
+        if s == 0:
+            for i, z in enumerate(out['z']):
+                arrays[f'z0/{i}'] = z.detach().numpy()
+            for k, p in model.named_parameters():
+                if p.grad is not None:                                    # the split blocks' embeddings get none
+                    arrays['grad0/' + k] = p.grad.detach().numpy().copy()
+        torch.nn.utils.clip_grad_norm_(model.parameters(), 1)
+        opt.step()
+        losses.append(out['loss'].item())
+    arrays['losses'] = np.array(losses, dtype=np.float64)
+    for k, v in model.state_dict().items():
+        if not torch.equal(v, sdi[k]):
+            arrays['sd_final_delta/' + k] = (v - sdi[k]).detach().numpy()
+    model.train(False)
+    with torch.no_grad(), _PatchedNoise(600) as pn:
+        out = model({'img': img.clone(), 'label': lab})
+        arrays['noise/eval/0'] = pn.drawn[0].numpy()
+        arrays['loss_eval'] = np.array(out['loss'].item())
+        rec = model.reverse({'z': out['z'], 'label': lab, 'reconstruct': True})['img']
+        arrays['reconstructed'] = rec.numpy()
+        gz = [torch.randn(4, *s, generator=torch.Generator().manual_seed(7 + i)) * 0.7 for i, s in enumerate(model.make_z_shapes())]
+        for i, z in enumerate(gz):
+            arrays[f'gen_z/{i}'] = z.numpy()
+        arrays['generated'] = model.generate(lab, gz).numpy()
+    if step_file:                       # the 3-channel model's arrays do not fit one file of the size a committed file may have
+        step = {k: arrays.pop(k) for k in list(arrays) if k.startswith(('grad0/', 'sd_final_delta/'))}
+        save(step_file, **step)
+    save(name, **arrays)
+
+
+def fx_cglow_small():
+    _cglow_small('cglow_small.npz', 1, 12, 2)
+
+
+def fx_cglow_cifar_small():
+    _cglow_small('cglow_cifar_small.npz', 3, 10, 2, step_file='cglow_cifar_small_step.npz')
+
+
+def fx_cglow_omniglot_small():
+    _cglow_small('cglow_omniglot_small.npz', 1, 1623, 1)
+
+
+FIXTURES.update(cglow_small=fx_cglow_small, cglow_cifar_small=fx_cglow_cifar_small, cglow_omniglot_small=fx_cglow_omniglot_small)
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--only', default=None)
