@@ -1688,7 +1688,7 @@ def prep_weight_ex(w: Tensor, dtype: torch.dtype, ksize: Optional[int] = None, *
 
 
 def prep_weight_ex_many(jobs, dtype: torch.dtype):
-    """Several prep_weight_ex images in ceil(n / 16) launches.  `jobs`: list of (w, kwargs) with the keyword arguments of
+    """Several prep_weight_ex images in ceil(n / MCGEN_PREPEX_MAX) = ceil(n / 32) launches.  `jobs`: list of (w, kwargs) with the keyword arguments of
     prep_weight_ex (ksize, kh0, kw0, transpose, row_scale, col_scale, rows_img, k_img, wscale).  Returns the images."""
     if not jobs:
         return []
