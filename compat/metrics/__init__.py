@@ -61,7 +61,10 @@ def NLL(output, target):
 
 
 def DBI(img, label):
-    """metrics.py:164-166 (scikit-learn's Davies-Bouldin index on the flattened images)."""
+    """metrics.py:164-166 (scikit-learn's Davies-Bouldin index on the flattened images): on the device for a CUDA tensor
+    (mcgen_amd.metrics.davies_bouldin, only the score reaches the host), scikit-learn itself for a CPU tensor."""
+    if img.is_cuda:
+        return _m.davies_bouldin(img.float(), label.to(img.device).long())
     from sklearn.metrics import davies_bouldin_score
     return float(davies_bouldin_score(img.view(img.size(0), -1).cpu().numpy(), label.cpu().numpy()))
 

@@ -809,6 +809,26 @@ int mcgen_cglow_prior_bwd(const void* dprior, const float* b_p, const float* s_p
                           int64_t dw_p_elems, float* dw_e, float* db_e, float* ds_e, int dtype, int N, int HW, int C2, int M,
                           int Cp, void* stream);
 
+/* ---- Davies-Bouldin index on the device (csrc/dbi_ops.hip) --------------------------------------------------------------
+ * scikit-learn's davies_bouldin_score (the reference's metrics.py:164-166) of rows x [N, D] fp32 in K clusters.  The caller
+ * groups the rows: cluster [N] int64 in [0, K) (the labels compressed to the ones present), order [N] int64 = the row ids
+ * sorted by cluster, offset [K + 1] int64 = each cluster's segment of `order` (no segment empty).  Inputs are read as fp32,
+ * every sum is fp64, every reduction has a fixed order and there are no atomics: the same input gives the same bits.
+ * mcgen_dbi_centroids: cent [K, D] fp64 = the cluster means.  K <= 65535. */
+int mcgen_dbi_centroids(const float* x, const int64_t* order, const int64_t* offset, double* cent, int64_t N, int D, int K,
+                        void* stream);
+/* dist [N] fp64 (workspace) = the Euclidean distance of row order[r] to its cluster's centroid, in sorted order;
+ * spread [K] fp64 = its mean per cluster (scikit-learn's intra_dists).  Two launches. */
+int mcgen_dbi_spread(const float* x, const int64_t* order, const int64_t* cluster, const int64_t* offset, const double* cent,
+                     double* dist, double* spread, int64_t N, int D, int K, void* stream);
+/* The centroid-pair stage in 16 x 16 tiles, T = mcgen_dbi_tiles(K) per side: M_kl = ||c_k - c_l||, a zero M_kl counting as
+ * +inf; tile_ratio / tile_m [K, T] fp64 (workspace) = per tile the row maxima of (s_k + s_l) / M_kl and of M_kl.
+ * out [3] fp64 = { mean_k max_l (s_k + s_l) / M_kl,  max_k s_k,  max_kl M_kl }: the score, and what the caller needs for
+ * scikit-learn's "all spreads or all distances are zero -> 0.0".  Two launches. */
+int mcgen_dbi_tiles(int K);
+int mcgen_dbi_score(const double* cent, const double* spread, double* tile_ratio, double* tile_m, double* out, int D, int K,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,9 +44,16 @@ class CGeneratorEngine:
         self.gen = gen
         self.dtype = dtype
         self.flat_p = FlatState(list(gen.parameters()))
+        self._emb_slot = next(i for i, p in enumerate(self.flat_p.tensors) if p is gen.embedding.weight)
         self._img_key = None
         self.img: Dict[str, Tensor] = {}
         self._prep_fwd = self._prep_bwd = None
+
+    def rebind(self):
+        """Follow an embedding table that create() / transit() replaced: `embedding.weight` is then a new nn.Parameter
+        (another object, possibly another shape), so the flat parameter set is laid out again over the live parameters."""
+        if self.flat_p.tensors[self._emb_slot] is not self.gen.embedding.weight:
+            self.flat_p = FlatState(list(self.gen.parameters()))
 
     def _layers(self):
         """(embedding, linear, [GenResBlock], head BN, head conv) of cgan.py:39-53."""
@@ -147,8 +154,12 @@ class CGeneratorEngine:
         N / groups images each, every one with its own BatchNorm batch statistics, as one pass (GANTrainer.fake_groups).
         `nhwc`: return the images as `Nhwc` instead of NCHW fp32."""
         _pending_counters.clear(); _pending_running.clear()
+        self.rebind()
         self.flat_p.ensure()
         emb, lin, res, head_bn, head_conv = self._layers()
+        if train and emb.weight.shape[1] != emb.in_features:
+            raise ValueError(f'Not valid mode: generator.embedding holds {emb.weight.shape[1]} modes but was built for '
+                             f'{emb.in_features}; after create() only evaluation-mode generation is supported')
         dt = self.dtype
         n = z.shape[0]
         if groups > 1 and not (train and self.groups_supported(n, groups)):

@@ -122,3 +122,35 @@ def fid(img: torch.Tensor, data_name: str, real=None, model=None, batch_size: in
             _REAL_CACHE.clear()
             _REAL_CACHE[key] = (real, rf)           # (keeps `real` alive so the id stays unique)
         return fid_from_features(_REAL_CACHE[key][1], f(img))
+
+
+# ---- Davies-Bouldin index (metrics.py:164-166 DBI) -------------------------------------------------------------------
+def davies_bouldin(img: torch.Tensor, label: torch.Tensor) -> float:
+    """scikit-learn's davies_bouldin_score on the flattened images, computed on the device: img [N, ...] float32, label [N]
+    int64, both on the GPU.  Labels are compressed to the ones present; s_k is the mean Euclidean distance of cluster k's
+    rows to their mean c_k, M_kl = ||c_k - c_l|| with a zero counting as +inf, and the score is mean_k max_l (s_k + s_l) / M_kl
+    -- or 0.0 when every s or every M is (allclose) zero.  Fewer than 2 clusters or as many as samples: ValueError.
+
+    torch supplies the grouping (unique, a stable argsort, a cumulative sum); the sums run in csrc/dbi_ops.hip, in float64
+    and in a fixed order, so two calls on one input return the same float.  Only that float reaches the host."""
+    from . import ops
+    if img.dtype != torch.float32 or not img.is_cuda:
+        raise ValueError(f'Not valid input: davies_bouldin needs float32 images on the device, got {img.dtype} on {img.device}')
+    if label.dtype != torch.int64 or label.dim() != 1 or label.shape[0] != img.shape[0] or label.device != img.device:
+        raise ValueError('Not valid label: davies_bouldin needs one int64 label per image, on the images\' device')
+    n = img.shape[0]
+    x = img.reshape(n, -1).contiguous()
+    present, cluster, counts = torch.unique(label, return_inverse=True, return_counts=True)
+    k = present.numel()
+    if not 1 < k < n:                                   # sklearn's check_number_of_labels
+        raise ValueError('Number of labels is %d. Valid values are 2 to n_samples - 1 (inclusive)' % k)
+    cluster = cluster.contiguous()
+    order = torch.argsort(cluster, stable=True)
+    offset = torch.zeros(k + 1, dtype=torch.int64, device=x.device)
+    offset[1:] = counts.cumsum(0)
+    cent = ops.dbi_centroids(x, order, offset)
+    spread = ops.dbi_spread(x, order, cluster, offset, cent)
+    score, s_max, m_max = ops.dbi_score(cent, spread).tolist()
+    if s_max <= 1e-8 or m_max <= 1e-8:                  # np.allclose(., 0): absolute tolerance 1e-8 on non-negative values
+        return 0.0
+    return score

@@ -16,7 +16,7 @@ import torch.nn as nn
 
 from ..cgan_engine import CDiscriminatorEngine, CGeneratorEngine
 from ..config import cfg
-from .utils import FusedNet, init_param, make_SpectralNormalization
+from .utils import FusedNet, init_param, live_modes, make_SpectralNormalization
 
 
 class GenResBlock(nn.Module):
@@ -63,10 +63,16 @@ class Generator(FusedNet):
         blocks += [nn.BatchNorm2d(hidden_size[-1]), nn.ReLU(), nn.Conv2d(hidden_size[-1], data_shape[0], 3, 1, 1), nn.Tanh()]
         self.blocks = nn.Sequential(*blocks)
 
+    def table_modes(self, train: bool) -> int:
+        """The column count of the live embedding table, the one the engine gathers from."""
+        w = self.embedding.weight
+        return live_modes([('generator.embedding', w.shape[1])], self.embedding.in_features, train)
+
     def forward(self, input, indicator, label: Optional[torch.Tensor] = None):
         """cgan.py:55-62.  The embedding is a column gather W[:, label]: `label` (int64) when the caller has it, else the
         argmax of the one-hot `indicator`."""
         eng = self._engine()
+        eng.rebind()
         eng.flat_p.ensure()
         lab = label if label is not None else indicator.argmax(1)
         return _GenFn.apply(eng, input, lab, self.training, *eng.flat_p.tensors)
@@ -137,8 +143,20 @@ class Discriminator(FusedNet):
         blocks += [nn.ReLU(), GlobalSumPooling(), nn.Linear(h[-1], 1)]
         self.blocks = nn.Sequential(*blocks)
 
+    def table_modes(self, train: bool) -> int:
+        """The column count of the table the engine gathers from: the spectral norm's `weight_orig`.  create() / transit()
+        install a `weight` parameter beside it that the engine (like the reference's own spectral-norm hook) cannot use,
+        after create() with another width than `weight_orig`: the discriminator is refused from then on."""
+        emb = self.embedding
+        if 'weight' in emb._parameters:
+            raise ValueError('Not valid discriminator: create() / transit() replaced discriminator.embedding.weight '
+                             f'({tuple(emb.weight.shape)}) while the spectral norm keeps weight_orig '
+                             f'({tuple(emb.weight_orig.shape)}); only the generator runs after surgery')
+        return live_modes([('discriminator.embedding', emb.weight_orig.shape[1])], emb.in_features, train)
+
     def forward(self, input, indicator, label: Optional[torch.Tensor] = None):
         """cgan.py:164-170 (`label` as in Generator.forward)."""
+        self.table_modes(self.training)
         eng = self._engine()
         eng._ensure_flat()
         lab = label if label is not None else indicator.argmax(1)
@@ -161,25 +179,27 @@ class CGAN(nn.Module):
         self.discriminator.set_compute_dtype(dtype)
         return self
 
-    def _labels(self, C):
+    def _labels(self, C, net):
         """The engines gather embedding columns by label, so the one-hot indicator of the reference (cgan.py:183,188) is
-        not built.  Its F.one_hot rejects a label outside [0, classes_size): evaluation mode checks that here (one host
-        read) and raises ValueError before any launch; training mode adds no host synchronisation -- there the kernels
-        give such a label a zero embedding and no gradient, and never read outside the embedding."""
+        not built.  Its F.one_hot rejects a label outside the table: evaluation mode checks that here (one host read)
+        against the column count of the live table `net`'s engine gathers from, and raises ValueError before any launch;
+        training mode adds no host synchronisation -- there the kernels give such a label a zero embedding and no
+        gradient, and never read outside the embedding."""
         if C.dtype != torch.int64 or C.dim() != 1:
             raise ValueError(f'labels must be a 1-d int64 tensor, got {C.dtype} {tuple(C.shape)}')
-        if not self.training and C.numel() and not (0 <= int(C.min()) and int(C.max()) < cfg['classes_size']):
-            raise ValueError(f"labels must lie in [0, {cfg['classes_size']})")
+        modes = net.table_modes(self.training)
+        if not self.training and C.numel() and not (0 <= int(C.min()) and int(C.max()) < modes):
+            raise ValueError(f'labels must lie in [0, {modes})')
         return C
 
     def generate(self, C, x=None):
-        C = self._labels(C)
+        C = self._labels(C, self.generator)
         if x is None:
             x = torch.randn([C.size(0), self.latent_size], device=cfg['device'])
         return self.generator(x, None, label=C)
 
     def discriminate(self, x, C):
-        return self.discriminator(x, None, label=self._labels(C))
+        return self.discriminator(x, None, label=self._labels(C, self.discriminator))
 
     def forward(self, input):
         x = torch.randn(input['img'].size(0), self.latent_size, device=cfg['device'])

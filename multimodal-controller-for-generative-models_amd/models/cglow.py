@@ -13,7 +13,7 @@ import torch.nn as nn
 from ..config import cfg
 from ..glow_engine import CGlowEngine
 from .mcglow import ActNorm, InvConv2dLU, MCGlow
-from .utils import FusedNet, init_param
+from .utils import FusedNet, check_labels, init_param, live_modes
 
 
 class ZeroConv2d(nn.Module):
@@ -86,12 +86,10 @@ class CGlow(FusedNet):
 
     def _label(self, label):
         """The prior kernel gives a label outside the table a zero embedding row; the reference's F.one_hot (cglow.py:298,317)
-        rejects one, so it is refused here, on the host, before any launch."""
-        if label.dtype != torch.int64 or label.dim() != 1:
-            raise ValueError('Not valid label: expected an int64 vector of class indices')
-        if label.numel() and (int(label.min()) < 0 or int(label.max()) >= self.num_mode):
-            raise ValueError(f'Not valid label: every label must lie in [0, {self.num_mode})')
-        return label
+        rejects one, so it is refused here, on the host, before any launch.
+        The bound is the column count of the live table the prior kernel gathers from: the last block's."""
+        tables = [(f'blocks.{len(self.blocks) - 1}.embedding.conv', self.blocks[-1].embedding.conv.weight.shape[1])]
+        return check_labels(label, live_modes(tables, self.num_mode, self.training))
 
     def forward(self, input):
         """Negative log-likelihood in bits/dim (cglow.py:284-313).  The dequantisation noise U(0,1)/256 is drawn here unless

@@ -10,16 +10,23 @@ import torch.nn.functional as F
 
 from ..config import cfg
 from ..cpixelcnn_engine import CPixelCNNEngine
-from .utils import FusedNet, init_param
+from .utils import FusedNet, init_param, live_modes
 
 
 def _check_labels(m, label):
     """Labels are gathered on the device with no host check inside the kernels (they clamp): refuse bad ones up front."""
     if label.dtype != torch.int64:
         raise ValueError(f'Not valid label dtype: {label.dtype}, CPixelCNN needs int64')
-    modes = m.layers[0].class_cond_embedding.num_embeddings
+    modes = table_modes(m)
     if label.numel() and (int(label.min()) < 0 or int(label.max()) >= modes):
         raise ValueError(f'Not valid label: every label must lie in [0, {modes})')
+
+
+def table_modes(m) -> int:
+    """The row count of the live class_cond_embedding tables (every layer gathers from its own, so all must agree); a
+    training-mode model whose tables no longer have the constructor's count is refused."""
+    tables = [(f'layers.{i}.class_cond_embedding', L.class_cond_embedding.weight.shape[0]) for i, L in enumerate(m.layers)]
+    return live_modes(tables, m.layers[0].class_cond_embedding.num_embeddings, m.training)
 
 
 class GatedActivation(nn.Module):

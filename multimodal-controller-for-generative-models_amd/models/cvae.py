@@ -10,7 +10,7 @@ import torch.nn as nn
 
 from ..config import cfg
 from ..cvae_engine import CVAEEngine
-from .utils import FusedNet, init_param
+from .utils import FusedNet, check_labels, init_param, live_modes
 
 
 def _bn_relu(width):
@@ -79,15 +79,14 @@ class CVAE(FusedNet):
         self.encoder = Encoder(data_shape, hidden_size, latent_size, num_res_block, num_mode, embedding_size)
         self.decoder = Decoder(data_shape, hidden_size, latent_size, num_res_block, num_mode, embedding_size)
 
-    def _label(self, label):
+    def _label(self, label, encoder=True):
         """The kernels gather embedding columns by label and give a label outside the table a zero row; the reference's
-        F.one_hot (cvae.py:126,135) rejects one, so it is refused here, on the host, before any launch."""
-        if label.dtype != torch.int64 or label.dim() != 1:
-            raise ValueError('Not valid label: expected an int64 vector of class indices')
-        modes = self.encoder.embedding.in_features
-        if label.numel() and (int(label.min()) < 0 or int(label.max()) >= modes):
-            raise ValueError(f'Not valid label: every label must lie in [0, {modes})')
-        return label
+        F.one_hot (cvae.py:126,135) rejects one, so it is refused here, on the host, before any launch.  The bound is the
+        column count of the live tables this call gathers from (the decoder's, and the encoder's unless `encoder` is False)."""
+        tables = [('decoder.embedding', self.decoder.embedding.weight.shape[1])]
+        if encoder:
+            tables.append(('encoder.embedding', self.encoder.embedding.weight.shape[1]))
+        return check_labels(label, live_modes(tables, self.num_mode, self.training))
 
     def generate(self, C, z=None):
         """Decode of a latent under the labels C (cvae.py:123-129) -> images in (-1, 1)."""
@@ -96,7 +95,7 @@ class CVAE(FusedNet):
         from .. import ops
         eng = self._engine()
         with torch.no_grad():
-            logits = eng.decode(eng.latent_rows(z, self._label(C)), self.training, None)
+            logits = eng.decode(eng.latent_rows(z, self._label(C, encoder=False)), self.training, None)
         return torch.sigmoid(ops.to_nchw(logits, self.data_shape[0])) * 2 - 1
 
     def forward(self, input):

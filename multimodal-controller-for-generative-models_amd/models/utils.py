@@ -1,4 +1,4 @@
-"""Parameter initialisation, spectral-norm applicator and codebook surgery with the reference's
+"""Parameter initialisation, spectral-norm applicator and codebook / label-embedding surgery with the reference's
 names and arity (src/models/utils.py:7-152); the plumbing every fused model shares (engine holder, autograd bridge)."""
 from __future__ import annotations
 
@@ -84,6 +84,32 @@ def make_SpectralNormalization(m):
     return m
 
 
+def live_modes(tables, built=None, train=False) -> int:
+    """The mode count of label-embedding tables, read from the live weights at call time: `tables` = [(name, modes)] of every
+    table a call will index.  create() swaps tables for ones with another number of modes, so nothing caches this count:
+    the host-side label check and the gather kernels both take it from the same tensors.  Tables that disagree, or a
+    training-mode call (`train`) on tables that no longer have the `built` count of the constructor, raise ValueError."""
+    counts = {modes for _, modes in tables}
+    if len(counts) != 1:
+        raise ValueError('Not valid embedding: the label tables disagree about the number of modes: '
+                         + ', '.join(f'{n} has {m}' for n, m in tables))
+    modes = counts.pop()
+    if train and built is not None and modes != built:
+        raise ValueError(f'Not valid mode: the label tables hold {modes} modes but the model was built for {built}; '
+                         'after create() only evaluation-mode generation is supported')
+    return modes
+
+
+def check_labels(label, modes: int):
+    """int64 vector of labels in [0, modes), checked on the host before any launch (the reference's F.one_hot rejects
+    the others; the gather kernels must never see one)."""
+    if label.dtype != torch.int64 or label.dim() != 1:
+        raise ValueError('Not valid label: expected an int64 vector of class indices')
+    if label.numel() and (int(label.min()) < 0 or int(label.max()) >= modes):
+        raise ValueError(f'Not valid label: every label must lie in [0, {modes})')
+    return label
+
+
 def _is_mc(module) -> bool:
     return module.__class__.__name__ == 'MultimodalController'
 
@@ -94,19 +120,48 @@ def create_codebook(codebook):
 
 
 def create_embedding(embedding):
-    """Dirichlet convex combinations of existing embeddings (models/utils.py:24-31); only the
-    non-MC baselines own embeddings, kept for surface compatibility."""
+    """Dirichlet(1) convex combinations of the existing embedding rows, one per new mode (models/utils.py:24-31):
+    embedding [modes, E] -> [cfg['classes_size'], E]."""
     c = embedding.size(0)
     mix = torch.distributions.dirichlet.Dirichlet(torch.ones(c, device=embedding.device)).sample((cfg['classes_size'],))
     return mix.matmul(embedding).to(cfg['device'])
 
 
+def _embedding_table(model, name, module):
+    """How the reference's create / transit address `module` as a label-embedding table of `model`
+    (models/utils.py:54-56, 64-66, 74-75, 84-86): (to_rows, from_rows) between the weight and its [modes, E] form, or None
+    when the module is not one.  The dispatch is the reference's: by the model's class name, the module's type and the depth
+    of its name."""
+    cls, parts = model.__class__.__name__, name.split('.')
+    columns = (lambda w: w.t()), (lambda rows: rows.t().contiguous())
+    if 'VAE' in cls:
+        return columns if isinstance(module, nn.Linear) and len(parts) == 2 and 'embedding' in parts[1] else None
+    if 'PixelCNN' in cls:
+        if isinstance(module, nn.Embedding) and len(parts) >= 3 and 'class_cond_embedding' in parts[2]:
+            return (lambda w: w), (lambda rows: rows.contiguous())
+        return None
+    if 'Glow' in cls:
+        if len(parts) == 4 and 'embedding' in parts[2]:
+            return (lambda w: w.squeeze().t()), (lambda rows: rows.t().unsqueeze(2).unsqueeze(3).contiguous())
+        return None
+    if 'GAN' in cls:
+        return columns if isinstance(module, nn.Linear) and len(parts) >= 2 and 'embedding' in parts[1] else None
+    return None
+
+
 def create(model):
-    """Give every MultimodalController a fresh codebook for the new set of modes
-    (models/utils.py:47-88; the embedding branches only exist in the c* baselines)."""
-    for _, module in model.named_modules():
+    """New modes for cfg['classes_size'] labels (models/utils.py:47-88): every MultimodalController gets a fresh codebook,
+    every label-embedding table of a c* baseline is replaced by Dirichlet mixtures of its rows -- a new nn.Parameter, as the
+    reference installs it, whose mode count the models read from its shape at call time.  The tables are stored contiguous:
+    the gather kernels index them as dense [E, modes] / [modes, 2C]."""
+    for name, module in model.named_modules():
         if _is_mc(module):
             module.register_buffer('codebook', create_codebook(module.codebook))
+            continue
+        table = _embedding_table(model, name, module)
+        if table is not None:
+            to_rows, from_rows = table
+            module.weight = nn.Parameter(from_rows(create_embedding(to_rows(module.weight))))
     return
 
 
@@ -122,18 +177,30 @@ def transit_codebook(codebook, root, alpha):
 
 
 def transit_embedding(embedding, root, alpha):
+    """alpha * e_i + (1 - alpha) * e_root for every mode i, the root's row kept (models/utils.py:91-98)."""
     e = embedding.detach().cpu().numpy()
+    alpha = float(alpha)          # a numpy float64 scalar (transit.py's np.linspace) would promote the float32 table to float64
     root_e = e[root]
     others = alpha * np.delete(e, root, 0) + (1 - alpha) * root_e
     return torch.tensor(np.insert(others, root, root_e, 0), device=cfg['device'])
 
 
 def transit(model, root, alpha):
-    """models/utils.py:112-152 for the MC models: keep the original codebook as
-    `codebook_orig`, install the transited one as the live `codebook`."""
-    for _, module in model.named_modules():
+    """models/utils.py:112-152: keep the original codebook / embedding as `codebook_orig` / `weight_orig`, install the
+    transited one as the live `codebook` / `weight`.  A spectral-normed embedding (CGAN's discriminator) already owns a
+    `weight_orig`, which the reference reuses as the original.  The reference has no PixelCNN branch: MCPixelCNN's codebooks
+    are spliced all the same, ConditionalGatedPixelCNN's tables stay."""
+    pixelcnn = 'PixelCNN' in model.__class__.__name__
+    for name, module in model.named_modules():
         if _is_mc(module):
             if not hasattr(module, 'codebook_orig'):
                 module.register_buffer('codebook_orig', module.codebook.data)
             module.register_buffer('codebook', transit_codebook(module.codebook_orig, root, alpha))
+            continue
+        table = None if pixelcnn else _embedding_table(model, name, module)
+        if table is not None:
+            to_rows, from_rows = table
+            if not hasattr(module, 'weight_orig'):
+                module.register_buffer('weight_orig', module.weight.data)
+            module.weight = nn.Parameter(from_rows(transit_embedding(to_rows(module.weight_orig), root, alpha)))
     return

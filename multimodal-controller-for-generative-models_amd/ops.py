@@ -2010,3 +2010,57 @@ def cglow_prior_bwd(dprior: Tensor, b_p: Tensor, s_p: Tensor, w_e: Tensor, b_e: 
                                             _f32(ws), _f32(db_p), _f32(ds_p), _f32(dw_p), 0 if dw_p is None else dw_p.numel(),
                                             _f32(dw_e), _f32(db_e), _f32(ds_e), _dt(dprior.dtype), n, dprior.numel() // (n * cp),
                                             c2, m, cp, _stream()), 'cglow_prior_bwd')
+
+
+# ---- Davies-Bouldin index (metrics.davies_bouldin) ------------------------------------------------------------------------
+def _i64(t: Tensor, what: str) -> int:
+    if t.dtype != torch.int64:
+        raise _lib.McgenError(f'{what}: expected int64, got {t.dtype}')
+    return _p(t)
+
+
+def _f64(t: Tensor) -> int:
+    if t.dtype != torch.float64:
+        raise _lib.McgenError(f'expected float64, got {t.dtype}')
+    return _p(t)
+
+
+def dbi_centroids(x: Tensor, order: Tensor, offset: Tensor) -> Tensor:
+    """fp64 [K, D]: the mean of the rows of x [N, D] fp32 in each segment offset[k] .. offset[k + 1] of `order` (row ids sorted
+    by cluster).  One launch (mcgen_dbi_centroids)."""
+    n, d = x.shape
+    k = offset.numel() - 1
+    if order.numel() != n or k < 1:
+        raise _lib.McgenError(f'dbi_centroids: {order.numel()} sorted row ids and {k} clusters for {n} rows')
+    cent = torch.empty((k, d), dtype=torch.float64, device=x.device)
+    check(_lib.load().mcgen_dbi_centroids(_f32(x), _i64(order, 'dbi_centroids'), _i64(offset, 'dbi_centroids'), _f64(cent), n, d, k,
+                                          _stream()), 'dbi_centroids')
+    return cent
+
+
+def dbi_spread(x: Tensor, order: Tensor, cluster: Tensor, offset: Tensor, cent: Tensor) -> Tensor:
+    """fp64 [K]: per cluster the mean Euclidean distance of its rows to its centroid.  Two launches (mcgen_dbi_spread)."""
+    n, d = x.shape
+    k = cent.shape[0]
+    if order.numel() != n or cluster.numel() != n or offset.numel() != k + 1 or cent.shape[1] != d:
+        raise _lib.McgenError('dbi_spread: one sorted id and one cluster per row, K + 1 offsets, centroids [K, D]')
+    dist = torch.empty(n, dtype=torch.float64, device=x.device)
+    spread = torch.empty(k, dtype=torch.float64, device=x.device)
+    check(_lib.load().mcgen_dbi_spread(_f32(x), _i64(order, 'dbi_spread'), _i64(cluster, 'dbi_spread'), _i64(offset, 'dbi_spread'),
+                                       _f64(cent), _f64(dist), _f64(spread), n, d, k, _stream()), 'dbi_spread')
+    return spread
+
+
+def dbi_score(cent: Tensor, spread: Tensor) -> Tensor:
+    """fp64 [3] on the device: (mean_k max_l (s_k + s_l) / ||c_k - c_l|| with a zero distance counting as +inf, max_k s_k,
+    max_kl ||c_k - c_l||).  Two launches (mcgen_dbi_score)."""
+    k, d = cent.shape
+    if spread.numel() != k:
+        raise _lib.McgenError(f'dbi_score: {spread.numel()} spreads for {k} centroids')
+    lib = _lib.load()
+    tiles = lib.mcgen_dbi_tiles(k)
+    tile_ratio = torch.empty((k, tiles), dtype=torch.float64, device=cent.device)
+    tile_m = torch.empty_like(tile_ratio)
+    out = torch.empty(3, dtype=torch.float64, device=cent.device)
+    check(lib.mcgen_dbi_score(_f64(cent), _f64(spread), _f64(tile_ratio), _f64(tile_m), _f64(out), d, k, _stream()), 'dbi_score')
+    return out

@@ -46,7 +46,8 @@ def conditional(m) -> bool:
 
 def num_modes(m) -> int:
     if conditional(m):
-        return m.layers[0].class_cond_embedding.num_embeddings
+        from .models.cpixelcnn import table_modes
+        return table_modes(m)            # the live tables' rows: create() replaces them
     return m.output_conv[3].codebook.shape[0]
 
 

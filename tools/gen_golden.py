@@ -1306,6 +1306,95 @@ def fx_cglow_omniglot_small():
 
 FIXTURES.update(cglow_small=fx_cglow_small, cglow_cifar_small=fx_cglow_cifar_small, cglow_omniglot_small=fx_cglow_omniglot_small)
 
+# ---- create / transit on the label-embedding baselines (models/utils.py:47-88, 112-152) and the created set's DBI -------------
+def _surgery_generate(model, name, label, x):
+    """Eval-mode generate of the reference; cpixelcnn: the greedy decode (argmax per position through reference forwards,
+    cpixelcnn.py:100-108 with the draw replaced) and the eval logits of the decoded map."""
+    with torch.no_grad():
+        if name != 'cpixelcnn':
+            return {'gen': model.generate(label, x).numpy()}
+        m = torch.zeros((label.numel(), 8, 8), dtype=torch.long)
+        for i in range(8):
+            for j in range(8):
+                m[:, i, j] = model({'img': m, 'label': label})['logits'][:, :, i, j].argmax(1)
+        return {'greedy': m.numpy(), 'logits': model({'img': m, 'label': label})['logits'].numpy()}
+
+
+def _fx_surgery(name):
+    """The reference's create (10 -> 14 modes, CPU, fixed seed) and transit(root 2, alpha in {0, 0.5, 1}) on the trained state of
+    the model's *_small fixture (tests/surgery_util.base_state): only the tensors each call changes or adds, the state dict's
+    key list after it, the inputs (C, x) and the eval-mode generate outputs.  The reference has no PixelCNN transit."""
+    import models
+    import surgery_util as su
+    base = su.base_state(name)
+
+    def fresh():
+        su.configure(name, 'cpu', cfg)
+        np.random.seed(0)
+        m = getattr(models, name)()
+        m.load_state_dict(base)
+        m.train(False)
+        return m
+
+    arrays = {'create_seed': np.array(su.CREATE_SEED), 'root': np.array(su.ROOT), 'alphas': np.array(su.ALPHAS)}
+    model = fresh()
+    cfg['classes_size'] = su.NEW_MODES
+    torch.manual_seed(su.CREATE_SEED)
+    with torch.no_grad():                                                 # create.py:56 / transit.py:50 call both under no_grad
+        models.utils.create(model)
+    sd = model.state_dict()
+    arrays['create_keys'] = np.array(list(sd))
+    arrays.update(np_state(su.changed(sd, base), 'create/'))
+    label, x = su.inputs(name, su.NEW_MODES)
+    arrays.update({'create_out/' + k: v for k, v in _surgery_generate(model, name, label, x).items()})
+    cfg['classes_size'] = su.MODES
+    if name != 'cpixelcnn':
+        model = fresh()
+        label, x = su.inputs(name, su.MODES)
+        for i, alpha in enumerate(su.ALPHAS):
+            with torch.no_grad():
+                models.utils.transit(model, su.ROOT, alpha)
+            sd = model.state_dict()
+            arrays['transit_keys'] = np.array(list(sd))
+            arrays.update(np_state(su.changed(sd, base), f'transit{i}/'))
+            arrays.update({f'transit{i}_out/' + k: v for k, v in _surgery_generate(model, name, label, x).items()})
+    save(f'surgery_{name}.npz', **arrays)
+
+
+def fx_surgery_cgan():
+    _fx_surgery('cgan')
+
+
+def fx_surgery_cvae():
+    _fx_surgery('cvae')
+
+
+def fx_surgery_cglow():
+    _fx_surgery('cglow')
+
+
+def fx_surgery_cpixelcnn():
+    _fx_surgery('cpixelcnn')
+
+
+def fx_dbi():
+    """scikit-learn's davies_bouldin_score on the three cases of tests/dbi_ref.py (inputs regenerated from their seeds): on the
+    float64 copy, and on the float32 rows themselves -- what the reference's DBI (metrics.py:164-166) computes."""
+    from sklearn.metrics import davies_bouldin_score
+    import dbi_ref
+    arrays = {'cases': np.array(list(dbi_ref.CASES))}
+    for name, (n, d, seed) in dbi_ref.CASES.items():
+        x, label = dbi_ref.make_case(name)
+        arrays[name + '/shape_seed'] = np.array([n, d, seed])
+        arrays[name + '/checksum'] = np.array([float(x.astype(np.float64).sum()), float(label.sum())])
+        arrays[name + '/sklearn_f64'] = np.array(davies_bouldin_score(x.astype(np.float64), label))
+        arrays[name + '/sklearn_f32'] = np.array(davies_bouldin_score(x, label), dtype=np.float64)
+    save('dbi.npz', **arrays)
+
+
+FIXTURES.update(surgery_cgan=fx_surgery_cgan, surgery_cvae=fx_surgery_cvae, surgery_cglow=fx_surgery_cglow,
+                surgery_cpixelcnn=fx_surgery_cpixelcnn, dbi=fx_dbi)
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--only', default=None)
