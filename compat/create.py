@@ -79,9 +79,9 @@ def create(model, ae=None):
                      nrow=save_num_mode, range=(-1, 1))
 
 
-def load_models(extra):
+def load_models_with_epoch(extra):
     """create.py:38-50: seed, dataset (for classes_size), the model and -- for the PixelCNN models -- its VQ-VAE, each
-    from its *_best.pt; -> (model, ae or None, dataset)."""
+    from its *_best.pt; -> (model, ae or None, dataset, the epoch `resume` read for the model: 1 without a checkpoint)."""
     seed = int(cfg['model_tag'].split('_')[0])
     torch.manual_seed(seed)
     torch.cuda.manual_seed(seed)
@@ -94,12 +94,17 @@ def load_models(extra):
         _, ae, _, _, _ = resume(ae, cfg['ae_tag'], load_tag='best')
         ae.train(False)
     model = eval('models.{}().to(cfg["device"])'.format(cfg['model_name']))
-    _, model, _, _, _ = resume(model, cfg['model_tag'], load_tag='best')
+    last_epoch, model, _, _, _ = resume(model, cfg['model_tag'], load_tag='best')
     if cfg.get('compute_dtype') == 'bfloat16':
         for m in (model, ae):
             if m is not None and hasattr(m, 'set_compute_dtype'):
                 m.set_compute_dtype(torch.bfloat16)
-    return model, ae, dataset
+    return model, ae, dataset, last_epoch
+
+
+def load_models(extra):
+    """-> (model, ae or None, dataset): load_models_with_epoch without the epoch."""
+    return load_models_with_epoch(extra)[:3]
 
 
 def main(run_experiment, overrides=None):

@@ -829,6 +829,34 @@ int mcgen_dbi_tiles(int K);
 int mcgen_dbi_score(const double* cent, const double* spread, double* tile_ratio, double* tile_m, double* out, int D, int K,
                     void* stream);
 
+/* ---- Per-batch evaluation metrics on the device (csrc/eval_ops.hip) --------------------------------------------------------
+ * What compat/metrics computes per batch, as reductions that leave one float64 behind (one read of the inputs; mcgen_eval_nll
+ * reads its logits twice, for the maximum and for the exp sum).  Inputs are the eval forwards'
+ * own tensors: contiguous fp32 and int64 targets; they are read as fp32 and all arithmetic (log / exp included) is fp64.
+ * No atomics and a fixed summation order (thread slice, 64-lane shuffle tree, waves in order, then a one-workgroup launch
+ * over the per-workgroup partials in ascending order), with a grid that depends on the element count alone: a repeated call
+ * returns the same bits.  Every entry point ends with  last[slot] = v;  acc[slot] += n * v  for the batch value v and the
+ * batch size n; slot -1 = not wanted.  acc / last: [MCGEN_EVAL_SLOTS] fp64, work: [MCGEN_EVAL_WORK] fp64 (partials), all
+ * owned by the caller; calls that share them must be on one stream.  Two launches each (mcgen_eval_scalar: one). */
+#define MCGEN_EVAL_SLOTS 16
+#define MCGEN_EVAL_GROUPS 256
+#define MCGEN_EVAL_WORK 512
+/* out / tgt: E >= 1 floats each, any 4-byte aligned address.  MSE = sum (o - t)^2 / E;  BCE = the reference's metrics.py:22-27:
+ * both tensors mapped (x + 1) / 2 in fp32, then mean of -(t log o + (1 - t) log(1 - o)) with each log clamped at -100 as
+ * F.binary_cross_entropy does;  PSNR = 20 log10(1 / sqrt(MSE)).  Slots that are not -1 must differ. */
+int mcgen_eval_img(const float* out, const float* tgt, int64_t E, int64_t n, double* work, int slot_mse, int slot_bce,
+                   int slot_psnr, double* acc, double* last, void* stream);
+/* F.cross_entropy(logits [N, K, HW], target [N, HW], 'mean'): the maximum is subtracted before the log-sum-exp.  A target
+ * outside [0, K) makes the value NaN and no logit is read for it. */
+int mcgen_eval_nll(const float* logits, const int64_t* target, int64_t N, int K, int64_t HW, int64_t n, double* work, int slot,
+                   double* acc, double* last, void* stream);
+/* Top-1 accuracy of logits [N, C] in percent: a row is a hit when its first maximum (lowest index on ties) is label[row];
+ * a row holding a NaN is a miss.  A label outside [0, C) makes the value NaN and its row is not read. */
+int mcgen_eval_accuracy(const float* logits, const int64_t* label, int64_t N, int C, int64_t n, double* work, int slot,
+                        double* acc, double* last, void* stream);
+/* v = value[0], an fp32 device scalar (a loss), NaN included. */
+int mcgen_eval_scalar(const float* value, int64_t n, int slot, double* acc, double* last, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2064,3 +2064,74 @@ def dbi_score(cent: Tensor, spread: Tensor) -> Tensor:
     out = torch.empty(3, dtype=torch.float64, device=cent.device)
     check(lib.mcgen_dbi_score(_f64(cent), _f64(spread), _f64(tile_ratio), _f64(tile_m), _f64(out), d, k, _stream()), 'dbi_score')
     return out
+
+
+# ---- per-batch evaluation metrics (evaluate.DeviceEvaluator) ---------------------------------------------------------------
+def _eval_state(work: Optional[Tensor], acc: Tensor, last: Tensor, device, what: str):
+    c = _lib.CONSTANTS
+    for t, size, name in ((work, c['MCGEN_EVAL_WORK'], 'work'), (acc, c['MCGEN_EVAL_SLOTS'], 'acc'), (last, c['MCGEN_EVAL_SLOTS'], 'last')):
+        if t is not None and (t.dtype != torch.float64 or t.dim() != 1 or t.numel() != size or t.device != device):
+            raise _lib.McgenError(f'{what}: Not valid {name}: float64 [{size}] on {device} expected, got {t.dtype} {tuple(t.shape)} on {t.device}')
+
+
+def _eval_slot(slot: int, what: str) -> int:
+    if not -1 <= int(slot) < _lib.CONSTANTS['MCGEN_EVAL_SLOTS']:
+        raise ValueError(f'{what}: Not valid slot: {slot}')
+    return int(slot)
+
+
+def _eval_n(n: int, what: str) -> int:
+    if int(n) < 1:
+        raise ValueError(f'{what}: Not valid batch size: {n}')
+    return int(n)
+
+
+def eval_img(out: Tensor, tgt: Tensor, n: int, work: Tensor, acc: Tensor, last: Tensor, slot_mse: int = -1, slot_bce: int = -1,
+             slot_psnr: int = -1):
+    """MSE, BCE (the reference's, on (x + 1) / 2) and PSNR of two equally shaped fp32 tensors from one pass over both, in
+    fp64: last[slot] = value, acc[slot] += n * value for each slot that is not -1.  Two launches (mcgen_eval_img)."""
+    if out.shape != tgt.shape or out.numel() < 1 or out.device != tgt.device:
+        raise ValueError(f'eval_img: Not valid input: {tuple(out.shape)} on {out.device} against {tuple(tgt.shape)} on {tgt.device}')
+    slots = [_eval_slot(x, 'eval_img') for x in (slot_mse, slot_bce, slot_psnr)]
+    wanted = [x for x in slots if x >= 0]
+    if len(set(wanted)) != len(wanted):
+        raise ValueError(f'eval_img: Not valid slot: two metrics share one of {slots}')
+    po, pt = _f32(out), _f32(tgt)
+    _eval_state(work, acc, last, out.device, 'eval_img')
+    check(_lib.load().mcgen_eval_img(po, pt, out.numel(), _eval_n(n, 'eval_img'), _f64(work), *slots, _f64(acc), _f64(last),
+                                     _stream()), 'eval_img')
+
+
+def eval_nll(logits: Tensor, target: Tensor, n: int, work: Tensor, acc: Tensor, last: Tensor, slot: int):
+    """F.cross_entropy(logits [N, K, ...] fp32, target [N, ...] int64, 'mean') in fp64 -> last[slot], acc[slot] += n * value.
+    Two launches (mcgen_eval_nll)."""
+    if logits.dim() < 2 or target.shape != logits.shape[:1] + logits.shape[2:] or logits.numel() < 1 or logits.device != target.device:
+        raise ValueError(f'eval_nll: Not valid input: logits {tuple(logits.shape)} on {logits.device} against targets '
+                         f'{tuple(target.shape)} on {target.device}')
+    pl, pt = _f32(logits), _i64(target, 'eval_nll')
+    _eval_state(work, acc, last, logits.device, 'eval_nll')
+    nb, k = logits.shape[0], logits.shape[1]
+    check(_lib.load().mcgen_eval_nll(pl, pt, nb, k, logits.numel() // (nb * k), _eval_n(n, 'eval_nll'), _f64(work),
+                                     _eval_slot(slot, 'eval_nll'), _f64(acc), _f64(last), _stream()), 'eval_nll')
+
+
+def eval_accuracy(logits: Tensor, label: Tensor, n: int, work: Tensor, acc: Tensor, last: Tensor, slot: int):
+    """Top-1 accuracy in percent of logits [N, C] fp32 against label [N] int64 (first maximum; a row with a NaN is a miss)
+    -> last[slot], acc[slot] += n * value.  Two launches (mcgen_eval_accuracy)."""
+    if logits.dim() != 2 or label.shape != logits.shape[:1] or logits.numel() < 1 or logits.device != label.device:
+        raise ValueError(f'eval_accuracy: Not valid input: logits {tuple(logits.shape)} on {logits.device} against labels '
+                         f'{tuple(label.shape)} on {label.device}')
+    pl, pt = _f32(logits), _i64(label, 'eval_accuracy')
+    _eval_state(work, acc, last, logits.device, 'eval_accuracy')
+    check(_lib.load().mcgen_eval_accuracy(pl, pt, logits.shape[0], logits.shape[1], _eval_n(n, 'eval_accuracy'), _f64(work),
+                                          _eval_slot(slot, 'eval_accuracy'), _f64(acc), _f64(last), _stream()), 'eval_accuracy')
+
+
+def eval_scalar(value: Tensor, n: int, acc: Tensor, last: Tensor, slot: int):
+    """An fp32 device scalar (a loss) as it is, NaN included -> last[slot], acc[slot] += n * value.  One launch."""
+    if value.numel() != 1:
+        raise ValueError(f'eval_scalar: Not valid input: one value expected, got {tuple(value.shape)}')
+    pv = _f32(value)
+    _eval_state(None, acc, last, value.device, 'eval_scalar')
+    check(_lib.load().mcgen_eval_scalar(pv, _eval_n(n, 'eval_scalar'), _eval_slot(slot, 'eval_scalar'), _f64(acc), _f64(last),
+                                        _stream()), 'eval_scalar')
