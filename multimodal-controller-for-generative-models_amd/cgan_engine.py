@@ -23,7 +23,7 @@ from . import ops
 from ._lib import McgenError
 from .gan_engine import (DiscriminatorEngine, FlatState, Nhwc, _LOWRES_SC_BWD, _SNConv, _bn_forward, _flush_counters,
                          _pending_counters, _pending_running)
-from .ops import Seg
+from .ops import PrepJob, Seg
 
 Tensor = torch.Tensor
 
@@ -89,18 +89,16 @@ class CGeneratorEngine:
             return t
 
         if self._prep_fwd is None or self._prep_fwd.dtype != dt or not self._prep_fwd.valid():
-            jobs = [(lin.weight, buf('lin', ops.weight_image_elems(lin.out_features, lin.in_features, 1), dt), False, 16, -1, 1.0)]
+            jobs = [PrepJob(lin.weight, buf('lin', ops.weight_image_elems(lin.out_features, lin.in_features, 1), dt), row_perm=16)]
             for i, b in enumerate(res):
                 c1, c2, sc, _, _ = self._convs(b)
-                jobs.append((c1.weight, buf(f'b{i}.w1', ops.weight_image_elems(c1.out_channels, c1.in_channels, 3), dt),
-                             False, 1, -1, 1.0))
+                jobs.append(PrepJob(c1.weight, buf(f'b{i}.w1', ops.weight_image_elems(c1.out_channels, c1.in_channels, 3), dt)))
                 n2 = ops.weight_image_elems(c2.out_channels, c2.in_channels, 3)
                 ns = ops.weight_image_elems(sc.out_channels, sc.in_channels, 1)
                 cat = buf(f'b{i}.w2s', n2 + ns, dt)
-                jobs += [(c2.weight, cat[:n2], False, 1, -1, 1.0), (sc.weight, cat[n2:], False, 1, -1, 1.0)]
-            jobs.append((head_conv.weight, buf('head', ops.weight_image_elems(head_conv.out_channels, head_conv.in_channels, 3), dt),
-                         False, 1, -1, 1.0))
-            self._prep_fwd = ops.PrepBatch([(j[0].detach(),) + tuple(j[1:]) for j in jobs], dt)
+                jobs += [PrepJob(c2.weight, cat[:n2]), PrepJob(sc.weight, cat[n2:])]
+            jobs.append(PrepJob(head_conv.weight, buf('head', ops.weight_image_elems(head_conv.out_channels, head_conv.in_channels, 3), dt)))
+            self._prep_fwd = ops.PrepBatch(jobs, dt)
         self._prep_fwd.run()
         buf('lin_bias', lin.out_features, torch.float32).view(16, c0).copy_(lin.bias.detach().view(c0, 16).t())
         self._img_key = key
@@ -115,7 +113,7 @@ class CGeneratorEngine:
             def tbuf(name, w):
                 t = torch.empty(ops.weight_image_elems(w.shape[0], w.shape[1], w.shape[2], True), dtype=dt, device=w.device)
                 self.img_t[name] = t
-                jobs.append((w.detach(), t, True, 1, -1, 1.0))
+                jobs.append(PrepJob(w, t, transpose=True))
             tbuf('head', head_conv.weight)
             for i, b in enumerate(res):
                 c1, c2, sc, _, _ = self._convs(b)
@@ -335,24 +333,24 @@ class CDiscriminatorEngine(DiscriminatorEngine):
             return t[:na], t[na:]
 
         fwd, bwd = [], []
-        W = lambda s: s.m.weight_orig.detach()                                # noqa: E731
+        W = lambda s: s.m.weight_orig                                         # noqa: E731
         c1m, c2m, scm, _ = self._block(0)
-        fwd.append((W(c1m), img('0.c1', c1m, False), False, 1, c1m.idx, 1.0))
+        fwd.append(PrepJob(W(c1m), img('0.c1', c1m, False), False, 1, c1m.idx, 1.0))
         ta, tb = cat('0.c2s', c2m, scm, False)
-        fwd += [(W(c2m), ta, False, 1, c2m.idx, 1.0), (W(scm), tb, False, 1, scm.idx, 1.0)]
-        bwd.append((W(c2m), img('0.c2t', c2m, True), True, 1, c2m.idx, 0.25))
+        fwd += [PrepJob(W(c2m), ta, False, 1, c2m.idx, 1.0), PrepJob(W(scm), tb, False, 1, scm.idx, 1.0)]
+        bwd.append(PrepJob(W(c2m), img('0.c2t', c2m, True), True, 1, c2m.idx, 0.25))
         for i in range(1, len(self.res)):
             c1m, c2m, scm, pooled = self._block(i)
             a = 0.25 if pooled else 1.0
-            fwd.append((W(c1m), img(f'{i}.c1', c1m, False), False, 1, c1m.idx, 1.0))
+            fwd.append(PrepJob(W(c1m), img(f'{i}.c1', c1m, False), False, 1, c1m.idx, 1.0))
             if scm is not None:
                 ta, tb = cat(f'{i}.c2s', c2m, scm, False)
-                fwd += [(W(c2m), ta, False, 1, c2m.idx, 1.0), (W(scm), tb, False, 1, scm.idx, 1.0)]
-                bwd.append((W(scm), img(f'{i}.sct', scm, True), True, 1, scm.idx, a))
+                fwd += [PrepJob(W(c2m), ta, False, 1, c2m.idx, 1.0), PrepJob(W(scm), tb, False, 1, scm.idx, 1.0)]
+                bwd.append(PrepJob(W(scm), img(f'{i}.sct', scm, True), True, 1, scm.idx, a))
             else:
-                fwd.append((W(c2m), img(f'{i}.c2', c2m, False), False, 1, c2m.idx, 1.0))
-            bwd += [(W(c2m), img(f'{i}.c2t', c2m, True), True, 1, c2m.idx, a),
-                    (W(c1m), img(f'{i}.c1t', c1m, True), True, 1, c1m.idx, 1.0)]
+                fwd.append(PrepJob(W(c2m), img(f'{i}.c2', c2m, False), False, 1, c2m.idx, 1.0))
+            bwd += [PrepJob(W(c2m), img(f'{i}.c2t', c2m, True), True, 1, c2m.idx, a),
+                    PrepJob(W(c1m), img(f'{i}.c1t', c1m, True), True, 1, c1m.idx, 1.0)]
         self._prep_fwd, self._prep_bwd = ops.PrepBatch(fwd, dt), ops.PrepBatch(bwd, dt)
         self._prep_all = ops.PrepBatch(fwd + bwd, dt)
         self._bwd_sigma = None
@@ -365,8 +363,8 @@ class CDiscriminatorEngine(DiscriminatorEngine):
         ns = ops.weight_image_elems(scm.cout, self.cimg, 1, True)
         t = torch.empty(n1 + ns, dtype=dt, device=dev)
         self.img['0.dimg'] = t
-        self._prep_dimg = ops.PrepBatch([(self._w_img[0], t[:n1], True, 1, c1m.idx, 1.0),
-                                         (self._w_img[1], t[n1:], True, 1, scm.idx, 0.25)], dt)
+        self._prep_dimg = ops.PrepBatch([PrepJob(self._w_img[0], t[:n1], True, 1, c1m.idx, 1.0),
+                                         PrepJob(self._w_img[1], t[n1:], True, 1, scm.idx, 0.25)], dt)
 
     # ---- forward ---------------------------------------------------------------------------------
     def forward(self, x_nchw, indicator: Optional[Tensor], train: bool, tail_loss: Optional[str] = None,

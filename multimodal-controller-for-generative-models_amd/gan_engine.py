@@ -23,9 +23,10 @@ from typing import Dict, List, Optional
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import gen_plan, ops
+from ._lib import McgenError
 from ._tuning import flag as _flag
-from .ops import Seg
+from .ops import PrepJob, Seg
 
 Tensor = torch.Tensor
 
@@ -171,7 +172,7 @@ class GeneratorEngine:
         self.gen = gen
         self.dtype = dtype
         self.flat_p = FlatState(list(gen.parameters()))
-        self._img_key = None
+        self._img_key = self._plan_key = self._stack_plan = None
         self.img: Dict[str, Tensor] = {}
         self._prep_fwd = self._prep_bwd = None
         lin, res, head_bn, head_mc, head_conv = self._layers()
@@ -188,22 +189,21 @@ class GeneratorEngine:
     # ---- weight images -------------------------------------------------------------------------
     def refresh_images(self, force: bool = False):
         """(Re)build the kernel weight images when a parameter changed (torch version counters;
-        kernels that write parameters bump them, see fused_adam)."""
+        kernels that write parameters bump them, see fused_adam), or when the plan lists other jobs."""
         lin, res, head_bn, head_mc, head_conv = self._layers()
-        ws = [lin.weight, lin.bias, head_conv.weight]
-        for b in res:
-            ws += [b.conv[4].module.weight, b.conv[8].module.weight, b.shortcut[2].module.weight,
-                   b.conv[8].module.bias, b.shortcut[2].module.bias]
-        cbs = ([m.codebook for b in res for m in (b.mc_1, b.mc_2)] + [head_mc.codebook]) if self._pm_enabled() else []
-        pm_key = tuple((c.data_ptr(), tuple(c.shape), c._version) for c in cbs)
-        key = (self.dtype, tuple((w.data_ptr(), w._version) for w in ws), pm_key)
+        plan = self._plan()
+        weights = {'lin': lin.weight, 'head': head_conv.weight}
+        for i, b in enumerate(res):
+            weights.update({f'b{i}.w1': b.conv[4].module.weight, f'b{i}.w2': b.conv[8].module.weight,
+                            f'b{i}.ws': b.shortcut[2].module.weight})
+        ws = list(weights.values()) + [lin.bias] + [m.bias for b in res for m in (b.conv[8].module, b.shortcut[2].module)]
+        # (per-mode jobs read the codebooks' compaction records: a new plan -- create / transit -- makes them stale)
+        key = (self.dtype, tuple((w.data_ptr(), w._version) for w in ws), self._plan_key if plan.pm_enabled else plan.jobs)
         if not force and key == self._img_key:
             return
-        if getattr(self, '_pm_key', None) != pm_key:            # a codebook changed (create / transit): the per-mode jobs are stale
+        if self._img_key is None or key[2] != self._img_key[2]:
             self._prep_fwd = None
-            self._pm_key = pm_key
-        dt = self.dtype
-        dev = lin.weight.device
+        dt, dev = self.dtype, lin.weight.device
         c0 = lin.out_features // 16
 
         def buf(name, numel, dtype):
@@ -215,83 +215,17 @@ class GeneratorEngine:
             return t
 
         if self._prep_fwd is None or self._prep_fwd.dtype != dt or not self._prep_fwd.valid():
-            jobs = [(lin.weight, buf('lin', ops.weight_image_elems(lin.out_features, lin.in_features, 1), dt), False, 16, -1, 1.0)]
-            for i, b in enumerate(res):
-                w1, w2, wsc = b.conv[4].module.weight, b.conv[8].module.weight, b.shortcut[2].module.weight
-                jobs.append((w1, buf(f'b{i}.w1', ops.weight_image_elems(w1.shape[0], w1.shape[1], 3), dt), False, 1, -1, 1.0))
-                n2 = ops.weight_image_elems(w2.shape[0], w2.shape[1], 3)
-                ns = ops.weight_image_elems(wsc.shape[0], wsc.shape[1], 1)
-                cat = buf(f'b{i}.w2s', n2 + ns, dt)
-                jobs.append((w2, cat[:n2], False, 1, -1, 1.0))
-                jobs.append((wsc, cat[n2:], False, 1, -1, 1.0))
-            jobs.append((head_conv.weight, buf('head', ops.weight_image_elems(head_conv.out_channels, head_conv.in_channels, 3), dt),
-                         False, 1, -1, 1.0))
-            if self._gk_enabled():
-                # K-major images of the launches that read compacted activations in the grouped forward-only pass:
-                # conv_b ++ shortcut of every block from 16x16 up, conv_a of every block from 32x32 up
-                for i, b in enumerate(res):
-                    if not self._gk_block(i):
-                        continue
-                    w1, w2, wsc = b.conv[4].module.weight, b.conv[8].module.weight, b.shortcut[2].module.weight
-                    n2 = ops.weight_image_k_elems(w2.shape[0], w2.shape[1], 3)
-                    ns = ops.weight_image_k_elems(wsc.shape[0], wsc.shape[1], 1)
-                    catk = buf(f'b{i}.w2sk', n2 + ns, dt)
-                    jobs.append((w2, catk[:n2], False, 1, -1, 1.0, True))
-                    jobs.append((wsc, catk[n2:], False, 1, -1, 1.0, True))
-                    if i > 0 and self._gk_block(i - 1):
-                        jobs.append((w1, buf(f'b{i}.w1g', ops.weight_image_k_elems(w1.shape[0], w1.shape[1], 3), dt), False, 1, -1, 1.0, True))
-            if self._pm_enabled():
-                # per-mode dense images of the same launches: for every mode m, the chunked image whose input channels are the
-                # mode's active ones in order (PrepBatch kmap = the cidx part of the mode's compaction record), padded with
-                # zero columns to the compacted pitch -- conv_b ++ shortcut as two jobs into one slot, conv_a where x arrives
-                # compacted.  img['b{i}.w2sm'] / ['b{i}.w1m'] hold the M sets back to back.
-                self._pm_maps = {}
-                for i, b in enumerate(res):
-                    if not self._gk_block(i):
-                        continue
-                    w1, w2, wsc = b.conv[4].module.weight, b.conv[8].module.weight, b.shortcut[2].module.weight
-                    cap_h, cm2 = self._cap(b.mc_2), self._mode_maps(b.mc_2)
-                    x_compact = i > 0 and self._gk_block(i - 1)
-                    cap_x, cm1 = (self._cap(b.mc_1), self._mode_maps(b.mc_1)) if x_compact else (None, None)
-                    if cap_h is None or (x_compact and cap_x is None):
-                        continue
-                    modes = b.mc_2.codebook.shape[0]
-                    n2 = ops.weight_image_elems(w2.shape[0], cap_h, 3)
-                    ns = ops.weight_image_elems(wsc.shape[0], cap_x if x_compact else wsc.shape[1], 1)
-                    slot = buf(f'b{i}.w2sm', modes * (n2 + ns), dt).view(modes, n2 + ns)
-                    # output channels in the order their consumer keeps them (mcgen_conv_t.yperm): h by mc_2, y by the next mask
-                    ymc = self._y_mc(i, True)
-                    py = self._mode_perms(ymc) if ymc is not None else None
-                    ph = self._mode_perms(b.mc_2)
-                    for m in range(modes):
-                        ry = None if py is None else py[m]
-                        jobs.append((w2, slot[m, :n2], False, 1, -1, 1.0, False, cm2[m, w2.shape[1]:], cap_h, ry))
-                        if x_compact:
-                            jobs.append((wsc, slot[m, n2:], False, 1, -1, 1.0, False, cm1[m, wsc.shape[1]:], cap_x, ry))
-                        else:
-                            jobs.append((wsc, slot[m, n2:], False, 1, -1, 1.0, False, None, 0, ry))
-                    if x_compact:
-                        n1 = ops.weight_image_elems(w1.shape[0], cap_x, 3)
-                        slot1 = buf(f'b{i}.w1m', modes * n1, dt).view(modes, n1)
-                        for m in range(modes):
-                            jobs.append((w1, slot1[m], False, 1, -1, 1.0, False, cm1[m, w1.shape[1]:], cap_x, ph[m]))
-                # the image head behind a compacting last block (conv_head.hip reads 5 chunks instead of 8)
-                if res and self._y_mc(len(res) - 1, True) is head_mc and f'b{len(res) - 1}.w2sm' in self.img:
-                    cap_o, cmo = self._cap(head_mc), self._mode_maps(head_mc)
-                    modes = head_mc.codebook.shape[0]
-                    nh = ops.weight_image_elems(head_conv.out_channels, cap_o, 3)
-                    sloth = buf('headm', modes * nh, dt).view(modes, nh)
-                    for m in range(modes):
-                        jobs.append((head_conv.weight, sloth[m], False, 1, -1, 1.0, False, cmo[m, head_conv.in_channels:], cap_o))
-            if self._mc_enabled():
-                # K-major images of the blocks whose maps are large enough for a tile to lie inside one image (the
-                # mode-compacted kernel gathers the active channels' rows from them): conv_a, and conv_b ++ shortcut
-                for i, b in enumerate(res):
-                    if not self._mc_block(i):
-                        continue
-                    w1 = b.conv[4].module.weight
-                    jobs.append((w1, buf(f'b{i}.w1k', ops.weight_image_k_elems(w1.shape[0], w1.shape[1], 3), dt), False, 1, -1, 1.0, True))
-            self._prep_fwd = ops.PrepBatch([(j[0].detach(),) + tuple(j[1:]) for j in jobs], dt)
+            imgs = {name: buf(name, numel, dt) for name, numel in plan.buffers}
+            mcs = self._codes.mcs
+            jobs = []
+            for j in plan.jobs:
+                w = weights[j.weight]
+                # (the cidx part of a compaction record starts at column C)
+                kmap = self._mode_maps(mcs[j.kmap[0]])[j.kmap[1], w.shape[1]:] if j.kmap else None
+                rmap = self._mode_perms(mcs[j.rmap[0]])[j.rmap[1]] if j.rmap else None
+                jobs.append(PrepJob(w, imgs[j.buffer][j.offset:j.offset + j.elems], row_perm=j.row_perm, kmajor=j.kmajor,
+                                    kmap=kmap, kcount=j.kcount, rmap=rmap))
+            self._prep_fwd = ops.PrepBatch(jobs, dt)
         self._prep_fwd.run()
         buf('lin_bias', lin.out_features, torch.float32).view(16, c0).copy_(lin.bias.detach().view(c0, 16).t())
         self._img_key = key
@@ -308,7 +242,7 @@ class GeneratorEngine:
                 ks = w.shape[2]
                 t = torch.empty(ops.weight_image_elems(w.shape[0], w.shape[1], ks, True), dtype=dt, device=dev)
                 self.img_t[name] = t
-                jobs.append((w.detach(), t, True, 1, -1, 1.0))
+                jobs.append(PrepJob(w, t, transpose=True))
             tbuf('head', head_conv.weight)
             for i, b in enumerate(res):
                 tbuf(f'b{i}.w1', b.conv[4].module.weight)
@@ -317,142 +251,89 @@ class GeneratorEngine:
             self._prep_bwd = ops.PrepBatch(jobs, dt)
         self._prep_bwd.run()
 
-    # ---- mode-compacted convolutions ---------------------------------------------------------------
-    def _mc_enabled(self) -> bool:
-        return _MC and self.dtype == torch.bfloat16
+    # ---- the plan of the pass ----------------------------------------------------------------------
+    def _plan(self) -> gen_plan.GenPlan:
+        """gen_plan.plan_generator of the current codebooks, dtype and flags (the flags are read here, not at import).
+        Cached; rebuilding reads the compacted pitches on the host (`_cap`), which a capture cannot do."""
+        mcs = self._codes.mcs
+        flags = (_MC, _GK, _PM, _PM_HEAD, _PM_MAX_MODES)
+        key = (tuple((m.codebook.data_ptr(), tuple(m.codebook.shape), m.codebook._version) for m in mcs), self.dtype, flags)
+        if key != self._plan_key:
+            lin, res, head_bn, head_mc, head_conv = self._layers()
+            bf16 = self.dtype == torch.bfloat16
+            # (the pitches matter to compacted passes only: without them no host read)
+            caps = [self._cap(m) if (_GK and bf16) else None for m in mcs]
+            blocks = [(b.conv[4].module.in_channels, b.conv[4].module.out_channels, 8 << i) for i, b in enumerate(res)]
+            self._plan_val = gen_plan.plan_generator((lin.in_features, lin.out_features), blocks,
+                                                     (head_conv.in_channels, head_conv.out_channels), bf16,
+                                                     mcs[0].codebook.shape[0], caps, *flags)
+            self._plan_key = key
+        return self._plan_val
 
-    def _mc_block(self, i: int) -> bool:
-        """Block i's convolutions run at side 8 * 2^i: from 16x16 up a 128- or 256-pixel tile lies inside one image, and
-        the channel counts must suit the kernel (multiples of 8, at least 64 outputs)."""
-        lin, res, head_bn, head_mc, head_conv = self._layers()
-        c1 = res[i].conv[4].module
-        return self._mc_enabled() and (8 << i) >= 16 and c1.out_channels >= 64 and c1.in_channels % 8 == 0 and c1.out_channels % 8 == 0
-
-    # ---- compacted activations in the forward-only grouped pass -------------------------------------
-    def _gk_enabled(self) -> bool:
-        return _GK and self.dtype == torch.bfloat16
-
-    def _gk_block(self, i: int) -> bool:
-        """Block i (convolutions at side 8 * 2^i) can keep its inner activation h compacted: from 16x16 up a tile lies
-        inside one image, and one 256-channel tile holds every output channel."""
-        lin, res, head_bn, head_mc, head_conv = self._layers()
-        c1 = res[i].conv[4].module
-        return (self._gk_enabled() and (8 << i) >= 16 and 64 <= c1.out_channels <= 256 and c1.out_channels % 32 == 0
-                and c1.in_channels % 8 == 0)
-
-    def _pm_enabled(self) -> bool:
-        lin, res, head_bn, head_mc, head_conv = self._layers()
-        return _PM and self._gk_enabled() and res[0].mc_1.codebook.shape[0] <= _PM_MAX_MODES
-
-    def _y_mc(self, i: int, pm: bool):
-        """The MultimodalController that masks block i's OUTPUT in front of its next convolutions, when those read it compacted
-        (the next block's mc_1, or -- per-mode weight sets only -- the image head's), else None."""
-        lin, res, head_bn, head_mc, head_conv = self._layers()
-        if not self._gk_block(i) or self._cap(res[i].mc_2) is None:
-            return None
-        if i + 1 < len(res):
-            nxt = res[i + 1]
-            ok = self._gk_block(i + 1) and self._cap(nxt.mc_2) is not None and self._cap(nxt.mc_1) is not None
-            return nxt.mc_1 if ok else None
-        # what conv_head.hip takes: 32x32 maps, <= 8 output channels, whole 32-channel chunks
-        ok = pm and _PM_HEAD and self._pm_enabled() and (8 << i) == 32 and head_conv.out_channels <= 8 \
-            and head_conv.in_channels % 32 == 0 and self._cap(head_mc) is not None and self._cap(head_mc) >= 64
-        return head_mc if ok else None
-
-    def _pm_need(self):
-        """The MultimodalControllers whose compaction records the grouped pass reads (per-mode weight sets in use)."""
-        lin, res, head_bn, head_mc, head_conv = self._layers()
-        need = []
-        for i, b in enumerate(res):
-            if not self._gk_block(i) or self._cap(b.mc_2) is None:
-                continue
-            need.append(b.mc_2)
-            ymc = self._y_mc(i, 'headm' in self.img)
-            if ymc is not None:
-                need.append(ymc)
-        return need
-
-    def _stacked_maps(self, need):
-        """(records of all modes of all `need` controllers back to back [K * modes, stride], row offsets [K, 1] int32), or None
-        when their record strides differ.  Cached per codebook versions."""
-        tabs = [self._mode_maps(mc) for mc in need]
-        if not tabs or any(t.shape != tabs[0].shape for t in tabs):
-            return None
-        key = tuple((id(mc), mc.codebook.data_ptr(), mc.codebook._version) for mc in need)
-        if getattr(self, '_stack_key', None) != key:
-            if tabs[0].is_cuda and torch.cuda.is_current_stream_capturing():
-                raise McgenError('compacted generator pass: a codebook changed since the last eager pass; call '
-                                 'GeneratorEngine.warm_caps() before capturing')
-            modes = tabs[0].shape[0]
-            self._stack = (torch.cat(tabs, 0).contiguous(),
-                           (torch.arange(len(tabs), dtype=torch.int32, device=tabs[0].device) * modes).view(-1, 1))
-            self._stack_key = key
+    def _stacked_maps(self, plan):
+        """(per-mode records of plan.pm_controllers back to back [K * modes, stride], row offsets [K, 1] int32), or None when
+        there are none or their record strides differ.  Cached per plan."""
+        if self._stack_plan is not plan:
+            tabs = [self._mode_maps(self._codes.mcs[j]) for j in plan.pm_controllers]
+            self._stack = None
+            if tabs and all(t.shape == tabs[0].shape for t in tabs):
+                if tabs[0].is_cuda and torch.cuda.is_current_stream_capturing():
+                    raise McgenError('compacted generator pass: a codebook changed since the last eager pass; call '
+                                     'GeneratorEngine.warm_caps() before capturing')
+                offs = torch.arange(len(tabs), dtype=torch.int32, device=tabs[0].device) * tabs[0].shape[0]
+                self._stack = (torch.cat(tabs, 0).contiguous(), offs.view(-1, 1))
+            self._stack_plan = plan
         return self._stack
 
-    def _gather_cmaps(self, need, wsel):
-        """-> {id(mc): int16 [N, stride]} the per-image compaction records of `need` (ops.mc_cmap of the one-hot samples' codes),
-        gathered from the per-mode records by label in ONE launch (+ one index add)."""
-        st = self._stacked_maps(need)
+    def _gather_cmaps(self, plan, wsel):
+        """-> {controller: int16 [N, stride]} the per-image compaction records of plan.pm_controllers (ops.mc_cmap of the
+        one-hot samples' codes), gathered from the per-mode records by label in ONE launch (+ one index add)."""
+        st, need = self._stacked_maps(plan), plan.pm_controllers
         if st is None:
             return {}
-        table, offs = st
-        idx = (wsel.view(1, -1) + offs).view(-1)
-        rows = table.index_select(0, idx).view(len(need), wsel.numel(), table.shape[1])
-        return {id(mc): rows[k] for k, mc in enumerate(need)}
+        idx = (wsel.view(1, -1) + st[1]).view(-1)
+        rows = st[0].index_select(0, idx).view(len(need), wsel.numel(), st[0].shape[1])
+        return {j: rows[k] for k, j in enumerate(need)}
+
+    def _per_codebook(self, slot, mc, make):
+        """make(codebook), cached per codebook version."""
+        cb = mc.codebook
+        key = (cb.data_ptr(), tuple(cb.shape), cb._version)
+        cache = self.__dict__.setdefault('_cb_cache', {})
+        if cache.get((slot, id(mc)), (None,))[0] != key:
+            cache[slot, id(mc)] = (key, make(cb))
+        return cache[slot, id(mc)][1]
 
     def _mode_perms(self, mc):
         """int16 [modes, C]: per codebook row, its active channels in order, then the others (mcgen_conv_t.yperm /
-        mcgen_prep_t.rmap).  Cached per codebook version."""
-        cb = mc.codebook
-        key = (cb.data_ptr(), tuple(cb.shape), cb._version)
-        cache = self.__dict__.setdefault('_perm_cache', {})
-        if cache.get(id(mc), (None,))[0] != key:
-            perm = torch.argsort((cb == 0).to(torch.int8), dim=1, stable=True).to(torch.int16).contiguous()
-            cache[id(mc)] = (key, perm)
-        return cache[id(mc)][1]
+        mcgen_prep_t.rmap)."""
+        return self._per_codebook('perms', mc, lambda cb: torch.argsort((cb == 0).to(torch.int8), dim=1, stable=True).to(torch.int16).contiguous())
 
     def _mode_maps(self, mc):
         """Compaction records of the codebook's ROWS (ops.mc_cmap: int16 [modes, stride]; the cidx part starts at column C):
-        the map of a one-hot sample is its mode's.  Cached per codebook version."""
-        cb = mc.codebook
-        key = (cb.data_ptr(), tuple(cb.shape), cb._version)
-        cache = self.__dict__.setdefault('_mm_cache', {})
-        if cache.get(id(mc), (None,))[0] != key:
-            cache[id(mc)] = (key, ops.mc_cmap(cb.detach().contiguous()))
-        return cache[id(mc)][1]
+        the map of a one-hot sample is its mode's."""
+        return self._per_codebook('maps', mc, lambda cb: ops.mc_cmap(cb.detach().contiguous()))
 
     def _cap(self, mc):
         """Compacted channel pitch for activations masked by `mc`: the largest number of active channels any mode keeps,
         rounded up to 32 (None when compaction would not pay, or a code is negative).  Read from the codebook on the
-        host once per codebook version (one-hot indicators: a sample's code is one codebook row, modules.py:73)."""
+        host when the plan is built (one-hot indicators: a sample's code is one codebook row, modules.py:73)."""
         cb = mc.codebook
-        key = (cb.data_ptr(), tuple(cb.shape), cb._version)
-        cache = self.__dict__.setdefault('_cap_cache', {})
-        if cache.get(id(mc), (None,))[0] != key:
-            if cb.is_cuda and torch.cuda.is_current_stream_capturing():
-                raise McgenError('compacted generator pass: a codebook changed since the last eager pass; call '
-                                 'GeneratorEngine.warm_caps() before capturing (the compacted pitch is read on the host)')
-            cnt = int((cb != 0).sum(1).max())
-            cap = (cnt + 31) // 32 * 32
-            ok = cap <= cb.shape[1] * 3 // 4 and float(cb.min()) >= 0.0
-            cache[id(mc)] = (key, cap if ok else None)
-        return cache[id(mc)][1]
+        if cb.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise McgenError('compacted generator pass: a codebook changed since the last eager pass; call '
+                             'GeneratorEngine.warm_caps() before capturing (the compacted pitch is read on the host)')
+        cap = (int((cb != 0).sum(1).max()) + 31) // 32 * 32
+        return cap if cap <= cb.shape[1] * 3 // 4 and float(cb.min()) >= 0.0 else None
 
     def warm_caps(self):
-        """Read the compacted pitches of the current codebooks (a host synchronisation): graph capture calls this after it
-        has restored the model state, so that the captured pass finds them cached."""
-        if self._gk_enabled():
-            lin, res, head_bn, head_mc, head_conv = self._layers()
-            for b in res:
-                self._cap(b.mc_1); self._cap(b.mc_2)
-                if self._pm_enabled():
-                    self._mode_maps(b.mc_1); self._mode_maps(b.mc_2)
-            self._cap(head_mc)
-            if self._pm_enabled():
-                self._mode_maps(head_mc); self._mode_perms(head_mc)
-                for b in res:
-                    self._mode_perms(b.mc_1); self._mode_perms(b.mc_2)
-                self._stacked_maps(self._pm_need())
+        """Build the plan of the current codebooks (a host synchronisation) and the per-mode tables it lists: graph capture
+        calls this after it has restored the model state, so that the captured pass finds them cached."""
+        plan, mcs = self._plan(), self._codes.mcs
+        for j in {j.kmap[0] for j in plan.jobs if j.kmap}:
+            self._mode_maps(mcs[j])
+        for j in {j.rmap[0] for j in plan.jobs if j.rmap}:
+            self._mode_perms(mcs[j])
+        self._stacked_maps(plan)
 
     # ---- forward ---------------------------------------------------------------------------------
     def groups_supported(self, n_total: int, groups: int) -> bool:
@@ -507,97 +388,70 @@ class GeneratorEngine:
         ctx['zt'] = zt
         blocks_ctx = []
         codes = self._codes.run_any(indicator)
-        # Forward-only grouped pass: activations between the launches stay COMPACTED -- the producer stores, per image, only
-        # the channels the consumer's MultimodalController keeps (ycmap), the consumer gathers the matching weight rows.
-        gk = groups > 1 and one_hot and self._gk_enabled()
-        # per-mode dense weight sets for the launches that read compacted activations: the mode of an image is its label
+        # The kind of pass (gen_plan): a grouped one-hot pass keeps the activations between its launches COMPACTED -- the
+        # producer stores, per image, only the channels the consumer's MultimodalController keeps, the consumer gathers the
+        # matching weight rows (gk) or, when the indicator carries its labels, reads its mode's own dense image (pm)
+        plan = self._plan()
         hint = getattr(indicator, '_mcgen_onehot', None)
-        pm = gk and self._pm_enabled() and hint is not None and hint[0].shape[0] * hint[1] == n
+        kind = 'plain'
+        if groups > 1 and one_hot:
+            kind = 'pm' if plan.pm_enabled and hint is not None and hint[0].shape[0] * hint[1] == n else 'gk'
+        route = getattr(plan, kind)
         # (walking the images mode by mode -- mcgen_conv_t.order -- measured neutral: 7.249 vs 7.256 ms/step; not used)
-        wsel = None
-        if pm:
+        wsel, cmaps = None, {}
+        if kind == 'pm':
             wsel = hint[2] if len(hint) > 2 and hint[2] is not None else hint[0].to(torch.int32).repeat(hint[1])
-        x_cm = None                                # compaction map / pitch of the block input x when it arrives compacted
-        # one-hot samples: an image's compaction record is its mode's -- one row gather for every map of the pass
-        cmaps = self._gather_cmaps(self._pm_need(), wsel) if pm else {}
-        caps_h = [self._cap(b.mc_2) if (gk and self._gk_block(i)) else None for i, b in enumerate(res)]
-        for i, b in enumerate(res):
+            # one-hot samples: an image's compaction record is its mode's -- one row gather for every map of the pass
+            cmaps = self._gather_cmaps(plan, wsel)
+
+        def compacted(j, cap):                     # (per-image compaction records of controller j, pitch), None: dense
+            return ((cmaps[j] if j in cmaps else ops.mc_cmap(codes[j])), cap) if cap else None
+
+        def seg(x, code, cm, bn=None, gather=False, cmap=None, **kw):
+            """The K segment that reads x through the controller code `code` (behind BatchNorm `bn`): dense, or x compacted
+            with cm = (records, pitch) -- `gather`: by a gk launch, which picks the matching weight rows."""
+            if cm is None:
+                return Seg(x, scale=bn and bn.scale, shift=bn and bn.shift, code=code, group_n=gn if bn else 0, cmap=cmap, **kw)
+            sc, sh = ops.mc_affine(code, cm[0], cm[1], bn and bn.scale, bn and bn.shift, group_n=gn if bn else 0)
+            return Seg(x, scale=sc, shift=sh, group_n=1, **(dict(cmap=cm[0], cw=code.shape[1]) if gather else {}), **kw)
+
+        x_cm = None                                # how the block input x arrives
+        for i, (b, r) in enumerate(zip(res, route.blocks)):
             s = x.shape[1]
             code1, code2 = codes[2 * i], codes[2 * i + 1]
             bn1 = _bn_forward(b.conv[0].module, st, ng * s * s, train, fold, groups)
             fold = 1
-            co = b.conv[4].module.out_channels
-            ci = b.conv[4].module.in_channels
-            cap_h = caps_h[i]                                                            # h of this block, masked by mc_2
-            nxt = res[i + 1] if i + 1 < len(res) else None
-            # the block's output x stays compacted only if the NEXT block reads it compacted in both of its launches
-            # the block's output x stays compacted only if its consumers read it compacted (the next block's two launches; the
-            # image head through its own per-mode images)
-            ymc = self._y_mc(i, pm and 'headm' in self.img) if cap_h is not None else None
-            cap_y = self._cap(ymc) if ymc is not None else None
-            cm_h = (cmaps[id(b.mc_2)] if id(b.mc_2) in cmaps else ops.mc_cmap(code2)) if cap_h else None
-            cm_y = (cmaps[id(ymc)] if id(ymc) in cmaps else ops.mc_cmap(codes[2 * (i + 1)])) if cap_y else None
+            conv_a, conv_b, conv_s = b.conv[4].module, b.conv[8].module, b.shortcut[2].module
+            co = conv_a.out_channels
+            cm_h = compacted(2 * i + 1, r.cap_h)                                         # h of this block, masked by mc_2
+            cm_y = compacted(r.y_ctrl, r.cap_y)                                          # its output, masked by its consumer's
             # ---- conv_a: BN -> ReLU -> Up -> MC1 -> conv3x3 (mcgan.py:15-19)
-            if x_cm is not None:
-                sa, ta = ops.mc_affine(code1, x_cm[0], x_cm[1], bn1.scale, bn1.shift, group_n=gn)
-                if pm and f'b{i}.w1m' in self.img:
-                    # dense K loop over the compacted pitch on the image's mode's own weight image
-                    seg_a = Seg(x, scale=sa, shift=ta, ups=True, relu=True, group_n=1)
-                    h, st_h = ops.conv_fused([seg_a], self.img[f'b{i}.w1m'], co, bias=b.conv[4].module.bias, stats_mode=st_mode,
-                                             cy=cap_h, wsel=wsel, yperm=self._mode_perms(b.mc_2))
-                else:
-                    seg_a = Seg(x, scale=sa, shift=ta, ups=True, relu=True, group_n=1, cmap=x_cm[0], cw=ci)
-                    h, st_h = ops.conv_fused([seg_a], self.img[f'b{i}.w1g'], co, bias=b.conv[4].module.bias, stats_mode=st_mode,
-                                             kmajor=2, ycmap=cm_h, cy=cap_h)
-            else:
-                # large maps: the K loop visits only each sample's active channels (mode-compacted kernel, K-major images)
-                mc = self._mc_block(i) and f'b{i}.w1k' in self.img
-                cm1 = ops.mc_cmap(code1) if mc else None
-                seg_a = Seg(x, scale=bn1.scale, shift=bn1.shift, code=code1, ups=True, relu=True, group_n=gn, cmap=cm1)
-                h, st_h = ops.conv_fused([seg_a], self.img[f'b{i}.w1k' if mc else f'b{i}.w1'], co, bias=b.conv[4].module.bias,
-                                         stats_mode=st_mode, kmajor=int(mc), ycmap=cm_h, cy=cap_h)
+            # (mc: the K loop visits only each sample's active channels -- mode-compacted kernel, K-major image)
+            seg_a = seg(x, code1, x_cm, bn1, r.a.form == 'gk', ops.mc_cmap(code1) if r.a.form == 'mc' else None, ups=True, relu=True)
+            # (pm: a dense K loop on the mode's own image, the output compacted through the image's row order; else by its map)
+            how = dict(wsel=wsel, yperm=self._mode_perms(b.mc_2)) if r.a.form == 'pm' else \
+                dict(kmajor=gen_plan.LAYOUT[r.a.form], ycmap=cm_h[0] if cm_h else None)
+            h, st_h = ops.conv_fused([seg_a], self.img[r.a.image], co, bias=conv_a.bias, stats_mode=st_mode, cy=r.cap_h, **how)
             bn2 = _bn_forward(b.conv[5].module, st_h, ng * 4 * s * s, train, 1, groups)
             # ---- conv_b ++ shortcut: conv3x3(MC2(ReLU(BN(h)))) + conv1x1(MC1(Up(x))) (mcgan.py:20-30,42)
-            if cm_h is not None:
-                sb, tb = ops.mc_affine(code2, cm_h, cap_h, bn2.scale, bn2.shift, group_n=gn)
-                use_pm = pm and f'b{i}.w2sm' in self.img
-                seg_b = Seg(h, scale=sb, shift=tb, relu=True, group_n=1) if use_pm else \
-                    Seg(h, scale=sb, shift=tb, relu=True, group_n=1, cmap=cm_h, cw=co)
-                if x_cm is not None:
-                    ss, ts = ops.mc_affine(code1, x_cm[0], x_cm[1])
-                    seg_s = Seg(x, ksize=1, scale=ss, shift=ts, ups=True, group_n=1) if use_pm else \
-                        Seg(x, ksize=1, scale=ss, shift=ts, ups=True, group_n=1, cmap=x_cm[0], cw=ci)
-                else:
-                    seg_s = Seg(x, ksize=1, code=code1, ups=True)
-                if use_pm:
-                    y, st = ops.conv_fused([seg_b, seg_s], self.img[f'b{i}.w2sm'].view(-1), co, bias=b.conv[8].module.bias,
-                                           bias2=b.shortcut[2].module.bias, stats_mode=st_mode, cy=cap_y, wsel=wsel,
-                                           yperm=self._mode_perms(ymc) if ymc is not None else None)
-                else:
-                    # (the gather pass of a compacted output takes one bias vector)
-                    y, st = ops.conv_fused([seg_b, seg_s], self.img[f'b{i}.w2sk'], co,
-                                           bias=b.conv[8].module.bias.detach() + b.shortcut[2].module.bias.detach(),
-                                           stats_mode=st_mode, kmajor=2, ycmap=cm_y, cy=cap_y)
+            gk = r.b.form == 'gk'
+            segs = [seg(h, code2, cm_h, bn2, gk, relu=True), seg(x, code1, x_cm, None, gk, ksize=1, ups=True)]
+            if gk:
+                # (the gather pass of a compacted output takes one bias vector)
+                how = dict(bias=conv_b.bias.detach() + conv_s.bias.detach(), kmajor=2, ycmap=cm_y[0] if cm_y else None)
             else:
-                # (conv_b ++ 1x1 shortcut stays dense in the mode-compacted form: one-tap K steps cost more than they save)
-                seg_b = Seg(h, scale=bn2.scale, shift=bn2.shift, code=code2, relu=True, group_n=gn)
-                seg_s = Seg(x, ksize=1, code=code1, ups=True)
                 # (the shortcut's own bias rides along as bias2: the sum is formed in fp32 in front of the accumulator)
-                y, st = ops.conv_fused([seg_b, seg_s], self.img[f'b{i}.w2s'], co, bias=b.conv[8].module.bias,
-                                       bias2=b.shortcut[2].module.bias, stats_mode=st_mode)
+                how = dict(bias=conv_b.bias, bias2=conv_s.bias)
+                if r.b.form == 'pm':
+                    how.update(wsel=wsel, yperm=self._mode_perms(self._codes.mcs[r.y_ctrl]) if cm_y else None)
+            y, st = ops.conv_fused(segs, self.img[r.b.image], co, stats_mode=st_mode, cy=r.cap_y, **how)
             blocks_ctx.append(dict(x=x, h=h, code1=code1, code2=code2, bn1=bn1, bn2=bn2))
-            x = y
-            x_cm = (cm_y, cap_y) if cm_y is not None else None
+            x, x_cm = y, cm_y
         s = x.shape[1]
         bnh = _bn_forward(head_bn, st, ng * s * s, train, fold, groups)
         codeh = codes[-1]
-        hw, hsel = self.img['head'], None
-        if x_cm is not None:
-            sh_, th_ = ops.mc_affine(codeh, x_cm[0], x_cm[1], bnh.scale, bnh.shift, group_n=gn)
-            seg_h = Seg(x, scale=sh_, shift=th_, relu=True, group_n=1)
-            hw, hsel = self.img['headm'], wsel
-        else:
-            seg_h = Seg(x, scale=bnh.scale, shift=bnh.shift, code=codeh, relu=True, group_n=gn)
+        seg_h = seg(x, codeh, x_cm, bnh, relu=True)
+        hw, hsel = self.img[route.head], (wsel if x_cm else None)       # 'headm': the head reads its mode's compacted image
         cimg = head_conv.out_channels
         if pair_out is not None:
             if tuple(pair_out.shape) != (2 * n, x.shape[1], x.shape[2], ops.pad8(cimg)) or pair_out.dtype != dt:
@@ -795,33 +649,33 @@ class DiscriminatorEngine:
             return t[:na], t[na:]
 
         fwd, bwd = [], []
-        W = lambda s: s.m.weight_orig.detach()                                # noqa: E731
+        W = lambda s: s.m.weight_orig                                         # noqa: E731
         b0 = self.res[0]
         c1m, c2m, scm = (self.sn_of[b0.conv[0].module], self.sn_of[b0.conv[3].module], self.sn_of[b0.shortcut[0].module])
-        fwd.append((W(c1m), img('0.c1', c1m, False), False, 1, c1m.idx, 1.0))
+        fwd.append(PrepJob(W(c1m), img('0.c1', c1m, False), False, 1, c1m.idx, 1.0))
         if _D0_FUSE:
             ta, tb = cat('0.c2s', c2m, scm, False)                           # conv2 + the 1x1 shortcut: one launch, two K segments
-            fwd += [(W(c2m), ta, False, 1, c2m.idx, 1.0), (W(scm), tb, False, 1, scm.idx, 1.0)]
+            fwd += [PrepJob(W(c2m), ta, False, 1, c2m.idx, 1.0), PrepJob(W(scm), tb, False, 1, scm.idx, 1.0)]
         else:
-            fwd += [(W(scm), img('0.sc', scm, False), False, 1, scm.idx, 1.0),
-                    (W(c2m), img('0.c2', c2m, False), False, 1, c2m.idx, 1.0)]
-        bwd.append((W(c2m), img('0.c2t', c2m, True), True, 1, c2m.idx, 0.25))
+            fwd += [PrepJob(W(scm), img('0.sc', scm, False), False, 1, scm.idx, 1.0),
+                    PrepJob(W(c2m), img('0.c2', c2m, False), False, 1, c2m.idx, 1.0)]
+        bwd.append(PrepJob(W(c2m), img('0.c2t', c2m, True), True, 1, c2m.idx, 0.25))
         ta, tb = cat('0.dimg', c1m, scm, True)
-        bwd += [(W(c1m), ta, True, 1, c1m.idx, 1.0), (W(scm), tb, True, 1, scm.idx, 0.25)]
+        bwd += [PrepJob(W(c1m), ta, True, 1, c1m.idx, 1.0), PrepJob(W(scm), tb, True, 1, scm.idx, 0.25)]
         for i, b in enumerate(self.res[1:], start=1):
             c1m, c2m = self.sn_of[b.conv[2].module], self.sn_of[b.conv[5].module]
             has_sc, pooled = len(b.shortcut) > 0, len(b.conv) == 7
             a = 0.25 if pooled else 1.0
-            fwd.append((W(c1m), img(f'{i}.c1', c1m, False), False, 1, c1m.idx, 1.0))
+            fwd.append(PrepJob(W(c1m), img(f'{i}.c1', c1m, False), False, 1, c1m.idx, 1.0))
             if has_sc:
                 scm = self.sn_of[b.shortcut[1].module]
                 ta, tb = cat(f'{i}.c2s', c2m, scm, False)
-                fwd += [(W(c2m), ta, False, 1, c2m.idx, 1.0), (W(scm), tb, False, 1, scm.idx, 1.0)]
-                bwd.append((W(scm), img(f'{i}.sct', scm, True), True, 1, scm.idx, a))
+                fwd += [PrepJob(W(c2m), ta, False, 1, c2m.idx, 1.0), PrepJob(W(scm), tb, False, 1, scm.idx, 1.0)]
+                bwd.append(PrepJob(W(scm), img(f'{i}.sct', scm, True), True, 1, scm.idx, a))
             else:
-                fwd.append((W(c2m), img(f'{i}.c2', c2m, False), False, 1, c2m.idx, 1.0))
-            bwd += [(W(c2m), img(f'{i}.c2t', c2m, True), True, 1, c2m.idx, a),
-                    (W(c1m), img(f'{i}.c1t', c1m, True), True, 1, c1m.idx, 1.0)]
+                fwd.append(PrepJob(W(c2m), img(f'{i}.c2', c2m, False), False, 1, c2m.idx, 1.0))
+            bwd += [PrepJob(W(c2m), img(f'{i}.c2t', c2m, True), True, 1, c2m.idx, a),
+                    PrepJob(W(c1m), img(f'{i}.c1t', c1m, True), True, 1, c1m.idx, 1.0)]
         self._prep_fwd, self._prep_bwd = ops.PrepBatch(fwd, dt), ops.PrepBatch(bwd, dt)
         # training passes build both sets in ONE launch at the start of the forward (same sigma): the backward pass that
         # follows finds its transposed images ready (`_bwd_sigma` remembers whose they are)

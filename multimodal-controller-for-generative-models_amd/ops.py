@@ -1060,22 +1060,33 @@ def _struct_table(arr, device) -> Tensor:
     return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
 
 
-class PrepBatch:
-    """A fixed list of weight-image jobs (master weight -> persistent image buffer) run as ONE launch.
-    jobs: (weight tensor, image tensor, transpose, row_perm, sigma_idx or -1, wscale)."""
+class PrepJob(NamedTuple):
+    """One weight-image job: master weight `w` -> the persistent buffer `image`."""
+    w: Tensor
+    image: Tensor
+    transpose: bool = False
+    row_perm: int = 1
+    sigma_idx: int = -1                  # index into the sigma vector of PrepBatch.run, or -1
+    wscale: float = 1.0
+    kmajor: bool = False                 # K-major image (mode-compacted launches)
+    kmap: Optional[Tensor] = None        # a mode's compacted image: input channel k <- kmap[k], k < kcount
+    kcount: int = 0
+    rmap: Optional[Tensor] = None        # image row r <- weight row rmap[r] (mcgen_conv_t.yperm)
 
-    def __init__(self, jobs, dtype: torch.dtype):
+
+class PrepBatch:
+    """A fixed list of weight-image jobs run as ONE launch.  A job is a PrepJob; a plain tuple in PrepJob's field order
+    (trailing fields left out take their defaults) is read as one."""
+
+    def __init__(self, jobs: Sequence[PrepJob], dtype: torch.dtype):
         self.dtype = dtype
-        self.jobs = jobs
+        jobs = [PrepJob(*j) for j in jobs]
+        self.jobs = jobs = [j._replace(w=j.w.detach(), kcount=int(j.kcount) if j.kmap is not None else 0) for j in jobs]
         arr = (_lib.Prep * len(jobs))()
-        for d, job in zip(arr, jobs):
-            w, img, transpose, row_perm, sidx, wscale = job[:6]
-            kmajor = bool(job[6]) if len(job) > 6 else False          # K-major image (mode-compacted launches)
-            kmap, kcount = (job[7], int(job[8])) if len(job) > 8 and job[7] is not None else (None, 0)
-            rmap = job[9] if len(job) > 9 else None                   # image row r <- weight row rmap[r] (mcgen_conv_t.yperm)
+        for d, (w, img, transpose, row_perm, sidx, wscale, kmajor, kmap, kcount, rmap) in zip(arr, jobs):
             cout, cin = w.shape[0], w.shape[1]
             ks = w.shape[2] if w.dim() == 4 else 1
-            if kmap is not None:                                      # a mode's compacted image: input channel k <- kmap[k], k < kcount
+            if kmap is not None:
                 assert not kmajor and not transpose and row_perm == 1 and kmap.dtype == torch.int16 and kmap.numel() >= kcount
                 want = weight_image_elems(cout, kcount, ks, False)
             else:
@@ -1089,7 +1100,7 @@ class PrepBatch:
                 assert not kmajor and not transpose and row_perm == 1 and rmap.dtype == torch.int16 and rmap.numel() >= cout and rmap.is_contiguous()
             d.rmap = _p(rmap)
         self.key = tuple((w.data_ptr(), img.data_ptr()) for w, img, *_ in jobs)
-        self.table = _struct_table(arr, jobs[0][0].device)
+        self.table = _struct_table(arr, jobs[0].w.device)
         self.n = len(jobs)
 
     def valid(self) -> bool:

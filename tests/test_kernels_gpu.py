@@ -1679,7 +1679,7 @@ def test_per_mode_weight_sets_match_the_masked_convolution(two_seg, ordered):
 
     def mode_sets(w, ks):
         per = ops.weight_image_elems(w.shape[0], cap, ks)
-        return per, [(w.cuda(), None, False, 1, -1, 1.0, False, cmaps[m, c:], cap) for m in range(modes)]
+        return per, [ops.PrepJob(w.cuda(), None, kmap=cmaps[m, c:], kcount=cap) for m in range(modes)]
     x = _hot(_rnd(g, n, c, h, h))
     w3, b = _rnd(g, co, c, 3, 3) * 0.03, _rnd(g, co)
     code = cb[label]
@@ -1697,9 +1697,9 @@ def test_per_mode_weight_sets_match_the_masked_convolution(two_seg, ordered):
     sets = torch.empty(modes, per, dtype=dtype, device='cuda')
     jobs = []
     for m in range(modes):
-        j = list(jobs3[m]); j[1] = sets[m, :per3]; jobs.append(tuple(j))
+        jobs.append(jobs3[m]._replace(image=sets[m, :per3]))
         if two_seg:
-            j = list(jobs1[m]); j[1] = sets[m, per3:]; jobs.append(tuple(j))
+            jobs.append(jobs1[m]._replace(image=sets[m, per3:]))
     ops.PrepBatch(jobs, dtype).run()
     lab32 = label.to(torch.int32).cuda()
     if ordered:
@@ -1765,9 +1765,9 @@ def test_permuted_weight_rows_store_the_compacted_output(two_seg):
         jobs = []
         for m in range(modes):
             r = perm2[m] if rows else None
-            jobs.append((w3.cuda(), sets[m, :per3], False, 1, -1, 1.0, False, cmaps[m, c:], cap, r))
+            jobs.append(ops.PrepJob(w3.cuda(), sets[m, :per3], kmap=cmaps[m, c:], kcount=cap, rmap=r))
             if two_seg:
-                jobs.append((w1.cuda(), sets[m, per3:], False, 1, -1, 1.0, False, cmaps[m, c:], cap, r))
+                jobs.append(ops.PrepJob(w1.cuda(), sets[m, per3:], kmap=cmaps[m, c:], kcount=cap, rmap=r))
         ops.PrepBatch(jobs, dtype).run()
         return sets
     lab32 = label.to(torch.int32).cuda()

@@ -503,7 +503,7 @@ def test_mode_compacted_generator_matches_dense():
     np.testing.assert_allclose(l_c, d['losses'][0], rtol=0, atol=5e-2)
 
 
-@pytest.mark.parametrize('cfg_name', ['cifar10', 'coil100'])
+@pytest.mark.parametrize('cfg_name', ['cifar10', 'coil100', 'w64', 'w128'])
 def test_compacted_grouped_pass_matches_dense(cfg_name):
     """MCGEN_GK: in the forward-only 5 N generator pass the activations h_1, x_2 and h_2 stay compacted between launches
     (producer stores only the channels the consumer's MultimodalController keeps, the consumer gathers the matching
@@ -511,16 +511,34 @@ def test_compacted_grouped_pass_matches_dense(cfg_name):
     grouped pass on the same state / latents, bf16 at N = 5 x 128, full width: same images to a bf16 rounding step,
     same BatchNorm running statistics, one train iteration inside the bf16 loss bound of the B = 128 digest.
     COIL100 widths (G [512,256,128,64]: channel counts change from block to block and only some masks are worth
-    compacting): the chain must fall back block by block -- same checks against the dense pass."""
+    compacting): the chain must fall back block by block -- same checks against the dense pass.
+    w64 / w128 (G [64] * 4 / [128] * 4, D [16] * 4, 10 modes): the narrowest generators that compact at all, with codebooks
+    of exactly 32 / 64 active channels per mode (pitch 32 / 64: at 64 the hinted pass takes the per-mode weight sets and the
+    image head reads compacted input too, at 32 it keeps the gathered-K form and a dense head), at N = 5 x 64 -- 64 is the smallest per-group batch for which groups_supported(5 N, 5) holds at these
+    widths (the Linear layer's and the 4x4 maps' tiles hold 64 images).
+    Every run's ops.FORM_LOG is the weight-layout sequence the engine's plan (gen_plan) gives for that kind of pass."""
     from mcgen_amd import gan_engine as GE, trainer as T, ops
+    nb = 128
     if cfg_name == 'cifar10':
         gh, dh, modes, data, kw = [256] * 4, [128] * 4, 10, 'CIFAR10', {}
-    else:
+    elif cfg_name == 'coil100':
         gh, dh, modes, data, kw = [512, 256, 128, 64], [64, 128, 256, 512], 100, 'COIL100', {'cifar_layout': False}
+    else:
+        width = int(cfg_name[1:])
+        gh, dh, modes, data, kw, nb = [width] * 4, [16] * 4, 10, 'CIFAR10', {}, 64
     sd = gu.procedural_state(gu.mcgan_shapes(gh, dh, modes, **kw), seed=1234, num_mode=modes)
-    img, lab = gu.synthetic_batch(128, modes, seed=1)
+    if cfg_name in ('w64', 'w128'):
+        g = torch.Generator().manual_seed(64)
+        books = {}                                   # (aliased keys of one MultimodalController share their table)
+        for k in sorted(sd):
+            if k.startswith('generator.') and k.endswith('codebook'):
+                owner = gu._codebook_owner(k)
+                if owner not in books:               # exactly width / 2 ones per row, at random places
+                    books[owner] = (torch.rand(sd[k].shape, generator=g).argsort(1) < gh[0] // 2).float()
+                sd[k] = books[owner]
+    img, lab = gu.synthetic_batch(nb, modes, seed=1)
     img, lab = img.cuda(), lab.cuda()
-    zs = [z.cuda() for z in gu.latent_batches(6, 128, 128, seed=2)]
+    zs = [z.cuda() for z in gu.latent_batches(6, nb, 128, seed=2)]
 
     def run(gk, hinted=False):
         old = GE._GK
@@ -529,7 +547,7 @@ def test_compacted_grouped_pass_matches_dense(cfg_name):
             m = _build(gh, dh, modes, data, sd, torch.bfloat16)
             m.train(True)
             tr = T.GANTrainer(m, modes)
-            assert tr.fake_groups(128) == 5
+            assert tr.fake_groups(nb) == 5 and (nb == 128 or not any(tr.geng.groups_supported(5 * k, 5) for k in range(1, nb)))
             ops.FORM_LOG = []
             ind = torch.nn.functional.one_hot(lab, modes).float()
             # `hinted`: the indicator as the trainer builds it (one launch, carrying its labels): <= 16 modes then take the
@@ -537,6 +555,8 @@ def test_compacted_grouped_pass_matches_dense(cfg_name):
             ind5 = tr.indicators(lab, 5)[2] if hinted else ind.repeat(5, 1)
             fakes = tr.g_fakes(ind5, torch.cat(zs[:5]), 5)
             tiles = list(ops.FORM_LOG); ops.FORM_LOG = None
+            plan = tr.geng._plan()
+            assert tiles == (plan.pm if hinted else plan.gk).layouts(), (gk, hinted, tiles)
             bn = {k: v.detach().float().cpu().clone() for k, v in m.state_dict().items()
                   if 'generator' in k and 'running' in k}
             m.load_state_dict(sd)
@@ -558,7 +578,8 @@ def test_compacted_grouped_pass_matches_dense(cfg_name):
         np.testing.assert_allclose(l_c, d['losses'][0], rtol=0, atol=5e-2)
     # the trainer's own indicator: per-mode weight sets on CIFAR-10 (10 modes), the gathered-K form on COIL100 (100 modes)
     f_p, bn_p, l_p, t_p = run(True, hinted=True)
-    if cfg_name == 'cifar10':
+    # (w64: a per-mode launch takes a 3x3 K segment of at least 64 channels, so pitch 32 stays with the gathered-K form)
+    if cfg_name in ('cifar10', 'w128'):
         assert t_p.count(2) == 0, t_p                # dense K loops over the compacted pitch: no gathered-K launch left
     else:
         assert t_p.count(2) >= 1, t_p

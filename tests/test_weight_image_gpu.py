@@ -307,7 +307,7 @@ def _prep_batch(jobs, dt):
         wd, km, rm = dev(w), dev(kmap), dev(rmap)
         keep += [wd, km, rm]
         imgs.append(img)
-        table.append((wd, img, transpose, row_perm, sidx, wscale, kmajor, km, kcount, rm))
+        table.append(ops.PrepJob(wd, img, transpose, row_perm, sidx, wscale, kmajor, km, kcount, rm))
     return ops.PrepBatch(table, dt), imgs, keep
 
 
