@@ -11,10 +11,13 @@ What differs, and why:
   * `--engine fused` (default) runs the loop body as `GraphedGANTrainer` (fused Adam, HIP-graph replay);
     `--engine autograd` runs the reference's own Python loop on the nn.Module surface with torch.optim.Adam;
   * --world_size > 1 means one process per GPU under torch.distributed.run (RCCL), not nn.DataParallel;
-  * test() generates `generate_per_mode` images per class (train_gan.py:197-207) and logs the pixel statistics of the
-    generated set under 'test/GeneratedMean', 'test/GeneratedStd' -- a STAND-IN, named as such in its log line: the
-    Inception-based IS / FID of train_gan.py:208-216 need downloaded inception_v3 weights (`metrics.Metric` raises for them
-    on CIFAR-10; on COIL100 / Omniglot it evaluates them through the reference's small classifier);
+  * test() generates `generate_per_mode` images per class (train_gan.py:197-207).  On COIL100 / Omniglot, with the trained
+    feature classifier at ./metrics_tf/res/classifier/ (where the reference keeps it; compat/train_classifier.py writes it),
+    it logs 'test/InceptionScore' and 'test/FID' from `mcgen_amd.metrics.GanScorer` (streaming float64 accumulators on the
+    device, csrc/score_ops.hip) and the checkpoint is copied to <model_tag>_best.pt whenever the InceptionScore improves
+    (train_gan.py:29-31,119-122).  Otherwise -- CIFAR-10, whose IS / FID need downloaded inception_v3 weights, or a missing
+    classifier file -- it logs the pixel statistics of the generated set under 'test/GeneratedMean', 'test/GeneratedStd': a
+    STAND-IN, named as such in its log line, with no pivot (the `cgan` baseline's latest checkpoint is then its best);
   * the checkpoint is the reference's dict INCLUDING `scheduler_dict` (torch MultiStepLR state, train_gan.py:239-240) and the
     pickled `logger.Logger`, so `--resume_mode 1` of the reference's own driver can read a file written here.
 """
@@ -129,13 +132,40 @@ def train_autograd(loader, model, optimizer, epoch):
     return last
 
 
-def test(model, per_mode, logger, epoch):
-    """train_gan.py:197-220: generate_per_mode images per class in eval mode, evaluate, log.  The metric logged here is
-    a STAND-IN (pixel mean / std of the generated set): see the module docstring."""
+def make_scorer(dataset):
+    """The epoch's IS / FID scorer (train_gan.py:208-216 through metrics.py:44-161), or None where only the stand-in can be
+    logged: a dataset the reference scores with inception_v3, or no trained classifier at the reference's location."""
+    from mcgen_amd.data import normalize_uint8
+    from mcgen_amd.metrics import GanScorer, classifier_checkpoint_path
+    if cfg['data_name'] not in ('COIL100', 'Omniglot') or not os.path.exists(classifier_checkpoint_path(cfg['data_name'], cfg['subset'])):
+        return None
+    real = (normalize_uint8(part).contiguous() for part in dataset['train'].img.split(512))
+    return GanScorer(cfg['data_name'], real, subset=cfg['subset'], device=cfg['device'])
+
+
+def pivot_update(pivot, value):
+    """train_gan.py:119-122: (the new pivot, whether the checkpoint becomes _best.pt).  InceptionScore is maximised, the
+    comparison is strict and starts from -inf, so the first epoch always copies and a tie keeps the earlier epoch."""
+    return (value, True) if pivot < value else (pivot, False)
+
+
+def test(model, per_mode, logger, epoch, scorer=None):
+    """train_gan.py:197-220: generate_per_mode images per class in eval mode, evaluate, log.  With a scorer the metrics
+    are InceptionScore and FID, fed chunk by chunk; without one a STAND-IN (pixel mean / std of the generated set): see
+    the module docstring."""
     model.train(False)
+    C = torch.arange(cfg['classes_size'], device=cfg['device']).repeat(per_mode)
+    chunks = C.split(min(500, C.numel()))
+    if scorer is not None:
+        with torch.no_grad():
+            evaluation = scorer.score(model.generate(c) for c in chunks)       # consumed chunk by chunk, never concatenated
+        model.train(True)
+        logger.append(evaluation, 'test')
+        logger.append({'info': ['Model: {}'.format(cfg['model_tag']), 'Test Epoch: {}({:.0f}%)'.format(epoch, 100.)]}, 'test', mean=False)
+        logger.write('test', cfg['metric_name']['test'])
+        return dict(evaluation, n=int(C.numel()))
     with torch.no_grad():
-        C = torch.arange(cfg['classes_size'], device=cfg['device']).repeat(per_mode)
-        outs = [model.generate(c) for c in C.split(min(500, C.numel()))]
+        outs = [model.generate(c) for c in chunks]
         generated = (torch.cat(outs) + 1) / 2 * 255
     model.train(True)
     stats = {'GeneratedMean': float(generated.mean()), 'GeneratedStd': float(generated.std())}
@@ -158,6 +188,8 @@ def run():
     seed = int(cfg['init_seed'])
     torch.manual_seed(seed); torch.cuda.manual_seed(seed)    # train_gan.py:54-55
     cfg['iter'] = {'generator': 1, 'discriminator': 5}       # train_gan.py:30-31
+    cfg['pivot_metric'], cfg['pivot'] = 'InceptionScore', -float('inf')                                  # train_gan.py:29-31
+    cfg['metric_name'] = {'train': ['Loss', 'Loss_D', 'Loss_G'], 'test': ['InceptionScore', 'FID']}
     cfg['model_tag'] = model_tag(seed)
     print(f'Experiment: {cfg["model_tag"]}')
     data_shim._SYNTHETIC['train'] = extra['synthetic_size']
@@ -193,6 +225,7 @@ def run():
     if logger is None:
         logger = Logger(os.path.join(extra['output_dir'], 'runs', 'train_{}_{}'.format(cfg['model_tag'], time.strftime('%b%d_%H-%M-%S'))))
     per_mode = extra['generate_per_mode'] or cfg['generate_per_mode']
+    scorer = make_scorer(dataset)
     for epoch in range(last_epoch, int(cfg['num_epochs']) + 1):
         t0 = time.time()
         logger.safe(True)
@@ -213,15 +246,18 @@ def run():
                                 '{:.0f} images/s'.format(rate)]}, 'train', mean=False)
         if rank == 0:
             logger.write('train', ['Loss', 'Loss_D', 'Loss_G'])
-        test(model, per_mode, logger, epoch)
+        test(model, per_mode, logger, epoch, scorer)
         for sch in scheduler.values():                                         # train_gan.py:105-106
             sch.step()
         logger.safe(False)
         if rank == 0:
             save(make_checkpoint(model, optimizer, epoch + 1, cfg, scheduler=scheduler, logger=logger), path)   # train_gan.py:111-119
-            if cfg['model_name'] == 'cgan':
-                # train_gan.py:120-123 copies the checkpoint to _best.pt when the pivot metric improves; the stand-in metric
-                # has no pivot, so the baseline's latest checkpoint is its best (what compat/generate.py reads)
+            if scorer is not None:                                             # train_gan.py:119-122
+                cfg['pivot'], best = pivot_update(cfg['pivot'], logger.mean['test/{}'.format(cfg['pivot_metric'])])
+                if best:
+                    shutil.copy(path, path[:-len('_checkpoint.pt')] + '_best.pt')
+            elif cfg['model_name'] == 'cgan':
+                # the stand-in metric has no pivot, so the baseline's latest checkpoint is its best (what compat/generate.py reads)
                 shutil.copy(path, path[:-len('_checkpoint.pt')] + '_best.pt')
         logger.reset()
     logger.safe(False)

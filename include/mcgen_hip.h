@@ -857,6 +857,26 @@ int mcgen_eval_accuracy(const float* logits, const int64_t* label, int64_t N, in
 /* v = value[0], an fp32 device scalar (a loss), NaN included. */
 int mcgen_eval_scalar(const float* value, int64_t n, int slot, double* acc, double* last, void* stream);
 
+/* ---- Streaming accumulators of Inception Score and FID (csrc/score_ops.hip) ------------------------------------------------
+ * What the reference's metrics.py:44-161 takes from one concatenated matrix, as sums that every batch adds to.  Inputs are
+ * contiguous fp32, read once per pass and widened; every sum, exp and log is fp64.  No atomics, and each reduction has an
+ * order that depends on the shapes alone, so a repeated call returns the same bits.  The accumulators (zeroed by the caller
+ * before the first call) and `work` are owned by the caller; calls that share them must be on one stream.  `work` holds
+ * mcgen_score_probs_work(n, C) / mcgen_score_moments_work(n, D) doubles at least (0 for sizes the call would refuse); its
+ * contents mean nothing between calls.
+ * mcgen_score_probs: logits [n, C], n >= 1, 2 <= C <= 65535.  Per row p = softmax(logits) with the row maximum subtracted
+ * first;  psum[c] += sum_rows p[row, c]  (psum [C]);  plogp[0] += sum_rows sum_c p log p, log p taken as x - max - log Z,
+ * and 0 log 0 = 0 (a p that underflows, a logit of -inf).  A row holding a NaN -- or nothing but -inf, or a +inf -- makes
+ * every psum[c] and plogp[0] NaN.  Two launches. */
+int64_t mcgen_score_probs_work(int64_t n, int C);
+int mcgen_score_probs(const float* logits, int64_t n, int C, double* work, double* psum, double* plogp, void* stream);
+/* mcgen_score_moments: feat [n, D], n >= 1, 1 <= D <= 65535.  fsum[j] += sum_r x[r, j]  (fsum [D]);
+ * gram[i, j] += sum_r x[r, i] x[r, j]  (gram [D, D]): raw second moments, an fp64 rank-n update on v_mfma_f64_16x16x4_f64
+ * with the rows taken in ascending order by the one workgroup that owns the 64 x 64 tile, added at (i, j) and at (j, i):
+ * gram is bitwise symmetric after any number of calls.  Three launches. */
+int64_t mcgen_score_moments_work(int64_t n, int D);
+int mcgen_score_moments(const float* feat, int64_t n, int D, double* work, double* fsum, double* gram, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

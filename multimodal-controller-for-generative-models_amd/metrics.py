@@ -124,6 +124,123 @@ def fid(img: torch.Tensor, data_name: str, real=None, model=None, batch_size: in
         return fid_from_features(_REAL_CACHE[key][1], f(img))
 
 
+# ---- streaming IS / FID: what train_gan.py:197-220 asks for after every epoch ----------------------------------------
+class ScoreAccumulator:
+    """The statistics behind IS and FID as float64 sums on the device that every batch adds to (csrc/score_ops.hip):
+    psum [C] = column sums of softmax(logits), plogp [1] = sum p log p, fsum [D] = column sums of the features,
+    gram [D, D] = their raw second moments.  Nothing is concatenated and `add` never synchronises with the host; the
+    sums have a fixed order, so the same batches in the same order give the same bits."""
+
+    def __init__(self, classes: int, feature_size: int, device):
+        self.classes, self.feature_size = int(classes), int(feature_size)
+        f64 = dict(dtype=torch.float64, device=device)
+        self.psum, self.plogp = torch.zeros(self.classes, **f64), torch.zeros(1, **f64)
+        self.fsum, self.gram = torch.zeros(self.feature_size, **f64), torch.zeros(self.feature_size, self.feature_size, **f64)
+        self._work = torch.empty(0, **f64)
+        self.count = 0
+
+    def reset(self):
+        for t in (self.psum, self.plogp, self.fsum, self.gram):
+            t.zero_()
+        self.count = 0
+
+    def add(self, logits: torch.Tensor, feature: torch.Tensor):
+        """logits [n, classes] and feature [n, feature_size] of the same n images, contiguous float32 on the device."""
+        from . import ops
+        if logits.dim() != 2 or feature.dim() != 2 or logits.shape[0] != feature.shape[0]:
+            raise ValueError(f'Not valid input: logits {tuple(logits.shape)} and features {tuple(feature.shape)} of one batch expected')
+        n = logits.shape[0]
+        need = max(ops.score_probs_work(n, logits.shape[1]), ops.score_moments_work(n, feature.shape[1]))
+        if self._work.numel() < need:                      # both calls are on one stream, so they can share it
+            self._work = torch.empty(need, dtype=torch.float64, device=self.psum.device)
+        ops.score_probs(logits, self._work, self.psum, self.plogp)
+        ops.score_moments(feature, self._work, self.fsum, self.gram)
+        self.count += n
+
+    def _need(self, least: int):
+        if self.count < least:
+            raise ValueError(f'Not valid count: {self.count} samples accumulated, at least {least} needed')
+
+    def inception_score_tensor(self) -> torch.Tensor:
+        """exp(mean_n KL(p(y|x_n) || p(y))) = exp(plogp / N - sum_c py_c log py_c), py = psum / N: the reference's
+        F.kl_div(py.log(), p, 'batchmean').exp() at splits = 1 (metrics.py:75-82 as train_gan.py calls it); float64, on the device."""
+        self._need(1)
+        py = self.psum / self.count
+        cross = torch.where(py > 0, py * py.clamp_min(1e-300).log(), py).sum()      # (a NaN py stays a NaN)
+        return (self.plogp[0] / self.count - cross).exp()
+
+    def inception_score(self) -> float:
+        return float(self.inception_score_tensor())
+
+    def moments(self):
+        """(N, mu [D], cov [D, D]) in float64 on the device; cov = (gram - fsum fsum^T / N) / (N - 1) is np.cov(rowvar=False)."""
+        self._need(2)
+        n = self.count
+        return n, self.fsum / n, (self.gram - torch.outer(self.fsum, self.fsum) / n) / (n - 1)
+
+
+def _fid_tensor(mu1, s1, mu2, s2, sqrt_s1=None) -> torch.Tensor:
+    r1 = _sqrt_psd(s1) if sqrt_s1 is None else sqrt_s1
+    m = r1 @ s2 @ r1
+    tr_covmean = torch.linalg.eigvalsh((m + m.t()) * 0.5).clamp_min(0).sqrt().sum()
+    diff = mu1 - mu2
+    return diff @ diff + torch.trace(s1) + torch.trace(s2) - 2 * tr_covmean
+
+
+def fid_from_moments(mu1, s1, mu2, s2, sqrt_s1=None) -> float:
+    """The tail of fid_from_features from means and covariances (float64): |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr sqrt(S1 S2).
+    `sqrt_s1` = _sqrt_psd(s1) when the caller has kept it (the real side does not change between epochs)."""
+    return float(_fid_tensor(mu1, s1, mu2, s2, sqrt_s1))
+
+
+class GanScorer:
+    """InceptionScore and FID of a generated set as train_gan.py:197-220 computes them after every epoch, on COIL100 /
+    Omniglot: the reference's small classifier (`feature_network`, which raises where it raises) run once per image for
+    both metrics (`Classifier.score_outputs`), its outputs folded into a `ScoreAccumulator`.  The real set -- a tensor of
+    images in (-1, 1), or an iterable of such tensors or of collated batches {'img': ...} -- goes through the same
+    accumulator once, at construction; its mean, covariance and the covariance's square root are kept."""
+
+    def __init__(self, data_name: str, real, subset: str | None = 'label', checkpoint: str | None = None, batch_size: int = 512,
+                 device=None):
+        if device is None:
+            device = real.device if torch.is_tensor(real) else 'cuda'
+        self.model = feature_network(data_name, checkpoint=checkpoint, device=device, subset=subset)
+        self.batch_size = int(batch_size)
+        head = self.model.classifier
+        self.acc = ScoreAccumulator(head.out_features, head.in_features, device)
+        self.real_passes = 0
+        self._real = None
+        self._real_moments(real)
+
+    def _feed(self, chunks):
+        dev = self.acc.psum.device
+        with torch.no_grad():
+            for chunk in ([chunks] if torch.is_tensor(chunks) else chunks):
+                img = chunk['img'] if isinstance(chunk, dict) else chunk
+                for x in img.to(dev).split(self.batch_size):
+                    self.acc.add(*self.model.score_outputs({'img': x}))
+
+    def _real_moments(self, real):
+        self.acc.reset()
+        self._feed(real)
+        _, mu, cov = self.acc.moments()
+        self._real = (mu, cov, _sqrt_psd(cov))
+        self.real_passes += 1
+        self.acc.reset()
+
+    def score(self, chunks) -> dict:
+        """chunks: an iterable of image tensors [n_i, C, H, W] in (-1, 1) (a generator is consumed as it goes: the set is
+        never concatenated).  -> {'InceptionScore', 'FID'}; the one device-to-host transfer is the pair of results."""
+        self.acc.reset()
+        self._feed(chunks)
+        _, mu2, s2 = self.acc.moments()
+        mu1, s1, r1 = self._real
+        both = torch.stack([self.acc.inception_score_tensor(), _fid_tensor(mu1, s1, mu2, s2, r1)])
+        self.acc.reset()
+        score, distance = both.tolist()
+        return {'InceptionScore': score, 'FID': distance}
+
+
 # ---- Davies-Bouldin index (metrics.py:164-166 DBI) -------------------------------------------------------------------
 def davies_bouldin(img: torch.Tensor, label: torch.Tensor) -> float:
     """scikit-learn's davies_bouldin_score on the flattened images, computed on the device: img [N, ...] float32, label [N]

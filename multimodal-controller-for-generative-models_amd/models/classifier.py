@@ -94,6 +94,12 @@ class Classifier(FusedNet):
                 ce, logits = eng.forward(input['img'], input['label'], True)
             return {'label': logits, 'loss': ce}
         y = self._encode(input['img'])                        # [N, h, w, Cp]
+        output = {'label': self._head(y)}
+        output['loss'] = loss(input, output) if 'label' in input else torch.zeros((), device=y.device)
+        return output
+
+    def _head(self, y: torch.Tensor) -> torch.Tensor:
+        """The Linear head on the NHWC map of `_encode` -> logits fp32 [N, classes]."""
         n, h, w, cp = y.shape
         c = self.encoded_shape[0]
         lin = self.classifier
@@ -104,9 +110,13 @@ class Classifier(FusedNet):
         wt = wt.reshape(lin.out_features, h * w * cp, 1, 1).contiguous()
         logits, _ = ops.conv_fused([Seg(y.view(n, 1, 1, h * w * cp), ksize=1)], ops.prep_weight(wt, y.dtype), lin.out_features,
                                    bias=lin.bias.detach())
-        output = {'label': ops.to_nchw(logits, lin.out_features).reshape(n, lin.out_features)}
-        output['loss'] = loss(input, output) if 'label' in input else torch.zeros((), device=y.device)
-        return output
+        return ops.to_nchw(logits, lin.out_features).reshape(n, lin.out_features)
+
+    def score_outputs(self, input):
+        """What IS and FID take from one image batch, from ONE eval-mode pass through the convolutions:
+        (logits [N, classes] fp32 as `forward` gives them, feature [N, c * h * w] fp32 as `feature` gives them)."""
+        y = self._encode(input['img'])
+        return self._head(y).float().contiguous(), ops.to_nchw(y, self.encoded_shape[0]).reshape(y.shape[0], -1).float().contiguous()
 
 
 def classifier():

@@ -2146,3 +2146,58 @@ def eval_scalar(value: Tensor, n: int, acc: Tensor, last: Tensor, slot: int):
     _eval_state(None, acc, last, value.device, 'eval_scalar')
     check(_lib.load().mcgen_eval_scalar(pv, _eval_n(n, 'eval_scalar'), _eval_slot(slot, 'eval_scalar'), _f64(acc), _f64(last),
                                         _stream()), 'eval_scalar')
+
+
+# ---- streaming IS / FID accumulators (metrics.ScoreAccumulator) --------------------------------------------------------------
+def _score_input(x: Tensor, what: str, least: int) -> Tuple[int, int]:
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2 or not x.is_cuda or not x.is_contiguous():
+        raise ValueError(f'{what}: Not valid input: a contiguous float32 [n, {"C" if least == 2 else "D"}] tensor on the device expected, got '
+                         f'{getattr(x, "dtype", type(x))} {tuple(getattr(x, "shape", ()))} on {getattr(x, "device", "the host")}')
+    n, c = x.shape
+    if n < 1 or not least <= c <= 65535:
+        raise ValueError(f'{what}: Not valid input: {n} rows of {c} columns (at least 1 row, {least} to 65535 columns)')
+    return n, c
+
+
+def _score_state(t: Tensor, shape: Tuple[int, ...], device, what: str, name: str):
+    if not torch.is_tensor(t) or t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != device or not t.is_contiguous():
+        raise ValueError(f'{what}: Not valid {name}: contiguous float64 {list(shape)} on {device} expected, got '
+                         f'{getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))} on {getattr(t, "device", "the host")}')
+
+
+def _score_work(t: Tensor, need: int, device, what: str):
+    if not torch.is_tensor(t) or t.dtype != torch.float64 or t.dim() != 1 or t.numel() < need or t.device != device:
+        raise ValueError(f'{what}: Not valid work: float64 [>= {need}] on {device} expected, got '
+                         f'{getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))} on {getattr(t, "device", "the host")}')
+
+
+def score_probs_work(n: int, c: int) -> int:
+    """Doubles of workspace `score_probs` needs for logits [n, c] (0 for sizes it refuses)."""
+    return int(_lib.load().mcgen_score_probs_work(int(n), int(c)))
+
+
+def score_moments_work(n: int, d: int) -> int:
+    """Doubles of workspace `score_moments` needs for features [n, d] (0 for sizes it refuses)."""
+    return int(_lib.load().mcgen_score_moments_work(int(n), int(d)))
+
+
+def score_probs(logits: Tensor, work: Tensor, psum: Tensor, plogp: Tensor):
+    """psum [C] += the column sums of softmax(logits [n, C] fp32), plogp [1] += sum p log p, both float64 and computed in
+    float64 (a row with a NaN makes both NaN).  Two launches (mcgen_score_probs), no synchronisation."""
+    n, c = _score_input(logits, 'score_probs', 2)
+    _score_state(psum, (c,), logits.device, 'score_probs', 'psum')
+    _score_state(plogp, (1,), logits.device, 'score_probs', 'plogp')
+    _score_work(work, score_probs_work(n, c), logits.device, 'score_probs')
+    check(_lib.load().mcgen_score_probs(logits.data_ptr(), n, c, work.data_ptr(), psum.data_ptr(), plogp.data_ptr(), _stream()),
+          'score_probs')
+
+
+def score_moments(feat: Tensor, work: Tensor, fsum: Tensor, gram: Tensor):
+    """fsum [D] += the column sums of feat [n, D] fp32, gram [D, D] += feat^T feat (raw second moments on the float64 MFMA, rows
+    in ascending order; bitwise symmetric), both float64.  Three launches (mcgen_score_moments), no synchronisation."""
+    n, d = _score_input(feat, 'score_moments', 1)
+    _score_state(fsum, (d,), feat.device, 'score_moments', 'fsum')
+    _score_state(gram, (d, d), feat.device, 'score_moments', 'gram')
+    _score_work(work, score_moments_work(n, d), feat.device, 'score_moments')
+    check(_lib.load().mcgen_score_moments(feat.data_ptr(), n, d, work.data_ptr(), fsum.data_ptr(), gram.data_ptr(), _stream()),
+          'score_moments')
