@@ -2217,8 +2217,17 @@ static long env_long(const char*, long dflt) { return dflt; }
 // every CU a workgroup (256 CUs); fp32 (parity build) is limited by LDS to the two small tiles.
 template <int BM, int BN, int WM, int WN, int R> static bool pp_fits(const mcgen_conv_t* p);
 
+// Pixels of one epilogue pass on a tile (ConvCfg::PPX; the pp form's merged passes hold whole row pairs by construction).
+// A pooled launch takes its 2x2 sums INSIDE a pass, so a pass has to hold two rows of the map -- or the whole tile.
+static int pass_pixels(int BM, int BN) { return (BN >= 128 && BM > 64) ? 64 : BM; }
+
 static TilePick pick_tile(const mcgen_conv_t* p, int dtype) {
     const long M = (long)p->N * p->H * p->W;
+    // pooled launches on 64-wide maps: the tiles with BN >= 128 pass 64 pixels -- ONE row -- at a time through the epilogue and
+    // would sum rows that are not there; the 128-pixel tiles with a single pass hold the two rows (tests/test_conv_exact_gpu.py,
+    // '128x128 W64' / pool, found this on the 128 x 128 tiles)
+    if (p->pool && p->W == 64 && p->Cout_w > 16)
+        return dtype == MCGEN_BF16 ? TilePick{128, 64, 5} : TilePick{128, 16, 0};
     if (p->Cout_w <= 16) {
         // skinny-N convolutions (Glow's ZeroConv2d and the input gradients of the coupling nets, image heads) are a
         // serial chain over K: with few pixels, 64-pixel tiles double the workgroups that overlap each other's
@@ -2612,6 +2621,9 @@ static int check_route(const mcgen_conv_t* p, int dtype, const Route& r) {
                     "(bf16, one 3x3 segment to <= 8 channels of pitch 8 on 32x32 maps, N %% y_group == 0)");
         return 0;
     }
+    // (the tiled policy never picks such a tile for a pooled launch; the K-major tiles all have BN >= 128)
+    MCGEN_CHECK(!p->pool || t.BM == 0 || t.pipe == 20 || pass_pixels(t.BM, t.BN) >= 2 * p->W || pass_pixels(t.BM, t.BN) == t.BM,
+                "conv_fused: pooling on a %d-wide map needs an epilogue pass of two rows, the %dx%d tile passes %d pixels", p->W, t.BM, t.BN, pass_pixels(t.BM, t.BN));
     if (p->w_layout == 1) return check_mc(p, dtype, t);
     if (p->w_layout == 2) return check_gk(p, dtype, t);
     for (int s = 0; s < p->nseg; ++s) MCGEN_CHECK(p->seg[s].cmap == nullptr, "conv_fused: a compaction map needs a K-major launch (w_layout 1 or 2)");
