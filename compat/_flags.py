@@ -1,0 +1,49 @@
+"""Command-line flags for cfg keys that only process_control creates: they are popped from argv before the shared parser
+sees it and applied to cfg after process_control has built its table.  No imports beyond the standard library, so every
+driver (and a test) can use it."""
+import sys
+
+GLOW_KEYS = ('affine', 'conv_lu')                         # cfg['glow'] keys of the reference's table (utils.py:183-184)
+_REFUSED = {'affine': 'Not valid coupling: only the affine form (cfg glow.affine = True) is built',
+            'conv_lu': 'Not valid invertible conv: only the LU form (cfg glow.conv_lu = True) is built'}
+
+
+def pop_flag(name, argv=None):
+    """Remove `--name V` / `--name=V` from argv; -> V or None."""
+    argv = sys.argv if argv is None else argv
+    for i, a in enumerate(argv):
+        if a == name and i + 1 < len(argv):
+            v = argv[i + 1]
+            del argv[i:i + 2]
+            return v
+        if a.startswith(name + '='):
+            del argv[i]
+            return a.split('=', 1)[1]
+    return None
+
+
+def pop_glow_flags(argv=None):
+    """--glow_affine {True,False} / --glow_conv_lu {True,False} -> {key: bool} of the flags given (none: the table stays)."""
+    out = {}
+    for key in GLOW_KEYS:
+        v = pop_flag('--glow_' + key, argv)
+        if v is None:
+            continue
+        if v not in ('True', 'False'):
+            raise ValueError('Not valid --glow_{}: {} (True or False)'.format(key, v))
+        out[key] = v == 'True'
+    return out
+
+
+def apply_glow_flags(cfg, flags):
+    """After process_control: set the popped keys in cfg['glow'].  MCGlow builds both values of each (mcglow.py:146,182-185);
+    the CGlow baseline only the table's, so a False is refused for it with its constructor's message."""
+    if not flags:
+        return
+    if 'glow' not in cfg.get('model_name', ''):
+        raise ValueError('Not valid model name: --glow_affine / --glow_conv_lu are flags of mcglow')
+    if cfg['model_name'] != 'mcglow':
+        for key in GLOW_KEYS:
+            if flags.get(key) is False:
+                raise ValueError(_REFUSED[key])
+    cfg['glow'] = dict(cfg['glow'], **flags)

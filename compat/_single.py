@@ -216,8 +216,12 @@ class Driver:
         model.train(True)
 
     # ---- train_vae.py:38-95 ------------------------------------------------------------------------------------
+    def after_control(self):
+        """Hook: cfg edits of a driver that have to follow process_control's table."""
+
     def main(self):
         process_control()
+        self.after_control()
         if self.extra['batch']:
             cfg['batch_size'] = dict(cfg['batch_size'], train=self.extra['batch'])
         seeds = list(range(cfg['init_seed'], cfg['init_seed'] + cfg['num_experiments']))

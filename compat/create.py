@@ -18,6 +18,7 @@ import models
 import data as data_shim
 from _single import cfg, parse
 from data import fetch_dataset
+from _flags import apply_glow_flags, pop_glow_flags
 from generate import SAMPLE_PER_ITER, _draw, _pop_flag
 from utils import process_control, process_dataset, resume, save, save_img
 
@@ -110,11 +111,13 @@ def load_models(extra):
 def main(run_experiment, overrides=None):
     """create.py:25-35, the loop every evaluation driver of the reference repeats: one `run_experiment(extra)` per seed."""
     per_mode = _pop_flag('--generate_per_mode')
+    glow_flags = pop_glow_flags()                         # --glow_affine / --glow_conv_lu (mcglow)
     extra = parse(overrides or {})
     if cfg['control_name'] == 'None':                     # the baselines take no control (create.py:19-22)
         cfg['control'] = {}
         cfg['control_name'] = ''
     process_control()
+    apply_glow_flags(cfg, glow_flags)
     if per_mode is not None:
         cfg['generate_per_mode'] = int(per_mode)
     if torch.cuda.is_available():

@@ -8,14 +8,14 @@ pixelcnn_sampler.py) and decodes them with `ae.decode_code`; MCGAN / CGAN / MCVA
                     save_per_mode samples per mode (generate.py:60-84);
   otherwise:        grids of 10 / 50 / 100 modes x save_per_mode samples (generate.py:85-104).
 Grids go through compat/utils.save_img (a .npy next to the requested path).  --generate_per_mode N overrides the
-process_control table (applied after it), so a short run is possible.  Shared CLI parsing: compat/_single.parse."""
-import sys
-
+process_control table (applied after it), so a short run is possible.  --glow_affine / --glow_conv_lu {True,False} pick
+MCGlow's coupling form and 1x1 convolution the same way (compat/_flags.py).  Shared CLI parsing: compat/_single.parse."""
 import torch
 
 import _single  # noqa: F401  (sys.path)
 import models
 import data as data_shim
+from _flags import apply_glow_flags, pop_flag, pop_glow_flags
 from _single import cfg, parse
 from data import fetch_dataset
 from utils import process_control, process_dataset, resume, save, save_img
@@ -25,16 +25,7 @@ SAMPLE_PER_ITER = 1000                                    # generate.py:57
 
 def _pop_flag(name):
     """Remove `--name V` / `--name=V` from argv (a cfg key that only process_control creates); -> V or None."""
-    argv = sys.argv
-    for i, a in enumerate(argv):
-        if a == name and i + 1 < len(argv):
-            v = argv[i + 1]
-            del argv[i:i + 2]
-            return v
-        if a.startswith(name + '='):
-            del argv[i]
-            return a.split('=', 1)[1]
-    return None
+    return pop_flag(name)
 
 
 def _draw(model, ae, C):
@@ -94,11 +85,13 @@ def run_experiment(extra):
 
 def main():
     per_mode = _pop_flag('--generate_per_mode')
+    glow_flags = pop_glow_flags()
     extra = parse({})
     if cfg['control_name'] == 'None':                     # the baselines take no control (generate.py:19-22)
         cfg['control'] = {}
         cfg['control_name'] = ''
     process_control()
+    apply_glow_flags(cfg, glow_flags)
     if per_mode is not None:
         cfg['generate_per_mode'] = int(per_mode)
     if torch.cuda.is_available():

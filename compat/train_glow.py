@@ -3,17 +3,24 @@
 data-dependent ActNorm initialisation on `num_init_batches` (8) concatenated batches BEFORE the resume / data-parallel
 wrap (train_glow.py:37,60-67) and the reconstruction through `model.reverse` in test() (:156-158).  Shared parts and
 the differences from the reference: compat/_single.py.
---model_name mcglow or cglow (the conditional baseline, models/cglow.py; with --control_name None, on one GPU)."""
+--model_name mcglow or cglow (the conditional baseline, models/cglow.py; with --control_name None, on one GPU).
+--glow_affine {True,False} / --glow_conv_lu {True,False} pick MCGlow's coupling form and 1x1 convolution (compat/_flags.py:
+applied to cfg['glow'] after process_control; default: the table's True, True; a False is refused for cglow)."""
 from itertools import islice
 
 import torch
 
 import _single
+from _flags import apply_glow_flags, pop_glow_flags
 from _single import cfg, Driver, parse, to_device
 
 
 class GlowDriver(Driver):
     from mcgen_amd.trainer import GlowTrainer as trainer_cls
+    glow_flags = {}                                   # --glow_affine / --glow_conv_lu, popped in main()
+
+    def after_control(self):
+        apply_glow_flags(cfg, self.glow_flags)
 
     def before_resume(self, model, loader):           # train_glow.py:60-67
         batches = list(islice(loader, None, cfg['num_init_batches']))
@@ -47,6 +54,7 @@ def apply_control():
 
 
 def main():
+    GlowDriver.glow_flags = pop_glow_flags()
     extra = parse({'pivot_metric': 'Loss', 'metric_name': {'train': ['Loss'], 'test': ['Loss']}, 'show': False,
                    'num_init_batches': 8})
     apply_control()

@@ -571,6 +571,26 @@ int mcgen_invconv_weight_batch(const mcgen_icw_t* jobs, int n, void* stream);
 int mcgen_invconv_bwd_batch(const mcgen_icb_t* jobs, int n, void* stream);
 int mcgen_actnorm_bwd_batch(const mcgen_an_bwd_t* jobs, int n, void* stream);
 int mcgen_prod_colsum_batch(const mcgen_pcs_t* jobs, int n, int dtype, float* workspace /* n * 256 * max C floats */, void* stream);
+/* ---- the other two forms of a flow: plain InvConv2d (cfg glow.conv_lu = False) and additive coupling (glow.affine = False)
+ * InvConv2d.forward / reverse (mcglow.py:58-73) on the dense C x C weight: logabsdet[0] = slogdet(W.double())[1].float()
+ * (mcglow.py:69: the reference takes the log-determinant in float64) and weight_inv = W^-1 (mcglow.py:73).  One workgroup,
+ * Gauss-Jordan with partial pivoting in float64 on [W | I] in LDS (2 C^2 doubles: 64 KB at C = 64), rounded to fp32 once at
+ * the end; C in 1..64.  An exactly zero pivot gives logabsdet = -inf and a NaN weight_inv (torch.slogdet's -inf). */
+int mcgen_invconv_plain(const float* weight, int C, float* logabsdet, float* weight_inv, void* stream);
+/* autograd of F.conv2d(x, W) and HW * slogdet(W)[1] (mcglow.py:68-69) w.r.t. W: grad[co][ci] (+)= dW[co * ldw + ci] +
+ * ld_coef * weight_inv[ci][co]  (d log|det W| / dW = W^-T; ld_coef = dL/dlogdet * N * H * W as in mcgen_invconv_bwd) */
+int mcgen_invconv_plain_bwd(const float* dW, int C, int ldw, const float* weight_inv, float ld_coef, float* grad,
+                            int accumulate, void* stream);
+/* batched forms, one workgroup per job, MCGEN_GLOW_BATCH_MAX jobs per launch (the job table travels by value) */
+typedef struct { const float* weight; float* logabsdet; float* weight_inv; int32_t C, _pad; } mcgen_icp_t;
+typedef struct { const float* dW; const float* weight_inv; float* grad; int32_t C, ldw, accumulate; float ld_coef; } mcgen_icpb_t;
+int mcgen_invconv_plain_batch(const mcgen_icp_t* jobs, int n, void* stream);
+int mcgen_invconv_plain_bwd_batch(const mcgen_icpb_t* jobs, int n, void* stream);
+/* additive coupling (mcglow.py:160-163 forward, 172-174 reverse) on [pixels, Cp] given the coupling network output h
+ * (C/2 channels, row pitch Ch): y[:, :C/2] = x[:, :C/2], y[:, C/2:C] = x[:, C/2:C] + sign * h[:, :C/2] (sign +1 forward,
+ * -1 reverse), y[:, C:Cp] = 0; no log-determinant (mcglow.py:163).  y may be x. */
+int mcgen_glow_coupling_add(const void* x, const void* h, void* y, int dtype, int64_t pixels, int C, int Cp, int Ch,
+                            int sign, void* stream);
 /* torch.nn.utils.clip_grad_norm_(params, max_norm) over one flat gradient buffer (train_vae.py:110) */
 int mcgen_clip_grad_norm(float* g, int64_t n, float max_norm, float* norm_out, float* workspace /* 256 floats */, void* stream);
 

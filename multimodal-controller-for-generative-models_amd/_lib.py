@@ -29,6 +29,8 @@ AnAffine = HEADER.structs['mcgen_an_affine_t']
 Pld = HEADER.structs['mcgen_pld_t']
 Icw = HEADER.structs['mcgen_icw_t']
 Icb = HEADER.structs['mcgen_icb_t']
+Icp = HEADER.structs['mcgen_icp_t']
+Icpb = HEADER.structs['mcgen_icpb_t']
 AnBwd = HEADER.structs['mcgen_an_bwd_t']
 Pcs = HEADER.structs['mcgen_pcs_t']
 BnRun = HEADER.structs['mcgen_bn_run_t']

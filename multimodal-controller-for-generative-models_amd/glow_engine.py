@@ -7,6 +7,11 @@ the coupling network is three fused convolutions (3x3, 1x1, 3x3) whose prologues
 ReLU and the MultimodalController codes; the affine transform + per-sample log-determinant is one kernel.
 The coupling network reads only the first C/2 channels: its first weight image is zero over the others,
 so no split/concat copy is needed inside a flow.
+
+A flow has two properties, read once by _is_plain / _is_additive: the 1x1 convolution is LU-parameterised or plain
+(InvConv2d, mcglow.py:58-73: the dense weight is the matrix, its log|det| and inverse come from one float64
+factorisation per pass), the coupling affine or additive (mcglow.py:160-163: the network ends in C/2 channels that are
+added, no log-determinant).  The affine / LU path's launches do not depend on the other forms.
 """
 from __future__ import annotations
 
@@ -37,6 +42,19 @@ class GlowEngine(EngineBase):
     def _layers(net):
         """(conv0, an1, mc1, conv1, an5, mc2, zc) of an AffineCoupling.net: the one place that knows its layout."""
         return net[0].module, net[1].module, net[3], net[4].module, net[5].module, net[7], net[8].module
+
+    @staticmethod
+    def _is_plain(flow) -> bool:
+        """The flow's 1x1 convolution is the plain InvConv2d (one dense `weight`), not the LU form."""
+        return not hasattr(flow.invconv, 'w_s')
+
+    @staticmethod
+    def _is_additive(flow) -> bool:
+        return not flow.coupling.affine
+
+    @staticmethod
+    def _plain_matrix(ic) -> Tensor:
+        return ic.weight.detach().view(ic.weight.shape[0], ic.weight.shape[1])
 
     def _full(self, value: float, n: int, device) -> Tensor:
         key = (value, n, str(device))
@@ -69,11 +87,18 @@ class GlowEngine(EngineBase):
             # ... and their biases times it (mcglow.py:127-130: (conv(x) + b) * exp(3 scale)): one launch, not one per flow
             self._bz = {id(z): b for z, b in zip(zcs, torch._foreach_mul([z.conv.bias.detach() for z in zcs], rs))}
             self._wmat = {}
+            self._plain = {}                       # plain InvConv2d: id(ic) -> (logabsdet [1], weight_inv [C, C])
         jobs, keys = [], []
         if not backward:
-            ics = [f.invconv for b in m.blocks for f in b.flows]
-            for ic, wmat in zip(ics, ops.invconv_weight_batch(ics)):      # every flow's LU weight, two launches
-                self._wmat[id(ic)] = wmat
+            flows = [f for b in m.blocks for f in b.flows]
+            ics = [f.invconv for f in flows if not self._is_plain(f)]
+            if ics:
+                for ic, wmat in zip(ics, ops.invconv_weight_batch(ics)):      # every flow's LU weight, two launches
+                    self._wmat[id(ic)] = wmat
+            ics = [f.invconv for f in flows if self._is_plain(f)]
+            if ics:                                # the dense weight is the matrix; log|det| and inverse in float64, two launches
+                for ic, fac in zip(ics, ops.invconv_plain_batch([self._plain_matrix(ic) for ic in ics])):
+                    self._wmat[id(ic)], self._plain[id(ic)] = self._plain_matrix(ic), fac
 
         def add(key, w, **kw):
             keys.append(key); jobs.append((w.detach(), dict(kw, transpose=backward)))
@@ -82,6 +107,7 @@ class GlowEngine(EngineBase):
             for flow in blk.flows:
                 conv0, an1, _, conv1, an5, _, zc = self._layers(flow.coupling.net)
                 hid, ic, rs = conv0.out_channels, flow.invconv, self._rs[id(zc)]
+                czp = pad8(c // 2) if self._is_additive(flow) else cp       # pitch of the coupling network's output
                 if not backward:
                     wmat = self._wmat[id(ic)]
                     add((id(conv0), 'f'), conv0.weight, k_img=cp)
@@ -89,7 +115,7 @@ class GlowEngine(EngineBase):
                     add((id(zc), 'f'), zc.conv.weight, row_scale=rs, k_img=hid)
                     add((id(ic), 'f'), wmat, ksize=1, k_img=cp)
                 else:
-                    add((id(zc), 'b'), zc.conv.weight, row_scale=rs, k_img=cp)
+                    add((id(zc), 'b'), zc.conv.weight, row_scale=rs, k_img=czp)
                     add((id(conv1), 'b'), conv1.weight, row_scale=an5.scale.detach().reshape(-1))
                     add((id(conv0), 'b'), conv0.weight, row_scale=an1.scale.detach().reshape(-1), rows_img=c)
                     add((id(ic), 'b'), self._wmat[id(ic)], ksize=1, col_scale=flow.actnorm.scale.detach().reshape(-1), k_img=cp)
@@ -139,8 +165,9 @@ class GlowEngine(EngineBase):
     def _last_prior_bwd(self, blk, rec, dprior: Tensor, c: int):
         self._zero_conv_bwd(blk.prior, None, rec['prior'], dprior, 2 * c, c, False)
 
-    def _coupling_net(self, cp_net, x: Tensor, c: int, codes, train: bool, saved=None):
-        """AffineCoupling.net on the first c/2 channels of x -> [log_s | t] (c channels)."""
+    def _coupling_net(self, cp_net, x: Tensor, c: int, codes, train: bool, saved=None, additive: bool = False):
+        """AffineCoupling.net on the first c/2 channels of x -> [log_s | t] (c channels, the pitch of x), or the c/2 added
+        channels of the additive form (their own pitch)."""
         net = cp_net
         dt = self.dtype
         n, h, w, cp = x.shape
@@ -159,7 +186,10 @@ class GlowEngine(EngineBase):
                                  stats_mode=1 if need5 else 0)
         a5, b5, nl5 = self._actnorm(an5, lambda: st2, count, train, hid)
         wz, bz = self._zero_conv_image(zc, hid)
-        hz, _ = ops.conv_fused([Seg(h2, scale=a5, shift=b5, relu=True, code=codes[1])], wz, c, bias=bz, cy=cp)
+        if additive:
+            hz, _ = ops.conv_fused([Seg(h2, scale=a5, shift=b5, relu=True, code=codes[1])], wz, c // 2, bias=bz)
+        else:
+            hz, _ = ops.conv_fused([Seg(h2, scale=a5, shift=b5, relu=True, code=codes[1])], wz, c, bias=bz, cy=cp)
         if saved is not None:
             saved.update(h1=h1, h2=h2, a1=a1, b1=b1, a5=a5, b5=b5, nl1=nl1, nl5=nl5)
         return hz
@@ -169,21 +199,28 @@ class GlowEngine(EngineBase):
         n, h, w, cp = x.shape
         a, b, nl = self._actnorm(flow.actnorm, lambda: ops.channel_stats(x), n * h * w, train, cp)
         ic = flow.invconv
+        plain, additive = self._is_plain(flow), self._is_additive(flow)
         wmat = self._wmat.get(id(ic)) if getattr(self, '_I', None) else None
-        if wmat is None:
+        fac = self._plain.get(id(ic)) if plain and wmat is not None else None
+        if wmat is None and plain:
+            wmat, fac = self._plain_matrix(ic), ops.invconv_plain(self._plain_matrix(ic))
+        elif wmat is None:
             wmat, _ = ops.invconv_weight(ic.w_p, ic.w_l.data, ic.w_u.data, ic.w_s.data, ic.s_sign)
         out, _ = ops.conv_fused([Seg(x, ksize=1, scale=a, shift=b)],
                                 self._img((id(ic), 'f'), lambda: ops.prep_weight_ex(wmat, dt, 1, k_img=cp)), c, cy=cp)
         # parameter-only log-determinants: H*W * (sum log|scale| + sum w_s)   (mcglow.py:46-47,101)
+        # (plain form: the one-element log|det W| of the float64 factorisation stands where sum w_s does, mcglow.py:69)
         if not (self._pass and self._pass.get('logdet')):
-            ops.glow_param_logdet(flow.actnorm.scale.detach(), ic.w_s.detach(), h * w, logdet)
+            ops.glow_param_logdet(flow.actnorm.scale.detach(), fac[0] if plain else ic.w_s.detach(), h * w, logdet)
         net = flow.coupling.net
         codes = self._codes(net, indicator, label)
-        rec = None if tape is None else dict(x=x, a=a, b=b, nl=nl, out=out, codes=codes, wmat=wmat)
-        hz = self._coupling_net(net, out, c, codes, train, rec)
+        rec = None if tape is None else dict(x=x, a=a, b=b, nl=nl, out=out, codes=codes, wmat=wmat, winv=fac[1] if plain else None)
+        hz = self._coupling_net(net, out, c, codes, train, rec, additive)
         if tape is not None:
             rec['hz'] = hz
             tape.append(rec)
+        if additive:                               # mcglow.py:160-163: no log-determinant
+            return ops.glow_coupling_add(out, hz, c)
         return ops.glow_coupling(out, hz, c, logdet, reverse=False, accumulate=True)
 
     def _codes(self, net, indicator, label):
@@ -221,7 +258,8 @@ class GlowEngine(EngineBase):
             items = []
             for blk in m.blocks:
                 hw //= 4
-                items += [(f.actnorm.scale.detach(), f.invconv.w_s.detach(), hw) for f in blk.flows]
+                items += [(f.actnorm.scale.detach(), self._plain[id(f.invconv)][0] if self._is_plain(f) else f.invconv.w_s.detach(), hw)
+                          for f in blk.flows]
             ops.glow_param_logdet_batch(items, logdet)
             self._pass['logdet'] = True
 
@@ -230,10 +268,14 @@ class GlowEngine(EngineBase):
         cp = y.shape[-1]
         net = flow.coupling.net
         codes = self._codes(net, indicator, label)
-        hz = self._coupling_net(net, y, c, codes, False)
-        x = ops.glow_coupling(y, hz, c, None, reverse=True)
+        additive = self._is_additive(flow)
+        hz = self._coupling_net(net, y, c, codes, False, additive=additive)
+        x = ops.glow_coupling_add(y, hz, c, reverse=True) if additive else ops.glow_coupling(y, hz, c, None, reverse=True)
         ic = flow.invconv
-        _, winv = ops.invconv_weight(ic.w_p, ic.w_l.data, ic.w_u.data, ic.w_s.data, ic.s_sign, inverse=True)
+        if self._is_plain(flow):
+            _, winv = ops.invconv_plain(self._plain_matrix(ic))            # mcglow.py:73, on the device in float64
+        else:
+            _, winv = ops.invconv_weight(ic.w_p, ic.w_l.data, ic.w_u.data, ic.w_s.data, ic.s_sign, inverse=True)
         # ActNorm.reverse folded in: x_prev = (W^-1 x) / scale - loc
         an = flow.actnorm
         wimg = ops.prep_weight_ex(winv, dt, 1, row_scale=1.0 / an.scale.detach().reshape(-1), k_img=cp)
@@ -319,9 +361,16 @@ class GlowEngine(EngineBase):
         hid = conv0.out_channels
         dev = out.device
         ones = self._full(1.0, hid, dev)
-        dv, dhz = ops.glow_coupling_bwd(out, hz, dy, c, g0)
+        if self._is_additive(flow):
+            # d(out)/d(in) is the identity: dy itself is the residual of the 3x3 input-gradient launch; dh = dy[..., c/2:c]
+            dv, cz = dy, c // 2
+            dhz = torch.zeros_like(hz)
+            ops.copy_channels(dy, cz, dhz, 0, cz)
+        else:
+            cz = c
+            dv, dhz = ops.glow_coupling_bwd(out, hz, dy, c, g0)
         # ZeroConv2d <- MC <- ReLU <- ActNorm(5)
-        v5, st5 = self._zero_conv_bwd(zc, Seg(r['h2'], scale=r['a5'], shift=r['b5'], relu=True, code=codes[1]), hz, dhz, c, hid,
+        v5, st5 = self._zero_conv_bwd(zc, Seg(r['h2'], scale=r['a5'], shift=r['b5'], relu=True, code=codes[1]), hz, dhz, cz, hid,
                                       True, ocode=codes[1], gate_x=r['h2'], gscale=r['a5'], gshift=r['b5'],
                                       gmean=r['nl5'], grstd=ones, stats_mode=2)
         (self._dfr or ops).actnorm_bwd(st5, an5.scale.detach(), 0.0, False, self._grad(an5.loc), self._grad(an5.scale))
@@ -342,12 +391,19 @@ class GlowEngine(EngineBase):
         an, ic = flow.actnorm, flow.invconv
         gW = torch.empty((c, cp), dtype=torch.float32, device=dev)
         ops.wgrad(Seg(x, ksize=1, scale=r['a'], shift=r['b']), dvt, c, cp, gW)
-        gl, gu, gs = self._grad(ic.w_l), self._grad(ic.w_u), self._grad(ic.w_s)
-        # the LU-parameter gradients need the reduced dW: after the pass's batched split-K reduction
-        if self._dfr is not None:
-            self._dfr.invconv_bwd(ic, gW, ld_coef, gl, gu, gs)
+        # the 1x1 parameter gradients need the reduced dW: after the pass's batched split-K reduction
+        if self._is_plain(flow):
+            gw, winv = self._grad(ic.weight), r['winv']                 # dW + ld_coef W^-T
+            if self._dfr is not None:
+                self._dfr.invconv_plain_bwd(gW, winv, ld_coef, gw)
+            else:
+                self._post.append(lambda: ops.invconv_plain_bwd(gW, winv, ld_coef, gw))
         else:
-            self._post.append(lambda: ops.invconv_bwd(ic.w_p, ic.w_l.data, ic.w_u.data, ic.w_s.data, ic.s_sign, gW, ld_coef, gl, gu, gs))
+            gl, gu, gs = self._grad(ic.w_l), self._grad(ic.w_u), self._grad(ic.w_s)
+            if self._dfr is not None:
+                self._dfr.invconv_bwd(ic, gW, ld_coef, gl, gu, gs)
+            else:
+                self._post.append(lambda: ops.invconv_bwd(ic.w_p, ic.w_l.data, ic.w_u.data, ic.w_s.data, ic.s_sign, gW, ld_coef, gl, gu, gs))
         s = an.scale.detach().reshape(-1)
         wmat = r['wmat']
         wt = self._img((id(ic), 'b'), lambda: ops.prep_weight_ex(wmat, dt, 1, transpose=True, col_scale=s, k_img=cp))   # [ci, co] = W[co, ci] * s[ci]

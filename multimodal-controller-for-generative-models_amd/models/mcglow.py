@@ -1,5 +1,6 @@
-"""MCGlow with the reference's module surface (src/models/mcglow.py): ActNorm, LU-parameterised invertible
-1x1 convolution, affine coupling with MultimodalController-masked coupling networks, multi-scale blocks.
+"""MCGlow with the reference's module surface (src/models/mcglow.py): ActNorm, invertible 1x1 convolution
+(LU-parameterised or plain), affine or additive coupling with MultimodalController-masked coupling networks, multi-scale
+blocks.
 
 The module tree carries the reference's parameter / buffer names (``state_dict`` compatible); the arithmetic
 runs in ``glow_engine.py`` on HIP kernels: the likelihood forward (incl. the data-dependent ActNorm
@@ -28,6 +29,16 @@ class ActNorm(nn.Module):
         self.scale = nn.Parameter(torch.ones(1, input_size, 1, 1))
         self.register_buffer('initialized', torch.tensor(0, dtype=torch.uint8))
         self.logdet = logdet
+
+
+class InvConv2d(nn.Module):
+    """mcglow.py:58-73: the plain form, one dense weight [C, C, 1, 1] initialised from the Q of a random matrix
+    (torch's global RNG, as in the reference); no buffers."""
+
+    def __init__(self, input_size):
+        super().__init__()
+        q, _ = torch.linalg.qr(torch.randn(input_size, input_size))
+        self.weight = nn.Parameter(q.unsqueeze(2).unsqueeze(3).contiguous())
 
 
 class InvConv2dLU(nn.Module):
@@ -62,12 +73,10 @@ class ZeroConv2d(nn.Module):
 
 
 class AffineCoupling(nn.Module):
-    """mcglow.py:133-175 (affine form)."""
+    """mcglow.py:133-175: affine, or additive (affine=False: the network ends in input_size // 2 channels)."""
 
     def __init__(self, input_size, hidden_size=512, affine=True, num_mode=None, controller_rate=None):
         super().__init__()
-        if not affine:
-            raise ValueError('Not valid coupling: only the affine form (cfg glow.affine = True) is built')
         self.affine = affine
         conv_in, conv_mid = nn.Conv2d(input_size // 2, hidden_size, 3, padding=1), nn.Conv2d(hidden_size, hidden_size, 1)
         for conv in (conv_in, conv_mid):
@@ -78,7 +87,7 @@ class AffineCoupling(nn.Module):
             MultimodalController(hidden_size, num_mode, controller_rate),
             Wrapper(conv_mid), Wrapper(ActNorm(hidden_size, logdet=False)), Wrapper(nn.ReLU(inplace=True)),
             MultimodalController(hidden_size, num_mode, controller_rate),
-            Wrapper(ZeroConv2d(hidden_size, input_size)))
+            Wrapper(ZeroConv2d(hidden_size, input_size if affine else input_size // 2)))
 
 
 class Flow(nn.Module):
@@ -86,10 +95,8 @@ class Flow(nn.Module):
 
     def __init__(self, input_size, hidden_size, affine=True, conv_lu=True, num_mode=None, controller_rate=None):
         super().__init__()
-        if not conv_lu:
-            raise ValueError('Not valid invertible conv: only the LU form (cfg glow.conv_lu = True) is built')
         self.actnorm = ActNorm(input_size)
-        self.invconv = InvConv2dLU(input_size)
+        self.invconv = InvConv2dLU(input_size) if conv_lu else InvConv2d(input_size)
         self.coupling = AffineCoupling(input_size, hidden_size, affine, num_mode, controller_rate)
 
 

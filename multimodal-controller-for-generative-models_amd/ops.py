@@ -1329,7 +1329,7 @@ class GlowDeferred:
     its end -- they were ~250 launches of 3-6 us."""
 
     def __init__(self):
-        self.an, self.pcs, self.icb, self.keep = [], [], [], []
+        self.an, self.pcs, self.icb, self.icp, self.keep = [], [], [], [], []
 
     def actnorm_bwd(self, partials, scale, ld_coef, input_side, dloc, dscale, accumulate=False):
         self.an.append((partials, scale, float(ld_coef), int(input_side), dloc, dscale, int(accumulate)))
@@ -1339,6 +1339,9 @@ class GlowDeferred:
 
     def invconv_bwd(self, ic, dW, ld_coef, dw_l, dw_u, dw_s, accumulate=False):
         self.icb.append((ic, dW, float(ld_coef), dw_l, dw_u, dw_s, int(accumulate)))
+
+    def invconv_plain_bwd(self, dW, weight_inv, ld_coef, grad, accumulate=False):
+        self.icp.append((dW, weight_inv, float(ld_coef), grad, int(accumulate)))
 
     def run(self):
         lib = _lib.load()
@@ -1366,7 +1369,9 @@ class GlowDeferred:
                 d.dW, d.dw_l, d.dw_u, d.dw_s = _f32(dW), _f32(dl), _f32(du), _f32(dsg)
                 d.C, d.ldw, d.accumulate, d.ld_coef = ic.w_s.numel(), dW.shape[-1], acc, ld
             check(lib.mcgen_invconv_bwd_batch(arr, len(self.icb), _stream()), 'invconv_bwd_batch')
-        self.an, self.pcs, self.icb = [], [], []
+        if self.icp:
+            invconv_plain_bwd_batch(self.icp)
+        self.an, self.pcs, self.icb, self.icp = [], [], [], []
 
 
 def prep_weight_rows(w: Tensor, dtype: torch.dtype, row_scale: Tensor) -> Tensor:
@@ -1443,6 +1448,84 @@ def invconv_bwd(w_p, w_l, w_u, w_s, s_sign, dW: Tensor, ld_coef: float, dw_l, dw
     check(_lib.load().mcgen_invconv_bwd(_f32(w_p), _f32(w_l), _f32(w_u), _f32(w_s), _f32(s_sign), _f32(dW), c, dW.shape[-1],
                                         float(ld_coef), _f32(dw_l), _f32(dw_u), _f32(dw_s), int(accumulate), _stream()),
           'invconv_bwd')
+
+
+# ---- the other two forms of a flow: plain InvConv2d (glow.conv_lu = False), additive coupling (glow.affine = False) ---------
+def _square_weight(weight: Tensor, what: str) -> int:
+    """C of an InvConv2d weight [C, C] or [C, C, 1, 1] (read densely); refuses what the kernel cannot take."""
+    if weight.dim() not in (2, 4) or weight.shape[0] != weight.shape[1] or weight.numel() != weight.shape[0] ** 2:
+        raise _lib.McgenError(f'{what}: expected a [C, C] or [C, C, 1, 1] weight, got {tuple(weight.shape)}')
+    c = weight.shape[0]
+    if not 1 <= c <= 64:
+        raise _lib.McgenError(f'{what}: C must be in 1..64, got {c}')
+    return c
+
+
+def invconv_plain(weight: Tensor):
+    """(logabsdet [1], weight_inv [C, C]) of an InvConv2d weight (mcglow.py:69,73), factorised in float64."""
+    c = _square_weight(weight, 'invconv_plain')
+    lad = torch.empty(1, dtype=torch.float32, device=weight.device)
+    winv = torch.empty((c, c), dtype=torch.float32, device=weight.device)
+    check(_lib.load().mcgen_invconv_plain(_f32(weight), c, _f32(lad), _f32(winv), _stream()), 'invconv_plain')
+    return lad, winv
+
+
+def invconv_plain_batch(weights):
+    """[(logabsdet [1], weight_inv [C, C])] of InvConv2d weights, one launch per MCGEN_GLOW_BATCH_MAX matrices: the
+    log-determinants share one buffer, the inverses another."""
+    cs = [_square_weight(w, 'invconv_plain_batch') for w in weights]
+    dev = weights[0].device
+    lads = torch.empty(len(cs), dtype=torch.float32, device=dev)
+    invs = torch.empty(sum(c * c for c in cs), dtype=torch.float32, device=dev)
+    arr = (_lib.Icp * len(cs))()
+    out, off = [], 0
+    for i, (d, w, c) in enumerate(zip(arr, weights, cs)):
+        lad, winv = lads[i:i + 1], invs[off:off + c * c].view(c, c)
+        off += c * c
+        d.weight, d.logabsdet, d.weight_inv, d.C = _f32(w), _f32(lad), _f32(winv), c
+        out.append((lad, winv))
+    check(_lib.load().mcgen_invconv_plain_batch(arr, len(cs), _stream()), 'invconv_plain_batch')
+    return out
+
+
+def _plain_bwd_args(dW: Tensor, weight_inv: Tensor, grad: Tensor, what: str):
+    c = _square_weight(weight_inv, what)
+    if dW.dim() != 2 or dW.shape[0] != c or dW.shape[1] < c:
+        raise _lib.McgenError(f'{what}: dW must be [C, ldw >= C] with C = {c}, got {tuple(dW.shape)}')
+    if grad.numel() != c * c:
+        raise _lib.McgenError(f'{what}: grad must hold C * C = {c * c} elements, got {tuple(grad.shape)}')
+    return c, dW.shape[1]
+
+
+def invconv_plain_bwd(dW: Tensor, weight_inv: Tensor, ld_coef: float, grad: Tensor, accumulate: bool = False):
+    """grad (+)= dW[:, :C] + ld_coef * weight_inv^T: the InvConv2d weight gradient from the reduced 1x1 weight gradient dW
+    [C, ldw] and d log|det W| / dW = W^-T."""
+    c, ldw = _plain_bwd_args(dW, weight_inv, grad, 'invconv_plain_bwd')
+    check(_lib.load().mcgen_invconv_plain_bwd(_f32(dW), c, ldw, _f32(weight_inv), float(ld_coef), _f32(grad), int(accumulate),
+                                              _stream()), 'invconv_plain_bwd')
+
+
+def invconv_plain_bwd_batch(jobs):
+    """`jobs`: [(dW, weight_inv, ld_coef, grad, accumulate)], one launch per MCGEN_GLOW_BATCH_MAX jobs."""
+    arr = (_lib.Icpb * len(jobs))()
+    for d, (dW, winv, ld, grad, acc) in zip(arr, jobs):
+        c, ldw = _plain_bwd_args(dW, winv, grad, 'invconv_plain_bwd_batch')
+        d.dW, d.weight_inv, d.grad, d.C, d.ldw, d.accumulate, d.ld_coef = _f32(dW), _f32(winv), _f32(grad), c, ldw, int(acc), float(ld)
+    check(_lib.load().mcgen_invconv_plain_bwd_batch(arr, len(jobs), _stream()), 'invconv_plain_bwd_batch')
+
+
+def glow_coupling_add(x: Tensor, h: Tensor, c: int, reverse: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """Additive coupling (mcglow.py:160-163 / 172-174): y = [x_a | x_b +- h] on [N, H, W, Cp] with h the coupling network's
+    C/2 channels (its own pitch); channels >= C of y are zero.  `out` may be x itself."""
+    cp, ch = x.shape[-1], h.shape[-1]
+    y = torch.empty_like(x) if out is None else out
+    if c <= 0 or c % 2 or cp < c or cp % 8 or ch < c // 2:
+        raise _lib.McgenError(f'glow_coupling_add: C = {c} must be even, Cp = {cp} a multiple of 8 >= C, Ch = {ch} >= C / 2')
+    if h.dtype != x.dtype or y.dtype != x.dtype or h.shape[:-1] != x.shape[:-1] or y.shape != x.shape:
+        raise _lib.McgenError('glow_coupling_add: x, h and y must share dtype and pixels')
+    check(_lib.load().mcgen_glow_coupling_add(_p(x), _p(h), _p(y), _dt(x.dtype), x.numel() // cp, c, cp, ch, -1 if reverse else 1,
+                                              _stream()), 'glow_coupling_add')
+    return y
 
 
 def clip_grad_norm_(gflat: Tensor, max_norm: float) -> Tensor:

@@ -1306,6 +1306,97 @@ def fx_cglow_omniglot_small():
 
 FIXTURES.update(cglow_small=fx_cglow_small, cglow_cifar_small=fx_cglow_cifar_small, cglow_omniglot_small=fx_cglow_omniglot_small)
 
+# ---- MCGlow with additive coupling and / or the plain InvConv2d (cfg glow.affine / glow.conv_lu = False) ------------------------
+def _mcglow_variant_small(name, channels, classes, affine, conv_lu, step_file=None):
+    """MCGlow [channels,32,32], K=2, L=3, hidden 32, B=4 with a repeated label, built like _cglow_small: the zero-initialised
+    ZeroConv2d tensors are perturbed from a seeded generator (at the all-zero initialisation the coupling networks' gradients
+    vanish identically) and, for the plain InvConv2d, so is the orthogonal initial weight (at an orthogonal W, W^-T = W and
+    the test of the log-determinant's gradient would be weak).  Contents as in fx_mcglow_small / _cglow_small: initial state,
+    state after the ActNorm data init, batch, per-step noise, two train_glow.py steps' losses, grad0/* (before
+    clip_grad_norm_), final state (as differences), loss_eval, z0/*, reconstructed, gen_z/*, generated.  `step_file` takes the
+    first step's gradients and the final differences, as in _cglow_small."""
+    import models
+    cfg['model_name'] = 'mcglow'; cfg['device'] = 'cpu'; cfg['classes_size'] = classes; cfg['controller_rate'] = 0.5
+    cfg['data_shape'] = [channels, 32, 32]
+    cfg['glow'] = {'hidden_size': 32, 'K': 2, 'L': 3, 'affine': affine, 'conv_lu': conv_lu}
+    torch.manual_seed(0); np.random.seed(0)
+    model = models.mcglow(); model.train(True)
+    g = torch.Generator().manual_seed(97)
+    with torch.no_grad():
+        for mod in model.modules():
+            if mod.__class__.__name__ == 'ZeroConv2d':
+                for t in (mod.conv.weight, mod.conv.bias, mod.scale):
+                    t.add_(0.02 * torch.randn(t.shape, generator=g))
+            if mod.__class__.__name__ == 'InvConv2d':
+                c = mod.weight.shape[0]
+                scale = 0.5 + 1.5 * torch.rand(c, generator=g)                 # singular values in [0.5, 2]
+                mod.weight.copy_((mod.weight[:, :, 0, 0] * scale + 0.05 * torch.randn(c, c, generator=g))[:, :, None, None])
+    sd0 = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    arrays = np_state(sd0, 'sd/')
+    arrays['layout'] = _cgan_layout({k: tuple(v.shape) for k, v in sd0.items()})
+    img, lab = gu.synthetic_batch(4, classes, seed=61, shape=(channels, 32, 32))
+    lab[0] = 1; lab[1] = classes - 1; lab[2] = 1; lab[3] = 0
+    arrays['img'] = img.numpy(); arrays['label'] = lab.numpy()
+    with _PatchedNoise(400) as pn, torch.no_grad():                       # train_glow.py:60-67 data-dependent init
+        model({'img': img.clone(), 'label': lab})
+    arrays['noise/init/0'] = pn.drawn[0].numpy()
+    sdi = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    arrays.update(np_state({k: v for k, v in sdi.items() if not torch.equal(v, sd0[k])}, 'sd_init/'))
+    opt = torch.optim.Adam(model.parameters(), lr=3e-4)
+    losses = []
+    for s in range(2):
+        with _PatchedNoise(500 + s) as pn:
+            opt.zero_grad()
+            out = model({'img': img.clone(), 'label': lab})
+            out['loss'].backward()
+        arrays[f'noise/{s}/0'] = pn.drawn[0].numpy()
+        if s == 0:
+            for i, z in enumerate(out['z']):
+                arrays[f'z0/{i}'] = z.detach().numpy()
+            for k, p in model.named_parameters():
+                arrays['grad0/' + k] = p.grad.detach().numpy().copy()
+        torch.nn.utils.clip_grad_norm_(model.parameters(), 1)
+        opt.step()
+        losses.append(out['loss'].item())
+    arrays['losses'] = np.array(losses, dtype=np.float64)
+    for k, v in model.state_dict().items():
+        if not torch.equal(v, sdi[k]):
+            arrays['sd_final_delta/' + k] = (v - sdi[k]).detach().numpy()
+    model.train(False)
+    with torch.no_grad(), _PatchedNoise(600) as pn:
+        out = model({'img': img.clone(), 'label': lab})
+        arrays['noise/eval/0'] = pn.drawn[0].numpy()
+        arrays['loss_eval'] = np.array(out['loss'].item())
+        rec = model.reverse({'z': out['z'], 'label': lab, 'reconstruct': True})['img']
+        arrays['reconstructed'] = rec.numpy()
+        gz = [torch.randn(4, *s, generator=torch.Generator().manual_seed(7 + i)) * 0.7 for i, s in enumerate(model.make_z_shapes())]
+        for i, z in enumerate(gz):
+            arrays[f'gen_z/{i}'] = z.numpy()
+        arrays['generated'] = model.generate(lab, gz).numpy()
+    for k, v in arrays.items():                       # loss_fn zeroes NaN samples: a NaN in a fixture would hide errors
+        assert v.dtype.kind != 'f' or np.isfinite(v).all(), k
+    if step_file:                       # the 3-channel model's arrays do not fit one file of the size a committed file may have
+        step = {k: arrays.pop(k) for k in list(arrays) if k.startswith(('grad0/', 'sd_final_delta/'))}
+        save(step_file, **step)
+    save(name, **arrays)
+
+
+def fx_mcglow_additive_small():
+    _mcglow_variant_small('mcglow_additive_small.npz', 1, 12, False, True)
+
+
+def fx_mcglow_plainconv_small():
+    _mcglow_variant_small('mcglow_plainconv_small.npz', 1, 12, True, False)
+
+
+def fx_mcglow_plain_additive_cifar_small():
+    _mcglow_variant_small('mcglow_plain_additive_cifar_small.npz', 3, 10, False, False,
+                          step_file='mcglow_plain_additive_cifar_small_step.npz')
+
+
+FIXTURES.update(mcglow_additive_small=fx_mcglow_additive_small, mcglow_plainconv_small=fx_mcglow_plainconv_small,
+                mcglow_plain_additive_cifar_small=fx_mcglow_plain_additive_cifar_small)
+
 # ---- create / transit on the label-embedding baselines (models/utils.py:47-88, 112-152) and the created set's DBI -------------
 def _surgery_generate(model, name, label, x):
     """Eval-mode generate of the reference; cpixelcnn: the greedy decode (argmax per position through reference forwards,
