@@ -31,7 +31,7 @@ extern "C" {
 enum { MCGEN_F32 = 0, MCGEN_BF16 = 1 };
 
 const char* mcgen_last_error(void);
-int mcgen_abi_version(void);      /* 9 (additions since, without a bump: the baseline models' entry points, mcgen_conv_plan): mcgen_conv_t.y_group (paired output layout of the image head), mcgen_onehot_rep, MCGEN_WREDUCE_MAX 32, mcgen_dtail_hinge_fused, mcgen_wgrad_c8_ok + tapcols slabs (mcgen_wgrad_reduce gained an argument), mcgen_mc_gather_batch(n_label, scale, n_half), mcgen_conv_t.wsel / wsel_stride / order / yperm + mcgen_prep_t.kmap / rmap (per-mode dense weight sets), mcgen_prep_weight_batch_codes, mcgen_wgrad_batch, mcgen_bn_finalize_batch, mcgen_gated_fwd_batch, mcgen_wreduce_t.tap0 / ntap_out; 8: mcgen_adam / mcgen_sn_fix_pair_adam take lr_dev (learning rate read on the device at execution time); 7: + mcgen_conv_form, mcgen_sn_power_iter_rounds, the MCGlow *_batch entry points, mcgen_sn_fix_pair_adam(advance_step); 6: + mcgen_wgrad_multi (5: + mcgen_conv_t.bias2, mcgen_sn_power_iter_snap; 4: compacted activations between forward-only launches) */
+int mcgen_abi_version(void);      /* 9 (additions since, without a bump: the baseline models' entry points, mcgen_conv_plan): mcgen_conv_t.y_group (paired output layout of the image head), mcgen_onehot_rep, MCGEN_WREDUCE_MAX 32, mcgen_dtail_hinge_fused, mcgen_wgrad_c8_ok + tapcols slabs (mcgen_wgrad_reduce gained an argument), mcgen_mc_gather_batch(n_label, scale, n_half), mcgen_conv_t.wsel / wsel_stride / order / yperm + mcgen_prep_t.kmap / rmap (per-mode dense weight sets), mcgen_conv_t.wlive (live chunks per weight set; yperm_stride moved into the padding behind nseg to make room: sizeof stays 352, a hand-written mirror of the struct must follow), mcgen_prep_weight_batch_codes, mcgen_wgrad_batch, mcgen_bn_finalize_batch, mcgen_gated_fwd_batch, mcgen_wreduce_t.tap0 / ntap_out; 8: mcgen_adam / mcgen_sn_fix_pair_adam take lr_dev (learning rate read on the device at execution time); 7: + mcgen_conv_form, mcgen_sn_power_iter_rounds, the MCGlow *_batch entry points, mcgen_sn_fix_pair_adam(advance_step); 6: + mcgen_wgrad_multi (5: + mcgen_conv_t.bias2, mcgen_sn_power_iter_snap; 4: compacted activations between forward-only launches) */
 
 /* One K-segment of a fused convolution: the input tensor and the prologue that
  * is applied while the tile is staged into LDS:
@@ -87,6 +87,8 @@ typedef struct {
 typedef struct {
     mcgen_seg_t  seg[2];
     int32_t      nseg;
+    int32_t      yperm_stride;   /* int16 elements per row of `yperm` (below).  It sits here, in what was alignment padding, so
+                                  * that `wlive` fits at the end without growing the struct (352 bytes)              */
     const void*  w;        /* weight image from mcgen_prep_weight (all segments, in order) */
     const float* bias;     /* [Cout] or NULL                                               */
     void*        y;        /* [N, Ho, Wo, Cy]  (Ho = H>>pool)                              */
@@ -139,7 +141,15 @@ typedef struct {
                             * statistics (pitch Cout_w) are indexed through the permutation, i.e. stay in true channel order.
                             * Columns between an image's active count and Cy hold channels its consumer masks: the consumer's
                             * weight image has zero columns there (mcgen_prep_t.kmap).  Same restrictions as ycmap.       */
-    int32_t yperm_stride, reserved_;
+    const int32_t* wlive;  /* [sets][nseg] or NULL (with wsel; the dense software-pipelined form and the image head): LIVE 32-channel
+                            * chunks of segment s in weight set m -- ceil(active channels of the mode / 32) where the segment's image
+                            * was built through mcgen_prep_t.kmap (zero columns behind the active ones), the segment's full chunk
+                            * count (or anything larger) elsewhere.  The tile of an image with set m = wsel[i] runs
+                            * min(wlive[m * nseg + s], chunks of the segment) K steps of segment s; entries below 0 count as 0.  Only
+                            * loop bounds follow it: the image layout, the window pitch and the table rows stay those of seg[s].C.
+                            * Any count from 0 up runs through the same pipeline (tests/test_live_chunks_gpu.py).  The skipped
+                            * chunks must multiply zero weights: their products then vanish for finite activations.  NULL: every
+                            * chunk of the pitch.                                                                              */
 } mcgen_conv_t;
 
 /* What mcgen_conv_fused will do with `p`: the launcher it hands `p` to and, for the launchers inside conv_fused.hip, the
@@ -304,7 +314,9 @@ int mcgen_mc_cmap(const float* code, int N, int C, int16_t* cmap, void* stream);
 int mcgen_nchw_to_nhwc(const float* src, void* dst, int dtype, int N, int C, int H, int W, int Cp, void* stream);
 /* out[r][i][m] = (label[i] == m) for r < reps: F.one_hot(label, classes).float() (mcgan.py:196,201) written `reps` times back to
  * back -- the indicator of a paired discriminator batch (2 N rows) and of the grouped generator pass (d_iters * N rows) are
- * prefixes of one such buffer.  Labels outside [0, classes) fail the launch's precondition (the row stays all zero). */
+ * prefixes of one such buffer.  A label outside [0, classes) leaves its indicator row all zero; lab32 (int32 [reps * N] or
+ * NULL: the labels themselves, repeated -- what mcgen_conv_t.wsel indexes weight sets and live-chunk tables with) receives
+ * it CLAMPED into [0, classes), as mcgen_mc_gather_batch clamps the row it gathers. */
 int mcgen_onehot_rep(const int64_t* label, float* out, int* lab32, int N, int classes, int reps, void* stream);
 int mcgen_nhwc_to_nchw(const void* src, float* dst, int dtype, int N, int C, int H, int W, int Cp, void* stream);
 /* y[N, Ho, Wo, C] = 2x2 sums of x[N, 2 Ho, 2 Wo, C] (NHWC, C a multiple of 8): the adjoint of the nearest x2 upsample.

@@ -1740,6 +1740,9 @@ void conv_gk_kernel(const mcgen_conv_t p, const int a_bytes) {
 // Every wave issues the same VMEM sequence per phase (window loads are unconditional, clamped to a valid address; the
 // DMAs past the last tap re-load it into the free slot), so the vmcnt counts are compile-time constants (pp_vmcnt_*).
 // Further (1x1) segments run after the pipeline has drained, as in the dma3 form, on window buffer 0 and ring slots 0 / 1.
+// The chunk count of a segment is a run-time, workgroup-uniform value: the segment's own (dense), the image's active ones
+// (GK) or the live ones of the tile's weight set (dense with mcgen_conv_t.wlive); every count from 0 up takes the same
+// prologue, counted waits and drain (0: the segment is skipped; tests/test_live_chunks_gpu.py walks 0, 1, 2, 3 and the pitch).
 template <int I, int E, typename F>
 static __device__ __forceinline__ void pp_static_for(F&& f) {
     if constexpr (I < E) { f(std::integral_constant<int, I>{}); pp_static_for<I + 1, E>(f); }
@@ -1851,7 +1854,20 @@ void conv_pp_kernel(const mcgen_conv_t p, const int a_bytes) {
     };
     const int16_t* cidx0 = nullptr; int cw0 = C0, cnt0 = C0;
     if constexpr (GK) seg_info(0, cidx0, cw0, cnt0);
-    const int nchunk = GK ? ((cnt0 + 31) >> 5) : (C0 >> 5), T0 = nchunk * 9;
+    // Chunks this tile MULTIPLIES.  GK: the image's.  Dense with per-mode weight sets: the set's live ones (mcgen_conv_t.wlive,
+    // workgroup-uniform, clamped to [0, C0 / 32]) -- behind them the set's image holds zero columns.  Only the loop bounds
+    // follow it (nchunk, T0 = the taps of the loop, past which the ring re-loads the last tap): the image layout does not
+    // shrink -- the tail segments' blocks stay behind (C0 / 32) * 9 --, nor does anything else derived from C0 (window pitch,
+    // table rows).  Any count runs: 0 skips the segment as a GK image without active channels does, 1 re-stages its only
+    // chunk into the idle buffer; the wait counts (pp_vmcnt_*) are per phase and do not know the bound.
+    int nlive0 = C0 >> 5;
+    if constexpr (!GK) {
+        if (p.wlive) {
+            const int v = __builtin_amdgcn_readfirstlane(p.wlive[wset * p.nseg]);
+            nlive0 = v < 0 ? 0 : (v < nlive0 ? v : nlive0);
+        }
+    }
+    const int nchunk = GK ? ((cnt0 + 31) >> 5) : nlive0, T0 = nchunk * 9;
     const size_t tapstride0 = (size_t)(cw0 + 1) * p.Cout_w * 2;          // (GK) bytes per tap of segment 0's image
 
     // ---- weight DMA: piece k of this wave -> ring slot -----------------------------------------------------------------
@@ -2118,14 +2134,22 @@ void conv_pp_kernel(const mcgen_conv_t p, const int a_bytes) {
         // (GK: one further segment; its chunks are the image's active ones)
         const int16_t* cidx1 = nullptr; int cw1 = 8, cnt1 = 0;
         if constexpr (GK) { seg_info(1, cidx1, cw1, cnt1); nrest = (cnt1 + 31) >> 5; }
-        else for (int s = 1; s < p.nseg; ++s) nrest += (p.seg[s].C + MCGEN_CK - 1) / MCGEN_CK;
+        else {
+            // (the launch has at most two segments; per-mode weight sets: the live chunks of the set's shortcut image)
+            nrest = (p.seg[1].C + MCGEN_CK - 1) / MCGEN_CK;
+            if (p.wlive) {
+                const int v = __builtin_amdgcn_readfirstlane(p.wlive[wset * p.nseg + 1]);
+                nrest = v < 0 ? 0 : (v < nrest ? v : nrest);
+            }
+        }
+        const int Tseg1 = (C0 >> 5) * 9;                      // dense: the first tail block of the image, whatever segment 0 multiplied
         const char* wseg1 = wimg + 9 * tapstride0;
         const size_t tapstride1 = (size_t)(cw1 + 1) * p.Cout_w * 2;
         auto tail_dma = [&](int t, int slot) {
 #pragma unroll
             for (int k = 0; k < PPW; ++k) {
                 if constexpr (GK) dma_piece_gk(wseg1, tapstride1, ksel(cidx1, cw1, t, k) * p.Cout_w * 2 + d_src[k], 0, slot, k);
-                else dma_piece(T0 + t, slot, k);
+                else dma_piece(Tseg1 + t, slot, k);
             }
         };
         pp_barrier();                                          // every wave is past its last ring / window read
@@ -2151,7 +2175,7 @@ void conv_pp_kernel(const mcgen_conv_t p, const int a_bytes) {
             PatchStager<T, NT, NI1, APITCH> stager;
             stager.setup(sg, g, N, H, W, tid);
             const int b_lane = (wm * (BM / WM) + l15) * APITCH + lg * 16;
-            const int nch = GK ? nrest : (sg.C + MCGEN_CK - 1) / MCGEN_CK;
+            const int nch = nrest;
 #pragma unroll 1
             for (int q0 = 0; q0 < nch; q0 += TG) {
                 const int ng = (nch - q0) < TG ? (nch - q0) : TG;
@@ -2570,6 +2594,7 @@ static int validate(const mcgen_conv_t* p, bool launching) {
         MCGEN_CHECK(p->w_layout == 0 && (p->y_group == 0 || !p->order), "conv_fused: per-mode weight sets (wsel / order) go with the chunked weight image (w_layout 0)");
         MCGEN_CHECK(!p->wsel || p->wsel_stride > 0, "conv_fused: wsel needs wsel_stride");
     }
+    MCGEN_CHECK(!p->wlive || p->wsel, "conv_fused: live chunk counts (wlive) are per weight set: they come with wsel");
     if (p->yperm) {
         MCGEN_CHECK(p->wsel && !p->order && !p->ycmap, "conv_fused: permuted weight rows (yperm) come with wsel, without order / ycmap");
         MCGEN_CHECK(!p->pool && !p->res && !p->gate_x && !p->ocode && !p->tanh_out, "conv_fused: a compacted output takes bias and statistics only");

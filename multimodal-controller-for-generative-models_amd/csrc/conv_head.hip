@@ -12,7 +12,8 @@
 //   * the chunk's nine 16 x 32 weight fragments come straight from the [chunk][tap][16][32] image into registers;
 //   * the epilogue stores 8 bytes per lane straight from the accumulators (channels 0 .. 3 | 4 .. 7 of the 8-channel pitch).
 // In the grouped forward-only pass the input arrives COMPACTED (160 of 256 channels, per-image affine rows from mcgen_mc_affine,
-// the image's mode's own weight image: mcgen_conv_t.wsel): 5 chunks instead of 8.
+// the image's mode's own weight image: mcgen_conv_t.wsel): 5 chunks instead of 8, and of those only the mode's live ones
+// (mcgen_conv_t.wlive: ceil(active channels / 32), 4 for about half of the modes; the time follows the chunk count).
 // Measured 151-178 us at N = 640 (2.0-2.3 TB/s of input; same-box 3 % under the general tile's step).  What did NOT move it
 // (same-box, tools/so_shapes.sh): pixels of two chunks in flight, weight fragments a chunk ahead (192 registers: one
 // workgroup per CU, 201 us), one workgroup per CU with the shallow pipeline, 64-channel steps (whole 128-byte lines per
@@ -35,7 +36,15 @@ void conv_head_kernel(const mcgen_conv_t p) {
     const int l15 = lane & 15, lg = lane >> 4;
     const int n = blockIdx.x >> 2, h0 = (blockIdx.x & 3) * HD_ROWS;
     const mcgen_seg_t sg = p.seg[0];
-    const int C = sg.C, nchunk = C >> 5;
+    const int C = sg.C;
+    // chunks this workgroup multiplies: all of the pitch, or the live ones of the image's weight set (mcgen_conv_t.wlive,
+    // clamped to [0, C / 32]; behind them the set's image holds zero columns).  Offsets keep following C.
+    const int wset = p.wsel ? p.wsel[n] : 0;
+    int nchunk = C >> 5;
+    if (p.wlive) {
+        const int v = __builtin_amdgcn_readfirstlane(p.wlive[wset]);
+        nchunk = v < 0 ? 0 : (v < nchunk ? v : nchunk);
+    }
     const float* anyf = reinterpret_cast<const float*>(p.w);
     const size_t arow = sg.group_n > 0 ? (size_t)(n / sg.group_n) * C : 0;      // the image's BatchNorm group
     const float* scp = sg.scale ? sg.scale + arow : anyf;
@@ -84,7 +93,7 @@ void conv_head_kernel(const mcgen_conv_t p) {
     f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
     // weight fragment (chunk q, tap j): rows l15 (16 channels), elements 8 lg .. of [chunk][tap][16][32]
     // (per-mode weight sets, mcgen_conv_t.wsel: the image's own dense image over its compacted channels)
-    const bf16_t* wimg = reinterpret_cast<const bf16_t*>(p.w) + (p.wsel ? (size_t)p.wsel[n] * (size_t)p.wsel_stride : 0) + (size_t)l15 * MCGEN_CK + lg * 8;
+    const bf16_t* wimg = reinterpret_cast<const bf16_t*>(p.w) + (size_t)wset * (size_t)p.wsel_stride + (size_t)l15 * MCGEN_CK + lg * 8;
     load_chunk(0);
     write_chunk(smem);
 #pragma unroll 1

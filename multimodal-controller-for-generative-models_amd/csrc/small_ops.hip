@@ -1285,7 +1285,11 @@ __global__ void onehot_rep_kernel(const int64_t* __restrict__ label, float* __re
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
         const int e = i % per, row = e / classes, m = e - row * classes;
         out[i] = (label[row] == (int64_t)m) ? 1.f : 0.f;
-        if (lab32 && m == 0) lab32[(i / per) * n + row] = (int)label[row];
+        // (lab32 indexes per-mode tables -- mcgen_conv_t.wsel / wlive: clamped into [0, classes) as mc_gather_body clamps)
+        if (lab32 && m == 0) {
+            const int64_t l = label[row];
+            lab32[(i / per) * n + row] = l < 0 ? 0 : (l >= (int64_t)classes ? classes - 1 : (int)l);
+        }
     }
 }
 }  // namespace

@@ -107,6 +107,9 @@ _PM = _flag('MCGEN_PM', '1') != '0'
 _PREP_CODES = _flag('MCGEN_PREP_CODES', '1') != '0'   # a discriminator pass's codes ride in its weight-image launch
 _PM_HEAD = _flag('MCGEN_PM_HEAD', '1') != '0'         # the last block stores its output compacted for the image head
 _PM_MAX_MODES = 16
+# per-mode launches stop their K loops at the mode's live 32-channel chunks (mcgen_conv_t.wlive; 0: walk the whole pitch)
+_PM_LIVE = _flag('MCGEN_PM_LIVE', '1') != '0'
+LIVE_ALL = 1 << 20                                    # a wlive entry of a segment without zero columns: every chunk
 class Nhwc:
     """An image batch in the engines' own layout ([N, H, W, C padded to 8] of the compute dtype, padding channels zero) with
     its true channel count: what the trainer hands from one engine to the other, instead of converting to the module
@@ -325,6 +328,44 @@ class GeneratorEngine:
         cap = (int((cb != 0).sum(1).max()) + 31) // 32 * 32
         return cap if cap <= cb.shape[1] * 3 // 4 and float(cb.min()) >= 0.0 else None
 
+    def live_chunks(self) -> Dict[str, Tensor]:
+        """{per-mode image: int32 [modes, segments]}: mcgen_conv_t.wlive of the launch that reads the image -- for a segment
+        whose image was built through a mode's compaction record (ImageJob.kmap) ceil(the mode's active channels / 32): the
+        chunks in front of that image's zero columns; for a dense segment LIVE_ALL (the kernel clamps to the segment's own).
+        Rebuilt with the plan, i.e. when a codebook changes (create / transit); a table keeps its address while its shape
+        stays, so captured graphs keep reading it."""
+        plan = self._plan()
+        if self.__dict__.get('_live_plan') is not plan:
+            mcs = self._codes.mcs
+            cb0 = mcs[0].codebook
+            if cb0.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise McgenError('compacted generator pass: a codebook changed since the last eager pass; call '
+                                 'GeneratorEngine.warm_caps() before capturing')
+            modes = cb0.shape[0]
+            by_image: Dict[str, list] = {}
+            for j in plan.jobs:
+                by_image.setdefault(j.buffer, []).append(j)
+            old, self._live = self.__dict__.get('_live', {}), {}
+            chunks = {}                                  # controller -> int32 [modes]
+            for name, jobs in by_image.items():
+                if not any(j.kmap for j in jobs):
+                    continue
+                nseg = len(jobs) // modes                # (a per-mode buffer: `modes` images, each its segments in order)
+                cols = []
+                for j in jobs[:nseg]:
+                    c = j.kmap[0] if j.kmap else None
+                    if c is not None and c not in chunks:
+                        chunks[c] = ((mcs[c].codebook != 0).sum(1).to(torch.int32) + 31) // 32
+                    cols.append(chunks[c] if c is not None else torch.full((modes,), LIVE_ALL, dtype=torch.int32, device=cb0.device))
+                t = torch.stack(cols, 1).contiguous()
+                keep = old.get(name)
+                if keep is not None and keep.shape == t.shape and keep.device == t.device:
+                    keep.copy_(t)
+                    t = keep
+                self._live[name] = t
+            self._live_plan = plan
+        return self._live
+
     def warm_caps(self):
         """Build the plan of the current codebooks (a host synchronisation) and the per-mode tables it lists: graph capture
         calls this after it has restored the model state, so that the captured pass finds them cached."""
@@ -334,6 +375,7 @@ class GeneratorEngine:
         for j in {j.rmap[0] for j in plan.jobs if j.rmap}:
             self._mode_perms(mcs[j])
         self._stacked_maps(plan)
+        self.live_chunks()
 
     # ---- forward ---------------------------------------------------------------------------------
     def groups_supported(self, n_total: int, groups: int) -> bool:
@@ -403,6 +445,7 @@ class GeneratorEngine:
             wsel = hint[2] if len(hint) > 2 and hint[2] is not None else hint[0].to(torch.int32).repeat(hint[1])
             # one-hot samples: an image's compaction record is its mode's -- one row gather for every map of the pass
             cmaps = self._gather_cmaps(plan, wsel)
+        live = self.live_chunks() if kind == 'pm' and _PM_LIVE else {}
 
         def compacted(j, cap):                     # (per-image compaction records of controller j, pitch), None: dense
             return ((cmaps[j] if j in cmaps else ops.mc_cmap(codes[j])), cap) if cap else None
@@ -429,7 +472,7 @@ class GeneratorEngine:
             # (mc: the K loop visits only each sample's active channels -- mode-compacted kernel, K-major image)
             seg_a = seg(x, code1, x_cm, bn1, r.a.form == 'gk', ops.mc_cmap(code1) if r.a.form == 'mc' else None, ups=True, relu=True)
             # (pm: a dense K loop on the mode's own image, the output compacted through the image's row order; else by its map)
-            how = dict(wsel=wsel, yperm=self._mode_perms(b.mc_2)) if r.a.form == 'pm' else \
+            how = dict(wsel=wsel, yperm=self._mode_perms(b.mc_2), wlive=live.get(r.a.image)) if r.a.form == 'pm' else \
                 dict(kmajor=gen_plan.LAYOUT[r.a.form], ycmap=cm_h[0] if cm_h else None)
             h, st_h = ops.conv_fused([seg_a], self.img[r.a.image], co, bias=conv_a.bias, stats_mode=st_mode, cy=r.cap_h, **how)
             bn2 = _bn_forward(b.conv[5].module, st_h, ng * 4 * s * s, train, 1, groups)
@@ -443,7 +486,7 @@ class GeneratorEngine:
                 # (the shortcut's own bias rides along as bias2: the sum is formed in fp32 in front of the accumulator)
                 how = dict(bias=conv_b.bias, bias2=conv_s.bias)
                 if r.b.form == 'pm':
-                    how.update(wsel=wsel, yperm=self._mode_perms(self._codes.mcs[r.y_ctrl]) if cm_y else None)
+                    how.update(wsel=wsel, yperm=self._mode_perms(self._codes.mcs[r.y_ctrl]) if cm_y else None, wlive=live.get(r.b.image))
             y, st = ops.conv_fused(segs, self.img[r.b.image], co, stats_mode=st_mode, cy=r.cap_y, **how)
             blocks_ctx.append(dict(x=x, h=h, code1=code1, code2=code2, bn1=bn1, bn2=bn2))
             x, x_cm = y, cm_y
@@ -452,6 +495,7 @@ class GeneratorEngine:
         codeh = codes[-1]
         seg_h = seg(x, codeh, x_cm, bnh, relu=True)
         hw, hsel = self.img[route.head], (wsel if x_cm else None)       # 'headm': the head reads its mode's compacted image
+        hlive = live.get(route.head) if hsel is not None else None
         cimg = head_conv.out_channels
         if pair_out is not None:
             if tuple(pair_out.shape) != (2 * n, x.shape[1], x.shape[2], ops.pad8(cimg)) or pair_out.dtype != dt:
@@ -460,14 +504,14 @@ class GeneratorEngine:
             direct = (dt == torch.bfloat16 and x.shape[1] == 32 and x.shape[2] == 32 and cimg <= 8 and x.shape[-1] % 32 == 0
                       and x.shape[-1] >= 64 and n * 32 * 32 * x.shape[-1] < (1 << 31))
             if direct:
-                ops.conv_fused([seg_h], hw, cimg, bias=head_conv.bias, tanh=True, out=pair_out, y_group=ng, wsel=hsel)
+                ops.conv_fused([seg_h], hw, cimg, bias=head_conv.bias, tanh=True, out=pair_out, y_group=ng, wsel=hsel, wlive=hlive)
                 out = None
             else:
-                out, _ = ops.conv_fused([seg_h], hw, cimg, bias=head_conv.bias, tanh=True, wsel=hsel)
+                out, _ = ops.conv_fused([seg_h], hw, cimg, bias=head_conv.bias, tanh=True, wsel=hsel, wlive=hlive)
                 pv = pair_out.view(groups, 2 * ng, *pair_out.shape[1:])
                 pv[:, ng:].copy_(out.view(groups, ng, *out.shape[1:]))
         else:
-            out, _ = ops.conv_fused([seg_h], hw, cimg, bias=head_conv.bias, tanh=True, wsel=hsel)
+            out, _ = ops.conv_fused([seg_h], hw, cimg, bias=head_conv.bias, tanh=True, wsel=hsel, wlive=hlive)
         ctx.update(blocks=blocks_ctx, y=x, bnh=bnh, codeh=codeh, out=out)
         _flush_counters()
         if pair_out is not None:

@@ -351,7 +351,7 @@ def conv_fused(segs: Sequence[Seg], wimg: Tensor, cout: int, *, bias: Optional[T
                tanh: bool = False, stats_mode: int = 0, cy: Optional[int] = None,
                out: Optional[Tensor] = None, kmajor: int = 0, ycmap: Optional[Tensor] = None,
                y_group: int = 0, wsel: Optional[Tensor] = None, order: Optional[Tensor] = None,
-               yperm: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
+               yperm: Optional[Tensor] = None, wlive: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
     """Launch mcgen_conv_fused; returns (y, per-tile stats partials or None).  `kmajor`: `wimg` is the K-major image
     (prep_weight_k, segments concatenated); 1: every segment carries a compaction map and is compacted while staged;
     2: segments hold ALREADY compacted channels (Seg.cw, cmap) or are dense.  `ycmap` (+ `cy` = compacted pitch): the
@@ -362,7 +362,8 @@ def conv_fused(segs: Sequence[Seg], wimg: Tensor, cout: int, *, bias: Optional[T
     the segments' (compacted) shapes back to back, the image walked at position i is order[i] and multiplies weight set
     wsel[i] (mcgen_conv_t.wsel: bf16, software-pipelined form only).  `yperm` (int16 [S, stride], with wsel and `cy`): the sets'
     weight ROWS were permuted at prep time (PrepBatch rmap = yperm[s]): the output comes out compacted (pitch cy) without a
-    gather pass; bias and statistics stay in true channel order (mcgen_conv_t.yperm)."""
+    gather pass; bias and statistics stay in true channel order (mcgen_conv_t.yperm).  `wlive` (int32 [S, len(segs)], with
+    wsel): the live 32-channel chunks of every segment of every set -- a tile stops its K loops there (mcgen_conv_t.wlive)."""
     s0 = segs[0]
     n = s0.x.shape[0]
     h = s0.x.shape[1] * (2 if s0.ups else 1)
@@ -421,6 +422,12 @@ def conv_fused(segs: Sequence[Seg], wimg: Tensor, cout: int, *, bias: Optional[T
         if wsel is None or yperm.dtype != torch.int16 or yperm.dim() != 2 or yperm.shape[0] * need != wimg.numel() or not yperm.is_contiguous():
             raise _lib.McgenError('yperm must be a contiguous int16 [sets, stride] table that comes with wsel')
         p.yperm, p.yperm_stride = _p(yperm), yperm.shape[1]
+    p.wlive = None
+    if wlive is not None:
+        if wsel is None or wlive.dtype != torch.int32 or not wlive.is_contiguous() or \
+                tuple(wlive.shape) != (wimg.numel() // need, len(segs)) or wlive.device != wimg.device:
+            raise _lib.McgenError('wlive must be a contiguous int32 [sets, segments] table that comes with wsel')
+        p.wlive = _p(wlive)
     p.ycmap, p.ycmap_stride = None, 0
     if ycmap is not None:
         if ycmap.dtype != torch.int16 or tuple(ycmap.shape) != (n, cmap_stride(pad8(cout))):
