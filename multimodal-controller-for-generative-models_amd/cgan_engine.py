@@ -19,9 +19,9 @@ from typing import Dict, Optional
 
 import torch
 
-from . import ops
+from . import dis_plan, ops
 from ._lib import McgenError
-from .gan_engine import (DiscriminatorEngine, FlatState, Nhwc, _LOWRES_SC_BWD, _SNConv, _bn_forward, _flush_counters,
+from .gan_engine import (DiscriminatorEngine, FlatState, Nhwc, _LOWRES_SC_BWD, _bn_forward, _flush_counters,
                          _pending_counters, _pending_running)
 from .ops import PrepJob, Seg
 
@@ -221,9 +221,7 @@ class CGeneratorEngine:
         y, bnh = ctx['y'], ctx['bnh']
         c_img, c = head_conv.out_channels, head_conv.in_channels
         G = lambda p: self.flat_p.view_of(gflat, p)                           # noqa: E731
-        red = ops.deferred_reduces()
-        red.__enter__()
-        try:
+        with ops.deferred_reduces():
             ops.wgrad(Seg(y, scale=bnh.scale, shift=bnh.shift, relu=True), dtn, c_img, c, G(head_conv.weight), accumulate=acc,
                       bias_grad=G(head_conv.bias))
             dz, part = ops.conv_fused([Seg(dtn)], self.img_t['head'], c, gate_x=y, gscale=bnh.scale, gshift=bnh.shift,
@@ -265,10 +263,6 @@ class CGeneratorEngine:
             # embedding: its columns of the Linear's input gradient, summed per label (cgan.py:58)
             de = ops.cgan_lin_dembed(dy, lin.weight.detach(), lin.in_features - emb.out_features, emb.out_features)
             ops.cgan_embed_bwd(de, ctx['label'], G(emb.weight), accumulate=acc)
-        except BaseException as e:
-            red.__exit__(type(e), e, None)
-            raise
-        red.__exit__(None, None, None)
         yield (0, gflat.numel(), True)
 
 
@@ -280,91 +274,23 @@ class CDiscriminatorEngine(DiscriminatorEngine):
     one more SN layer, 32 x num_mode); the forward and backward passes are CGAN's own."""
 
     def __init__(self, dis, dtype: torch.dtype = torch.float32):
-        self.dis = dis
-        self.dtype = dtype
-        blocks = list(dis.blocks.children())
-        self.res = [b for b in blocks if hasattr(b, 'shortcut')]
-        self.tail_lin = blocks[len(self.res) + 2]              # ReLU, GlobalSumPooling, Linear (cgan.py:150-152)
-        self.sn = []
-        for m in dis.modules():
-            if hasattr(m, 'weight_orig'):
-                self.sn.append(_SNConv(m, len(self.sn)))
-        self.sn_of = {s.m: s for s in self.sn}
-        params = list(dis.parameters())
-        sn_w = {id(s.m.weight_orig) for s in self.sn}
-        self.plain = [p for p in params if id(p) not in sn_w]
-        self.flat_p = FlatState(params)
-        uv = []
-        for s in self.sn:
-            uv += [s.m.weight_u, s.m.weight_v]
-        self.flat_uv = FlatState(uv)
-        self._layers_dev = None
-        self._layers_key = None
-        self._prep_fwd = self._prep_bwd = None
-        self._prep_dimg = None
-        self.img: Dict[str, Tensor] = {}
-        self.emb = self.sn_of[dis.embedding]
+        super().__init__(dis, dtype)
+        self.emb = next(s for s in self.sn if s.m is dis.embedding)
         self.cimg = dis.data_shape[0]
 
-    def _block(self, i):
-        """(conv1, conv2, shortcut conv or None, pooled) of residual block i as _SNConv (cgan.py:65-123)."""
-        b = self.res[i]
-        if i == 0:
-            return self.sn_of[b.conv[0]], self.sn_of[b.conv[2]], self.sn_of[b.shortcut[0]], True
-        pooled = len(b.conv) == 5
-        sc = self.sn_of[b.shortcut[0]] if len(b.shortcut) > 0 else None
-        return self.sn_of[b.conv[1]], self.sn_of[b.conv[3]], sc, pooled
-
-    def _build_preps(self):
-        dt = self.dtype
-        dev = self.flat_p.flat.device
-        self.img = {}
-
-        def img(name, s: _SNConv, transpose):
-            t = torch.empty(ops.weight_image_elems(s.cout, s.cin, s.ks, transpose), dtype=dt, device=dev)
-            self.img[name] = t
-            return t
-
-        def cat(name, a: _SNConv, b: _SNConv, transpose):
-            na = ops.weight_image_elems(a.cout, a.cin, a.ks, transpose)
-            nb = ops.weight_image_elems(b.cout, b.cin, b.ks, transpose)
-            t = torch.empty(na + nb, dtype=dt, device=dev)
-            self.img[name] = t
-            return t[:na], t[na:]
-
-        fwd, bwd = [], []
-        W = lambda s: s.m.weight_orig                                         # noqa: E731
-        c1m, c2m, scm, _ = self._block(0)
-        fwd.append(PrepJob(W(c1m), img('0.c1', c1m, False), False, 1, c1m.idx, 1.0))
-        ta, tb = cat('0.c2s', c2m, scm, False)
-        fwd += [PrepJob(W(c2m), ta, False, 1, c2m.idx, 1.0), PrepJob(W(scm), tb, False, 1, scm.idx, 1.0)]
-        bwd.append(PrepJob(W(c2m), img('0.c2t', c2m, True), True, 1, c2m.idx, 0.25))
-        for i in range(1, len(self.res)):
-            c1m, c2m, scm, pooled = self._block(i)
-            a = 0.25 if pooled else 1.0
-            fwd.append(PrepJob(W(c1m), img(f'{i}.c1', c1m, False), False, 1, c1m.idx, 1.0))
-            if scm is not None:
-                ta, tb = cat(f'{i}.c2s', c2m, scm, False)
-                fwd += [PrepJob(W(c2m), ta, False, 1, c2m.idx, 1.0), PrepJob(W(scm), tb, False, 1, scm.idx, 1.0)]
-                bwd.append(PrepJob(W(scm), img(f'{i}.sct', scm, True), True, 1, scm.idx, a))
-            else:
-                fwd.append(PrepJob(W(c2m), img(f'{i}.c2', c2m, False), False, 1, c2m.idx, 1.0))
-            bwd += [PrepJob(W(c2m), img(f'{i}.c2t', c2m, True), True, 1, c2m.idx, a),
-                    PrepJob(W(c1m), img(f'{i}.c1t', c1m, True), True, 1, c1m.idx, 1.0)]
-        self._prep_fwd, self._prep_bwd = ops.PrepBatch(fwd, dt), ops.PrepBatch(bwd, dt)
-        self._prep_all = ops.PrepBatch(fwd + bwd, dt)
-        self._bwd_sigma = None
-        # the generator update's input gradient: the IMAGE channels of the first block's conv1 / 1x1 shortcut only
-        # (persistent fp32 copies of those weight columns, refreshed in front of the image build)
-        c1m, _, scm, _ = self._block(0)
-        self._w_img = (torch.empty((c1m.cout, self.cimg, 3, 3), dtype=torch.float32, device=dev),
-                       torch.empty((scm.cout, self.cimg, 1, 1), dtype=torch.float32, device=dev))
-        n1 = ops.weight_image_elems(c1m.cout, self.cimg, 3, True)
-        ns = ops.weight_image_elems(scm.cout, self.cimg, 1, True)
-        t = torch.empty(n1 + ns, dtype=dt, device=dev)
-        self.img['0.dimg'] = t
-        self._prep_dimg = ops.PrepBatch([PrepJob(self._w_img[0], t[:n1], True, 1, c1m.idx, 1.0),
-                                         PrepJob(self._w_img[1], t[n1:], True, 1, scm.idx, 0.25)], dt)
+    def _describe(self, sn_of):
+        """As DiscriminatorEngine._describe, for cgan.py:65-153: no controllers; the first block reads image (+) embedding,
+        so the generator update's input gradient covers the IMAGE channels of its conv1 / 1x1 shortcut only (plan.dimg)."""
+        blocks = list(self.dis.blocks.children())
+        res = [b for b in blocks if hasattr(b, 'shortcut')]
+        L = lambda m: sn_of[m].layer                                          # noqa: E731
+        b0 = res[0]
+        facts = [dis_plan.BlockFacts(L(b0.conv[0]), L(b0.conv[2]), L(b0.shortcut[0]), True, None, None)]
+        for b in res[1:]:
+            facts.append(dis_plan.BlockFacts(L(b.conv[1]), L(b.conv[3]), L(b.shortcut[0]) if len(b.shortcut) > 0 else None,
+                                             len(b.conv) == 5, None, None))
+        tail = sn_of[blocks[len(res) + 2]]                     # ReLU, GlobalSumPooling, Linear (cgan.py:150-152)
+        return facts, tail, [], dict(image_cin=self.dis.data_shape[0], one_bucket=True)
 
     # ---- forward ---------------------------------------------------------------------------------
     def forward(self, x_nchw, indicator: Optional[Tensor], train: bool, tail_loss: Optional[str] = None,
@@ -380,7 +306,7 @@ class CDiscriminatorEngine(DiscriminatorEngine):
         (self._prep_all if train else self._prep_fwd).run(sigma)
         if train:
             self._bwd_sigma = sigma
-        I = self.img
+        I, S = self.img, self.sn
         img = x_nchw.t if isinstance(x_nchw, Nhwc) else ops.to_nhwc(x_nchw.detach().contiguous(), dt)
         if img.dtype != dt:
             raise RuntimeError(f'Nhwc input is {img.dtype}, the engine computes in {dt}')
@@ -388,33 +314,34 @@ class CDiscriminatorEngine(DiscriminatorEngine):
         e = self.emb
         xin = ops.cgan_dis_input(img, self.cimg, e.m.weight_orig.detach(), sigma[e.idx:e.idx + 1], lab)
         ctx['img'], ctx['xin'], ctx['nhwc'] = img, xin, isinstance(x_nchw, Nhwc)
-        c1m, c2m, scm, _ = self._block(0)
+        b = self.plan.blocks[0]
+        c1m, c2m, scm = S[b.conv1], S[b.conv2], S[b.shortcut]
         co = c1m.cout
-        c1, _ = ops.conv_fused([Seg(xin)], I['0.c1'], co, bias=c1m.m.bias)
-        y, _ = ops.conv_fused([Seg(c1, relu=True), Seg(xin, ksize=1)], I['0.c2s'], co, bias=c2m.m.bias, bias2=scm.m.bias,
-                              pool=True, alpha=0.25)
+        c1, _ = ops.conv_fused([Seg(xin)], I[b.c1], co, bias=c1m.m.bias)
+        y, _ = ops.conv_fused([Seg(c1, relu=True), Seg(xin, ksize=1)], I[b.c2], co, bias=c2m.m.bias, bias2=scm.m.bias,
+                              pool=True, alpha=b.alpha)
         ctx['blocks'].append({'c1': c1})
         x = y
-        for i in range(1, len(self.res)):
-            c1m, c2m, scm, pooled = self._block(i)
-            c1, _ = ops.conv_fused([Seg(x, relu=True)], I[f'{i}.c1'], c1m.cout, bias=c1m.m.bias)
-            if scm is not None:
-                y, _ = ops.conv_fused([Seg(c1, relu=True), Seg(x, ksize=1)], I[f'{i}.c2s'], c2m.cout, bias=c2m.m.bias,
-                                      bias2=scm.m.bias, pool=pooled, alpha=0.25 if pooled else 1.0)
+        for b in self.plan.blocks[1:]:
+            c1m, c2m = S[b.conv1], S[b.conv2]
+            c1, _ = ops.conv_fused([Seg(x, relu=True)], I[b.c1], c1m.cout, bias=c1m.m.bias)
+            if b.fused:
+                y, _ = ops.conv_fused([Seg(c1, relu=True), Seg(x, ksize=1)], I[b.c2], c2m.cout, bias=c2m.m.bias,
+                                      bias2=S[b.shortcut].m.bias, pool=b.pooled, alpha=b.alpha)
             else:
-                y, _ = ops.conv_fused([Seg(c1, relu=True)], I[f'{i}.c2'], c2m.cout, bias=c2m.m.bias, res=x)
+                y, _ = ops.conv_fused([Seg(c1, relu=True)], I[b.c2], c2m.cout, bias=c2m.m.bias, res=x)
             ctx['blocks'].append({'x': x, 'c1': c1})
             x = y
         # tail: ReLU -> global sum pool -> SN linear (cgan.py:150-152)
-        tl = self.sn_of[self.tail_lin]
-        wl = self.tail_lin.weight_orig.detach().view(-1)
+        tl = self.tail
+        wl = tl.m.weight_orig.detach().view(-1)
         if tail_loss is not None and ops.dtail_hinge_ok(x):
             if tail_loss != 'g':
                 raise McgenError("CGAN discriminator: tail_loss 'g' only (there is no paired pass)")
-            logit, pooled_feat, dlogit, dxt = ops.dtail_hinge_fused(x, None, wl, self.tail_lin.bias, sigma[tl.idx:tl.idx + 1], 'g')
+            logit, pooled_feat, dlogit, dxt = ops.dtail_hinge_fused(x, None, wl, tl.m.bias, sigma[tl.idx:tl.idx + 1], 'g')
             ctx['tail'] = (dlogit, dxt)
         else:
-            logit, pooled_feat = ops.dtail_fwd(x, None, wl, self.tail_lin.bias, sigma[tl.idx:tl.idx + 1])
+            logit, pooled_feat = ops.dtail_fwd(x, None, wl, tl.m.bias, sigma[tl.idx:tl.idx + 1])
         ctx.update(xt=x, pooled=pooled_feat)
         return logit.view(n, 1), ctx
 
@@ -423,9 +350,6 @@ class CDiscriminatorEngine(DiscriminatorEngine):
 
     def pair_codes(self, *a, **k):
         raise McgenError('CGAN discriminator: no MultimodalController codes')
-
-    def bucket_cut(self) -> int:
-        return 0
 
     # ---- backward ----------------------------------------------------------------------------------
     def backward_iter(self, ctx, dlogit: Tensor, gflat: Optional[Tensor], accumulate: bool, need_input_grad: bool,
@@ -443,45 +367,45 @@ class CDiscriminatorEngine(DiscriminatorEngine):
         if self._bwd_sigma is not sigma:
             self._prep_bwd.run(sigma)
             self._bwd_sigma = sigma
-        I = self.img
-        tl = self.sn_of[self.tail_lin]
+        I, S = self.img, self.sn
+        tl = self.tail
         sg_t = sigma[tl.idx:tl.idx + 1]
-        wl = self.tail_lin.weight_orig
-        red = ops.deferred_reduces()
-        red.__enter__()
-        try:
+        wl = tl.m.weight_orig
+        with ops.deferred_reduces():
             tail = ctx.get('tail')
             if tail is not None and dlogit is tail[0] and not want_w:
                 dy = tail[1]
             else:
                 dy = ops.dtail_bwd(dlogit, ctx['xt'], None, wl.detach().view(-1), sg_t, ctx['pooled'],
-                                   T(wl).view(-1) if want_w else None, T(self.tail_lin.bias) if want_w else None)
-            for bi in reversed(range(1, len(self.res))):
-                bc = ctx['blocks'][bi]
+                                   T(wl).view(-1) if want_w else None, T(tl.m.bias) if want_w else None)
+            blocks = self.plan.blocks
+            for bi in reversed(range(1, len(blocks))):
+                b, bc = blocks[bi], ctx['blocks'][bi]
                 x, c1 = bc['x'], bc['c1']
-                c1m, c2m, scm, pooled = self._block(bi)
-                a = 0.25 if pooled else 1.0
+                c1m, c2m = S[b.conv1], S[b.conv2]
+                scm = S[b.shortcut] if b.fused else None
                 if want_w:
                     ops.wgrad(Seg(c1, relu=True), dy, c2m.cout, c2m.cin, T(c2m.m.weight_orig), bias_grad=T(c2m.m.bias),
-                              bias_grad2=T(scm.m.bias) if scm is not None else None, dy_ups=pooled, alpha=a)
+                              bias_grad2=T(scm.m.bias) if scm is not None else None, dy_ups=b.pooled, alpha=b.alpha)
                     if scm is not None:
-                        ops.wgrad(Seg(x, ksize=1), dy, scm.cout, scm.cin, T(scm.m.weight_orig), dy_ups=pooled, alpha=a)
-                dc1, _ = ops.conv_fused([Seg(dy, ups=pooled)], I[f'{bi}.c2t'], c2m.cin, gate_x=c1)
+                        ops.wgrad(Seg(x, ksize=1), dy, scm.cout, scm.cin, T(scm.m.weight_orig), dy_ups=b.pooled, alpha=b.alpha)
+                dc1, _ = ops.conv_fused([Seg(dy, ups=b.pooled)], I[b.c2t], c2m.cin, gate_x=c1)
                 if want_w:
                     ops.wgrad(Seg(x, relu=True), dc1, c1m.cout, c1m.cin, T(c1m.m.weight_orig), bias_grad=T(c1m.m.bias))
                 if scm is not None:
-                    res, _ = ops.conv_fused([Seg(dy, ksize=1, ups=pooled)], I[f'{bi}.sct'], scm.cin)
+                    res, _ = ops.conv_fused([Seg(dy, ksize=1, ups=b.pooled)], I[b.sct], scm.cin)
                 else:
                     res = dy
-                dy, _ = ops.conv_fused([Seg(dc1)], I[f'{bi}.c1t'], c1m.cin, gate_x=x, res=res)
+                dy, _ = ops.conv_fused([Seg(dc1)], I[b.c1t], c1m.cin, gate_x=x, res=res)
             # FirstDisResBlock on the image (+) embedding input
-            c1m, c2m, scm, _ = self._block(0)
+            b = blocks[0]
+            c1m, c2m, scm = S[b.conv1], S[b.conv2], S[b.shortcut]
             c1, xin = ctx['blocks'][0]['c1'], ctx['xin']
             if want_w:
                 ops.wgrad(Seg(c1, relu=True), dy, c2m.cout, c2m.cin, T(c2m.m.weight_orig), bias_grad=T(c2m.m.bias),
-                          bias_grad2=T(scm.m.bias), dy_ups=True, alpha=0.25)
-                ops.wgrad(Seg(xin, ksize=1), dy, scm.cout, scm.cin, T(scm.m.weight_orig), dy_ups=True, alpha=0.25)
-            dc1, _ = ops.conv_fused([Seg(dy, ups=True)], I['0.c2t'], c2m.cin, gate_x=c1)
+                          bias_grad2=T(scm.m.bias), dy_ups=True, alpha=b.alpha)
+                ops.wgrad(Seg(xin, ksize=1), dy, scm.cout, scm.cin, T(scm.m.weight_orig), dy_ups=True, alpha=b.alpha)
+            dc1, _ = ops.conv_fused([Seg(dy, ups=True)], I[b.c2t], c2m.cin, gate_x=c1)
             if want_w:
                 ops.wgrad(Seg(xin), dc1, c1m.cout, c1m.cin, T(c1m.m.weight_orig), bias_grad=T(c1m.m.bias))
                 # the embedding: per-image window sums of dc1 and the plain sum of dy -- no input-gradient launch
@@ -492,17 +416,12 @@ class CDiscriminatorEngine(DiscriminatorEngine):
             dimg = None
             if need_input_grad:
                 # only the image channels of the input gradient (the embedding's input is a parameter, not an image)
-                w1, wsc = self._w_img
-                w1.copy_(c1m.m.weight_orig.detach()[:, :self.cimg])
-                wsc.copy_(scm.m.weight_orig.detach()[:, :self.cimg])
+                for s in (c1m, scm):
+                    self._w_cols[s.idx].copy_(s.m.weight_orig.detach()[:, :self.cimg])
                 self._prep_dimg.run(sigma)
                 img = ctx['img']
-                dimg_t, _ = ops.conv_fused([Seg(dc1), Seg(dy, ksize=1, ups=True)], I['0.dimg'], self.cimg, cy=img.shape[-1])
+                dimg_t, _ = ops.conv_fused([Seg(dc1), Seg(dy, ksize=1, ups=True)], I[b.dimg], self.cimg, cy=img.shape[-1])
                 dimg = Nhwc(dimg_t, self.cimg) if ctx.get('nhwc') else ops.to_nchw(dimg_t, self.cimg)
-        except BaseException as e:
-            red.__exit__(type(e), e, None)
-            raise
-        red.__exit__(None, None, None)
         if want_w:
             # d/d(W / sigma) -> d/d(weight_orig) with this forward's u, v, sigma; biases moved as they are
             ops.sn_grad_fix(gt, gflat, fp, uv, self._layers_dev, len(self.sn) + len(self.plain), sigma, accumulate=accumulate)

@@ -23,7 +23,7 @@ from typing import Dict, List, Optional
 import torch
 import torch.nn as nn
 
-from . import gen_plan, ops
+from . import dis_plan, gen_plan, ops
 from ._lib import McgenError
 from ._tuning import flag as _flag
 from .ops import PrepJob, Seg
@@ -175,8 +175,13 @@ class GeneratorEngine:
         self.gen = gen
         self.dtype = dtype
         self.flat_p = FlatState(list(gen.parameters()))
-        self._img_key = self._plan_key = self._stack_plan = None
+        self._img_key = None
+        self._plan_key = self._plan_val = None               # _plan
+        self._stack_plan = self._stack = None                # _stacked_maps
+        self._live_plan, self._live = None, {}               # live_chunks
+        self._cb_cache: Dict = {}                            # _per_codebook
         self.img: Dict[str, Tensor] = {}
+        self.img_t: Dict[str, Tensor] = {}
         self._prep_fwd = self._prep_bwd = None
         lin, res, head_bn, head_mc, head_conv = self._layers()
         self._codes = ops.CodeBatch([m for b in res for m in (b.mc_1, b.mc_2)] + [head_mc])
@@ -302,7 +307,7 @@ class GeneratorEngine:
         """make(codebook), cached per codebook version."""
         cb = mc.codebook
         key = (cb.data_ptr(), tuple(cb.shape), cb._version)
-        cache = self.__dict__.setdefault('_cb_cache', {})
+        cache = self._cb_cache
         if cache.get((slot, id(mc)), (None,))[0] != key:
             cache[slot, id(mc)] = (key, make(cb))
         return cache[slot, id(mc)][1]
@@ -335,7 +340,7 @@ class GeneratorEngine:
         Rebuilt with the plan, i.e. when a codebook changes (create / transit); a table keeps its address while its shape
         stays, so captured graphs keep reading it."""
         plan = self._plan()
-        if self.__dict__.get('_live_plan') is not plan:
+        if self._live_plan is not plan:
             mcs = self._codes.mcs
             cb0 = mcs[0].codebook
             if cb0.is_cuda and torch.cuda.is_current_stream_capturing():
@@ -345,7 +350,7 @@ class GeneratorEngine:
             by_image: Dict[str, list] = {}
             for j in plan.jobs:
                 by_image.setdefault(j.buffer, []).append(j)
-            old, self._live = self.__dict__.get('_live', {}), {}
+            old, self._live = self._live, {}
             chunks = {}                                  # controller -> int32 [modes]
             for name, jobs in by_image.items():
                 if not any(j.kmap for j in jobs):
@@ -551,69 +556,76 @@ class GeneratorEngine:
         cut = self.bucket_cut()
         off_cut = self.flat_p.offset_of(next(p for p in res[cut].parameters())) if res else 0
         G = lambda p: self.flat_p.view_of(gflat, p)                           # noqa: E731
-        red = ops.deferred_reduces()           # the split-K reductions of one bucket: one launch
-        red.__enter__()
-        try:
+        split = split and cut > 0 and _BUCKETS
+
+        def head_bwd():
             # head conv: bias / weight grads, then the input gradient through MC, ReLU and BN
             seg_h = Seg(y, scale=bnh.scale, shift=bnh.shift, code=codeh, relu=True)
             ops.wgrad(seg_h, dtn, c_img, c, G(head_conv.weight), accumulate=acc, bias_grad=G(head_conv.bias))
             wt = self.img_t['head']
             dz, part = ops.conv_fused([Seg(dtn)], wt, c, ocode=codeh, gate_x=y, gscale=bnh.scale, gshift=bnh.shift,
                                       gmean=bnh.mean, grstd=bnh.rstd, stats_mode=2)
-            dy = ops.bn_backward(part, dz, y, bnh.count, bnh.scale, bnh.mean, bnh.rstd,
-                                 G(head_bn.weight), G(head_bn.bias), accumulate=acc)
-            for i in reversed(range(len(res))):
-                b, bc = res[i], ctx['blocks'][i]
-                x, h, code1, code2, bn1, bn2 = bc['x'], bc['h'], bc['code1'], bc['code2'], bc['bn1'], bc['bn2']
-                conv1, conv2, convs = b.conv[4].module, b.conv[8].module, b.shortcut[2].module
-                bnm1, bnm2 = b.conv[0].module, b.conv[5].module
-                ci, co = conv1.in_channels, conv1.out_channels
-                # second conv and the 1x1 shortcut both see dy
-                seg_b = Seg(h, scale=bn2.scale, shift=bn2.shift, code=code2, relu=True)
-                seg_s = Seg(x, ksize=1, code=code1, ups=True)
-                ops.wgrad(seg_b, dy, co, co, G(conv2.weight), accumulate=acc, bias_grad=G(conv2.bias), bias_grad2=G(convs.bias))
-                # the shortcut conv1x1(Up(x)) commutes with the upsample: in bf16 its weight gradient and input gradient are
-                # taken at x's resolution from the 2x2-pooled dy (a quarter of the FLOPs; fp32 keeps the literal form)
-                lowres = _LOWRES_SC_BWD and dt == torch.bfloat16 and dy.shape[1] >= 16
-                dy_lo = ops.pool2_sum(dy) if lowres else None
-                if lowres:
-                    ops.wgrad(Seg(x, ksize=1, code=code1), dy_lo, co, ci, G(convs.weight), accumulate=acc)
-                else:
-                    ops.wgrad(seg_s, dy, co, ci, G(convs.weight), accumulate=acc)
-                w2t = self.img_t[f'b{i}.w2']
-                dz2, part2 = ops.conv_fused([Seg(dy)], w2t, co, ocode=code2, gate_x=h, gscale=bn2.scale, gshift=bn2.shift,
-                                            gmean=bn2.mean, grstd=bn2.rstd, stats_mode=2)
-                dh = ops.bn_backward(part2, dz2, h, bn2.count, bn2.scale, bn2.mean, bn2.rstd,
-                                     G(bnm2.weight), G(bnm2.bias), accumulate=acc)
-                # first conv: gradient goes through MC, the nearest-upsample adjoint (2x2 sum), ReLU, BN
-                seg_a = Seg(x, scale=bn1.scale, shift=bn1.shift, code=code1, ups=True, relu=True)
-                ops.wgrad(seg_a, dh, co, ci, G(conv1.weight), accumulate=acc, bias_grad=G(conv1.bias))
-                wst = self.img_t[f'b{i}.ws']
-                if lowres:
-                    dx_sc, _ = ops.conv_fused([Seg(dy_lo, ksize=1)], wst, ci, ocode=code1)
-                else:
-                    dx_sc, _ = ops.conv_fused([Seg(dy, ksize=1)], wst, ci, pool=True, alpha=1.0, ocode=code1)
-                w1t = self.img_t[f'b{i}.w1']
-                dz1, part1 = ops.conv_fused([Seg(dh)], w1t, ci, pool=True, alpha=1.0, ocode=code1, gate_x=x,
-                                            gscale=bn1.scale, gshift=bn1.shift, gmean=bn1.mean, grstd=bn1.rstd, stats_mode=2)
-                dy = ops.bn_backward(part1, dz1, x, bn1.count, bn1.scale, bn1.mean, bn1.rstd,
-                                     G(bnm1.weight), G(bnm1.bias), add=dx_sc, accumulate=acc)
-                if i == cut and cut > 0 and _BUCKETS and split:
-                    red.__exit__(None, None, None)           # head + blocks cut .. last are final
-                    if _BUCKETS and split:
-                        yield (off_cut, gflat.numel(), False)
-                    red = ops.deferred_reduces()
-                    red.__enter__()
+            return ops.bn_backward(part, dz, y, bnh.count, bnh.scale, bnh.mean, bnh.rstd,
+                                   G(head_bn.weight), G(head_bn.bias), accumulate=acc)
+
+        def block_bwd(i, dy):
+            b, bc = res[i], ctx['blocks'][i]
+            x, h, code1, code2, bn1, bn2 = bc['x'], bc['h'], bc['code1'], bc['code2'], bc['bn1'], bc['bn2']
+            conv1, conv2, convs = b.conv[4].module, b.conv[8].module, b.shortcut[2].module
+            bnm1, bnm2 = b.conv[0].module, b.conv[5].module
+            ci, co = conv1.in_channels, conv1.out_channels
+            # second conv and the 1x1 shortcut both see dy
+            seg_b = Seg(h, scale=bn2.scale, shift=bn2.shift, code=code2, relu=True)
+            seg_s = Seg(x, ksize=1, code=code1, ups=True)
+            ops.wgrad(seg_b, dy, co, co, G(conv2.weight), accumulate=acc, bias_grad=G(conv2.bias), bias_grad2=G(convs.bias))
+            # the shortcut conv1x1(Up(x)) commutes with the upsample: in bf16 its weight gradient and input gradient are
+            # taken at x's resolution from the 2x2-pooled dy (a quarter of the FLOPs; fp32 keeps the literal form)
+            lowres = _LOWRES_SC_BWD and dt == torch.bfloat16 and dy.shape[1] >= 16
+            dy_lo = ops.pool2_sum(dy) if lowres else None
+            if lowres:
+                ops.wgrad(Seg(x, ksize=1, code=code1), dy_lo, co, ci, G(convs.weight), accumulate=acc)
+            else:
+                ops.wgrad(seg_s, dy, co, ci, G(convs.weight), accumulate=acc)
+            w2t = self.img_t[f'b{i}.w2']
+            dz2, part2 = ops.conv_fused([Seg(dy)], w2t, co, ocode=code2, gate_x=h, gscale=bn2.scale, gshift=bn2.shift,
+                                        gmean=bn2.mean, grstd=bn2.rstd, stats_mode=2)
+            dh = ops.bn_backward(part2, dz2, h, bn2.count, bn2.scale, bn2.mean, bn2.rstd,
+                                 G(bnm2.weight), G(bnm2.bias), accumulate=acc)
+            # first conv: gradient goes through MC, the nearest-upsample adjoint (2x2 sum), ReLU, BN
+            seg_a = Seg(x, scale=bn1.scale, shift=bn1.shift, code=code1, ups=True, relu=True)
+            ops.wgrad(seg_a, dh, co, ci, G(conv1.weight), accumulate=acc, bias_grad=G(conv1.bias))
+            wst = self.img_t[f'b{i}.ws']
+            if lowres:
+                dx_sc, _ = ops.conv_fused([Seg(dy_lo, ksize=1)], wst, ci, ocode=code1)
+            else:
+                dx_sc, _ = ops.conv_fused([Seg(dy, ksize=1)], wst, ci, pool=True, alpha=1.0, ocode=code1)
+            w1t = self.img_t[f'b{i}.w1']
+            dz1, part1 = ops.conv_fused([Seg(dh)], w1t, ci, pool=True, alpha=1.0, ocode=code1, gate_x=x,
+                                        gscale=bn1.scale, gshift=bn1.shift, gmean=bn1.mean, grstd=bn1.rstd, stats_mode=2)
+            return ops.bn_backward(part1, dz1, x, bn1.count, bn1.scale, bn1.mean, bn1.rstd,
+                                   G(bnm1.weight), G(bnm1.bias), add=dx_sc, accumulate=acc)
+
+        def linear_bwd(dy):
             # linear layer: dy is [N,4,4,C0] == [N,1,1,16*C0] in the permuted row order
             c0 = lin.out_features // 16
             dflat = dy.view(n, 1, 1, 16 * c0)
             ops.wgrad(Seg(ctx['zt'], ksize=1), dflat, 16 * c0, lin.in_features, G(lin.weight), row_perm=16, accumulate=acc,
                       bias_grad=G(lin.bias))
-        except BaseException as e:
-            red.__exit__(type(e), e, None)
-            raise
-        red.__exit__(None, None, None)
-        yield (0, off_cut if (cut > 0 and _BUCKETS and split) else gflat.numel(), True)
+
+        # (the split-K reductions of one bucket: one launch, when its `with` block ends)
+        with ops.deferred_reduces():
+            dy = head_bwd()
+            for i in reversed(range(cut if split else 0, len(res))):
+                dy = block_bwd(i, dy)
+            if not split:
+                linear_bwd(dy)
+        if split:
+            yield (off_cut, gflat.numel(), False)            # head + blocks cut .. last are final
+            with ops.deferred_reduces():
+                for i in reversed(range(cut)):
+                    dy = block_bwd(i, dy)
+                linear_bwd(dy)
+        yield (0, off_cut if split else gflat.numel(), True)
 
 
 # ============================================================================================= #
@@ -629,20 +641,26 @@ class _SNConv:
         self.cout, self.cin = w.shape[0], w.shape[1]
         self.ks = w.shape[2] if w.dim() == 4 else 1
 
+    @property
+    def layer(self) -> dis_plan.Layer:
+        return dis_plan.Layer(self.idx, self.cout, self.cin, self.ks)
+
+
+class _Ones:
+    """Stands in for a MultimodalController on the raw image (8 padded channels) in the paired pass's code jobs."""
+
+    def __init__(self, modes: int, device):
+        self.codebook = torch.ones(modes, 8, device=device)
+
 
 class DiscriminatorEngine:
     def __init__(self, dis, dtype: torch.dtype = torch.float32):
         self.dis = dis
         self.dtype = dtype
-        blocks = list(dis.blocks.children())
-        self.res = [b for b in blocks if hasattr(b, 'mc_1')]
-        t = len(self.res)
-        self.tail_mc, self.tail_lin = blocks[t + 1], blocks[t + 3].module
         self.sn: List[_SNConv] = []
         for m in dis.modules():
             if hasattr(m, 'weight_orig'):
                 self.sn.append(_SNConv(m, len(self.sn)))
-        self.sn_of = {s.m: s for s in self.sn}
         params = list(dis.parameters())
         sn_w = {id(s.m.weight_orig) for s in self.sn}
         self.plain = [p for p in params if id(p) not in sn_w]
@@ -653,78 +671,70 @@ class DiscriminatorEngine:
         self.flat_uv = FlatState(uv)
         self._layers_dev = None          # SN layers first, then plain parameters (rows == 0)
         self._layers_key = None
-        mcs = [self.res[0].mc_1] + [m for b in self.res[1:] for m in (b.mc_1, b.mc_2)] + [self.tail_mc]
-        self._codes = ops.CodeBatch(mcs)
-        self._prep_fwd = self._prep_bwd = None
+        # the network as plain data (dis_plan): every walk below reads block records and plan names
+        facts, self.tail, mcs, options = self._describe({s.m: s for s in self.sn})
+        self.plan = dis_plan.plan_discriminator(facts, (self.tail.idx, len(mcs) - 1 if mcs else None), **options)
+        self._codes = ops.CodeBatch(mcs) if mcs else None
+        self._codes_pair = self._ones_mc = None          # forward_pair: one code job per convolution input
+        self._sn_ratio = None                            # _power_iters: sigma_1 / sigma_2 of a two-round launch
         self.img: Dict[str, Tensor] = {}
+        self._prep_fwd = self._prep_bwd = self._prep_all = self._prep_dimg = None     # _build_preps
+        self._w_cols: Dict[int, Tensor] = {}             # plan.dimg: fp32 copies of its layers' image columns
+        self._bwd_sigma = None                           # the sigma the transposed images were built with
+        self._bk = self._bk_key = None                   # _bucket_tables
+        self.pending_fix = None                          # backward_iter(defer_fix=True) -> GANTrainer.d_apply
+
+    def _describe(self, sn_of):
+        """-> (dis_plan.BlockFacts of every residual block, the tail Linear's _SNConv, the MultimodalControllers in code
+        order, plan_discriminator options): the one place that knows where mcgan.py:72-181 keeps its layers."""
+        blocks = list(self.dis.blocks.children())
+        res = [b for b in blocks if hasattr(b, 'mc_1')]
+        L = lambda m: sn_of[m.module].layer                                   # noqa: E731
+        b0 = res[0]
+        facts = [dis_plan.BlockFacts(L(b0.conv[0]), L(b0.conv[3]), L(b0.shortcut[0]), True, None, 0)]
+        for i, b in enumerate(res[1:], start=1):
+            facts.append(dis_plan.BlockFacts(L(b.conv[2]), L(b.conv[5]), L(b.shortcut[1]) if len(b.shortcut) > 0 else None,
+                                             len(b.conv) == 7, 2 * i - 1, 2 * i))
+        mcs = [b0.mc_1] + [m for b in res[1:] for m in (b.mc_1, b.mc_2)] + [blocks[len(res) + 1]]
+        return facts, sn_of[blocks[len(res) + 3].module], mcs, dict(d0_fuse=_D0_FUSE)
+
+    def _layer_rows(self, sns, plains):
+        """mcgen_sn_layer_t rows (weight offset, u offset, v offset, rows, cols) of spectrally normalised layers, then of
+        plain parameters (rows == 0)."""
+        P, UV = self.flat_p.offset_of, self.flat_uv.offset_of
+        rows = [(P(s.m.weight_orig), UV(s.m.weight_u), UV(s.m.weight_v), s.m.weight_orig.shape[0], s.m.weight_orig[0].numel())
+                for s in sns]
+        return rows + [(P(p), 0, 0, 0, p.numel()) for p in plains]
 
     def _ensure_flat(self):
         fp, fuv = self.flat_p.ensure(), self.flat_uv.ensure()
         key = (fp.data_ptr(), fuv.data_ptr())
         if key != self._layers_key:
-            rows = []
-            for s in self.sn:
-                w = s.m.weight_orig
-                rows.append((self.flat_p.offset_of(w), self.flat_uv.offset_of(s.m.weight_u),
-                             self.flat_uv.offset_of(s.m.weight_v), w.shape[0], w[0].numel()))
-            for p in self.plain:
-                rows.append((self.flat_p.offset_of(p), 0, 0, 0, p.numel()))
-            self._layers_dev = ops.sn_layers_tensor(rows, fp.device)
+            self._layers_dev = ops.sn_layers_tensor(self._layer_rows(self.sn, self.plain), fp.device)
             self._layers_key = key
         return fp, fuv
 
     def _build_preps(self):
-        """Job lists of the forward and backward weight images (persistent buffers, sigma by index)."""
-        dt = self.dtype
-        dev = self.flat_p.flat.device
-        self.img = {}
+        """The plan's weight-image jobs as launches (persistent buffers, sigma by index)."""
+        dt, dev, plan = self.dtype, self.flat_p.flat.device, self.plan
+        self.img = {name: torch.empty(n, dtype=dt, device=dev) for name, n in plan.buffers}
 
-        def img(name, s: _SNConv, transpose, parts=None):
-            n = ops.weight_image_elems(s.cout, s.cin, s.ks, transpose)
-            t = torch.empty(n, dtype=dt, device=dev)
-            self.img[name] = t
-            return t
+        def batch(jobs, weights=None):
+            return ops.PrepBatch([PrepJob(weights[j.layer] if weights else self.sn[j.layer].m.weight_orig,
+                                          self.img[j.buffer][j.offset:j.offset + j.elems], j.transpose, 1, j.sigma, j.wscale)
+                                  for j in jobs], dt)
 
-        def cat(name, a: _SNConv, b: _SNConv, transpose):
-            na = ops.weight_image_elems(a.cout, a.cin, a.ks, transpose)
-            nb = ops.weight_image_elems(b.cout, b.cin, b.ks, transpose)
-            t = torch.empty(na + nb, dtype=dt, device=dev)
-            self.img[name] = t
-            return t[:na], t[na:]
-
-        fwd, bwd = [], []
-        W = lambda s: s.m.weight_orig                                         # noqa: E731
-        b0 = self.res[0]
-        c1m, c2m, scm = (self.sn_of[b0.conv[0].module], self.sn_of[b0.conv[3].module], self.sn_of[b0.shortcut[0].module])
-        fwd.append(PrepJob(W(c1m), img('0.c1', c1m, False), False, 1, c1m.idx, 1.0))
-        if _D0_FUSE:
-            ta, tb = cat('0.c2s', c2m, scm, False)                           # conv2 + the 1x1 shortcut: one launch, two K segments
-            fwd += [PrepJob(W(c2m), ta, False, 1, c2m.idx, 1.0), PrepJob(W(scm), tb, False, 1, scm.idx, 1.0)]
-        else:
-            fwd += [PrepJob(W(scm), img('0.sc', scm, False), False, 1, scm.idx, 1.0),
-                    PrepJob(W(c2m), img('0.c2', c2m, False), False, 1, c2m.idx, 1.0)]
-        bwd.append(PrepJob(W(c2m), img('0.c2t', c2m, True), True, 1, c2m.idx, 0.25))
-        ta, tb = cat('0.dimg', c1m, scm, True)
-        bwd += [PrepJob(W(c1m), ta, True, 1, c1m.idx, 1.0), PrepJob(W(scm), tb, True, 1, scm.idx, 0.25)]
-        for i, b in enumerate(self.res[1:], start=1):
-            c1m, c2m = self.sn_of[b.conv[2].module], self.sn_of[b.conv[5].module]
-            has_sc, pooled = len(b.shortcut) > 0, len(b.conv) == 7
-            a = 0.25 if pooled else 1.0
-            fwd.append(PrepJob(W(c1m), img(f'{i}.c1', c1m, False), False, 1, c1m.idx, 1.0))
-            if has_sc:
-                scm = self.sn_of[b.shortcut[1].module]
-                ta, tb = cat(f'{i}.c2s', c2m, scm, False)
-                fwd += [PrepJob(W(c2m), ta, False, 1, c2m.idx, 1.0), PrepJob(W(scm), tb, False, 1, scm.idx, 1.0)]
-                bwd.append(PrepJob(W(scm), img(f'{i}.sct', scm, True), True, 1, scm.idx, a))
-            else:
-                fwd.append(PrepJob(W(c2m), img(f'{i}.c2', c2m, False), False, 1, c2m.idx, 1.0))
-            bwd += [PrepJob(W(c2m), img(f'{i}.c2t', c2m, True), True, 1, c2m.idx, a),
-                    PrepJob(W(c1m), img(f'{i}.c1t', c1m, True), True, 1, c1m.idx, 1.0)]
-        self._prep_fwd, self._prep_bwd = ops.PrepBatch(fwd, dt), ops.PrepBatch(bwd, dt)
+        self._prep_fwd, self._prep_bwd = batch(plan.fwd), batch(plan.bwd)
         # training passes build both sets in ONE launch at the start of the forward (same sigma): the backward pass that
         # follows finds its transposed images ready (`_bwd_sigma` remembers whose they are)
-        self._prep_all = ops.PrepBatch(fwd + bwd, dt)
+        self._prep_all = batch(plan.fwd + plan.bwd)
         self._bwd_sigma = None
+        if plan.dimg:
+            # the input-gradient image of a first block that reads more than the image: built from persistent fp32 copies
+            # of its layers' image columns, which the backward pass refreshes in front of the build
+            self._w_cols = {j.layer: torch.empty((s.cout, plan.image_cin, s.ks, s.ks), dtype=torch.float32, device=dev)
+                            for j in plan.dimg for s in (self.sn[j.layer],)}
+            self._prep_dimg = batch(plan.dimg, self._w_cols)
 
     def _ensure_preps(self):
         if self._prep_fwd is None or self._prep_fwd.dtype != self.dtype or not self._prep_fwd.valid():
@@ -799,19 +809,15 @@ class DiscriminatorEngine:
         (ctx['tail']); `backward_iter` writes the loss value into ctx['loss'] (train_gan.py:154)."""
         n = x2.shape[0] // 2 if x2 is not None else real_nchw.shape[0]
         (sigma1, uv1), (sigma2, uv2) = self._power_iters(2, True)
-        ratio = self._sn_ratio if getattr(self, '_sn_ratio', None) is not None else sigma1 / sigma2
+        ratio = self._sn_ratio if self._sn_ratio is not None else sigma1 / sigma2
         if ind2 is None:
             ind2 = torch.cat([indicator, indicator])
-        uses = self._code_uses()
-        if getattr(self, '_codes_pair', None) is None:
+        uses = self.plan.uses
+        if self._codes_pair is None:
             # one job per convolution input: the MC's codebook (an all-ones table for the image inputs, which have no
             # MC) and the SN layer whose sigma ratio scales the fake half
-            class _Ones:                                        # stands in for an MC on the raw image (8 padded channels)
-                pass
-            ones = _Ones()
-            ones.codebook = torch.ones(indicator.shape[1], 8, device=indicator.device)
-            self._ones_mc = ones
-            self._codes_pair = ops.CodeBatch([self._codes.mcs[u[0]] if u[0] is not None else ones for u in uses],
+            self._ones_mc = _Ones(indicator.shape[1], indicator.device)
+            self._codes_pair = ops.CodeBatch([self._codes.mcs[u[0]] if u[0] is not None else self._ones_mc for u in uses],
                                              [u[1] for u in uses])
         scaled = {}
         if codes is None:
@@ -827,22 +833,6 @@ class DiscriminatorEngine:
             scaled.update(zip(uses, self._codes_pair.run_any(ind2, ratio, n)))     # all scaled codes of the pass: one launch
         return self._forward_body(x, ctx, lambda mc_i, sn_idx: scaled[(mc_i, sn_idx)], tail_loss)
 
-    def _code_uses(self):
-        """(MC index or None for the image, SN layer index) of every convolution input of the network."""
-        if getattr(self, '_uses', None) is None:
-            b0 = self.res[0]
-            c1m, c2m, scm = (self.sn_of[b0.conv[0].module], self.sn_of[b0.conv[3].module], self.sn_of[b0.shortcut[0].module])
-            uses = [(None, c1m.idx), (None, scm.idx), (0, c2m.idx)]
-            for i, b in enumerate(self.res[1:], start=1):
-                c1m, c2m = self.sn_of[b.conv[2].module], self.sn_of[b.conv[5].module]
-                uses += [(2 * i - 1, c1m.idx), (2 * i, c2m.idx)]
-                if len(b.shortcut) > 0:
-                    uses.append((2 * i - 1, self.sn_of[b.shortcut[1].module].idx))
-            uses.append((len(self._codes.mcs) - 1, self.sn_of[self.tail_lin].idx))
-            self._uses = uses
-            self._use_idx = {}
-        return self._uses
-
     def _forward_body(self, x_nchw: Tensor, ctx, code_of, tail_loss: Optional[str] = None):
         dt = self.dtype
         n = x_nchw.shape[0]
@@ -857,59 +847,58 @@ class DiscriminatorEngine:
             prep.run(sigma)                       # every W / sigma image of this pass, forward and transposed, in one launch
         if ctx.get('train', True):
             self._bwd_sigma = sigma
-        I = self.img
+        I, S = self.img, self.sn
         img = x_nchw.t if isinstance(x_nchw, Nhwc) else ops.to_nhwc(x_nchw.detach().contiguous(), dt)
         if img.dtype != dt:
             raise RuntimeError(f'Nhwc input is {img.dtype}, the engine computes in {dt}')
         ctx['img'], ctx['nhwc'] = img, isinstance(x_nchw, Nhwc)
         # --- FirstDisResBlock (mcgan.py:72-93)
-        b0 = self.res[0]
-        c1m, c2m, scm = (self.sn_of[b0.conv[0].module], self.sn_of[b0.conv[3].module], self.sn_of[b0.shortcut[0].module])
+        b = self.plan.blocks[0]
+        c1m, c2m, scm = S[b.conv1], S[b.conv2], S[b.shortcut]
         co = c1m.cout
-        c1, _ = ops.conv_fused([Seg(img, code=code_of(None, c1m.idx))], I['0.c1'], co, bias=c1m.m.bias)
+        c1, _ = ops.conv_fused([Seg(img, code=code_of(b.ctrl_x, c1m.idx))], I[b.c1], co, bias=c1m.m.bias)
         # conv2 and the shortcut's 1x1 (mcgan.py:83-86: conv then AvgPool, like conv2) share the pooled epilogue: the shortcut is
         # a second K segment of the same launch, as in the later blocks (its own launch + the residual read: 21 us of 80)
-        code = code_of(0, c2m.idx)
-        if _D0_FUSE:
-            y, _ = ops.conv_fused([Seg(c1, code=code, relu=True), Seg(img, ksize=1, code=code_of(None, scm.idx))], I['0.c2s'], co,
-                                  bias=c2m.m.bias, bias2=scm.m.bias, pool=True, alpha=0.25)
+        code = code_of(b.ctrl_h, c2m.idx)
+        seg_s = Seg(img, ksize=1, code=code_of(b.ctrl_x, scm.idx))
+        if b.fused:
+            y, _ = ops.conv_fused([Seg(c1, code=code, relu=True), seg_s], I[b.c2], co,
+                                  bias=c2m.m.bias, bias2=scm.m.bias, pool=True, alpha=b.alpha)
         else:
-            sc, _ = ops.conv_fused([Seg(img, ksize=1, code=code_of(None, scm.idx))], I['0.sc'], co, bias=scm.m.bias, pool=True, alpha=0.25)
-            y, _ = ops.conv_fused([Seg(c1, code=code, relu=True)], I['0.c2'], co, bias=c2m.m.bias, pool=True, alpha=0.25, res=sc)
+            sc, _ = ops.conv_fused([seg_s], I[b.sc], co, bias=scm.m.bias, pool=True, alpha=b.alpha)
+            y, _ = ops.conv_fused([Seg(c1, code=code, relu=True)], I[b.c2], co, bias=c2m.m.bias, pool=True, alpha=b.alpha, res=sc)
         ctx['blocks'].append({'c1': c1, 'code': code})
         x = y
         # --- DisResBlocks (mcgan.py:96-138)
-        for i, b in enumerate(self.res[1:], start=1):
-            c1m, c2m = self.sn_of[b.conv[2].module], self.sn_of[b.conv[5].module]
-            has_sc = len(b.shortcut) > 0
-            pooled = len(b.conv) == 7
-            code1, code2 = code_of(2 * i - 1, c1m.idx), code_of(2 * i, c2m.idx)
+        for b in self.plan.blocks[1:]:
+            c1m, c2m = S[b.conv1], S[b.conv2]
+            code1, code2 = code_of(b.ctrl_x, c1m.idx), code_of(b.ctrl_h, c2m.idx)
             code1s = None
-            c1, _ = ops.conv_fused([Seg(x, code=code1, relu=True)], I[f'{i}.c1'], c1m.cout, bias=c1m.m.bias)
-            if has_sc:
-                scm = self.sn_of[b.shortcut[1].module]
-                code1s = code_of(2 * i - 1, scm.idx)
-                y, _ = ops.conv_fused([Seg(c1, code=code2, relu=True), Seg(x, ksize=1, code=code1s)], I[f'{i}.c2s'], c2m.cout,
-                                      bias=c2m.m.bias, bias2=scm.m.bias, pool=pooled, alpha=0.25 if pooled else 1.0)
+            c1, _ = ops.conv_fused([Seg(x, code=code1, relu=True)], I[b.c1], c1m.cout, bias=c1m.m.bias)
+            if b.fused:
+                scm = S[b.shortcut]
+                code1s = code_of(b.ctrl_x, scm.idx)
+                y, _ = ops.conv_fused([Seg(c1, code=code2, relu=True), Seg(x, ksize=1, code=code1s)], I[b.c2], c2m.cout,
+                                      bias=c2m.m.bias, bias2=scm.m.bias, pool=b.pooled, alpha=b.alpha)
             else:
-                y, _ = ops.conv_fused([Seg(c1, code=code2, relu=True)], I[f'{i}.c2'], c2m.cout,
+                y, _ = ops.conv_fused([Seg(c1, code=code2, relu=True)], I[b.c2], c2m.cout,
                                       bias=c2m.m.bias, res=x)
-            ctx['blocks'].append({'x': x, 'c1': c1, 'code1': code1, 'code1s': code1s, 'code2': code2, 'pooled': pooled, 'has_sc': has_sc})
+            ctx['blocks'].append({'x': x, 'c1': c1, 'code1': code1, 'code1s': code1s, 'code2': code2})
             x = y
         # --- tail: ReLU -> MC -> global sum pool -> SN linear (mcgan.py:158-165)
-        tl = self.sn_of[self.tail_lin]
-        codet = code_of(len(self._codes.mcs) - 1, tl.idx)
+        tl = self.tail
+        codet = code_of(self.plan.tail[1], tl.idx)
         if tail_loss is not None and ops.dtail_hinge_ok(x):
             if (tail_loss == 'd_pair') != (ctx['pair'] is not None):
                 raise McgenError("tail_loss: 'd_pair' goes with forward_pair, 'g' with forward")
-            logit, pooled_feat, dlogit, dxt = ops.dtail_hinge_fused(x, codet, self.tail_lin.weight_orig.detach().view(-1), self.tail_lin.bias,
+            logit, pooled_feat, dlogit, dxt = ops.dtail_hinge_fused(x, codet, tl.m.weight_orig.detach().view(-1), tl.m.bias,
                                                                     sigma[tl.idx:tl.idx + 1], tail_loss)
             ctx['tail'] = (dlogit, dxt)
             if tail_loss == 'd_pair':
                 ctx['loss'] = torch.empty(1, dtype=torch.float32, device=x.device)
                 ctx['logit'] = logit
         else:
-            logit, pooled_feat = ops.dtail_fwd(x, codet, self.tail_lin.weight_orig.detach().view(-1), self.tail_lin.bias,
+            logit, pooled_feat = ops.dtail_fwd(x, codet, tl.m.weight_orig.detach().view(-1), tl.m.bias,
                                                sigma[tl.idx:tl.idx + 1])
         ctx.update(xt=x, codet=codet, pooled=pooled_feat)
         return logit.view(n, 1), ctx
@@ -929,31 +918,30 @@ class DiscriminatorEngine:
         first, so gflat[offset(block cut) :] is final while blocks cut-1 .. 0 are still running -- a data-parallel run
         starts that bucket's all-reduce there (GANTrainer), under the rest of the backward.
         (0: a discriminator with a single residual block has nothing to split -- one bucket, as the generator's rule.)"""
-        return max(1, len(self.res) // 2) if len(self.res) > 1 else 0
+        return self.plan.bucket_cut
 
     def _bucket_tables(self):
         """Spectral-norm fix-up tables of the two buckets: SN layers with index >= the cut block's first layer + the plain
         parameters stored behind the cut offset, and the rest."""
         fp, _ = self._ensure_flat()
-        key = (self._layers_key, self.bucket_cut())
-        if getattr(self, '_bk_key', None) != key:
-            cut_block = self.res[self.bucket_cut()]
-            first = next(p for p in cut_block.parameters())
-            off_cut = self.flat_p.offset_of(first)
-            sn_hi = [sn for sn in self.sn if self.flat_p.offset_of(sn.m.weight_orig) >= off_cut]
+        key = (self._layers_key, self.plan.bucket_cut)
+        if self._bk_key != key:
+            off = self.flat_p.offset_of
+            b = self.plan.blocks[self.plan.bucket_cut]
+            # (a block's parameters lie back to back in module order: the first of them is where the late bucket starts)
+            off_cut = min(off(p) for i in (b.conv1, b.conv2, b.shortcut) if i is not None
+                          for p in (self.sn[i].m.weight_orig, self.sn[i].m.bias))
+            sn_hi = [sn for sn in self.sn if off(sn.m.weight_orig) >= off_cut]
             i_cut = min(sn.idx for sn in sn_hi)
             assert [sn.idx for sn in sn_hi] == list(range(i_cut, len(self.sn))), 'SN layers of the late bucket are not contiguous'
 
             def table(sns, plains):
-                rows = [(self.flat_p.offset_of(sn.m.weight_orig), self.flat_uv.offset_of(sn.m.weight_u),
-                         self.flat_uv.offset_of(sn.m.weight_v), sn.m.weight_orig.shape[0], sn.m.weight_orig[0].numel()) for sn in sns]
-                rows += [(self.flat_p.offset_of(p), 0, 0, 0, p.numel()) for p in plains]
+                rows = self._layer_rows(sns, plains)
                 return (ops.sn_layers_tensor(rows, fp.device) if rows else None), len(rows)
-            hi = table(sn_hi, [p for p in self.plain if self.flat_p.offset_of(p) >= off_cut])
-            lo = table([sn for sn in self.sn if sn.idx < i_cut], [p for p in self.plain if self.flat_p.offset_of(p) < off_cut])
+            hi = table(sn_hi, [p for p in self.plain if off(p) >= off_cut])
+            lo = table(self.sn[:i_cut], [p for p in self.plain if off(p) < off_cut])
             # (a single-rank update has nothing to overlap with: one table for the fused fix + Adam launch)
-            every = table(sorted(self.sn, key=lambda sn: sn.idx), list(self.plain))
-            self._bk = {'off_cut': off_cut, 'i_cut': i_cut, 'hi': hi, 'lo': lo, 'all': every}
+            self._bk = {'off_cut': off_cut, 'i_cut': i_cut, 'hi': hi, 'lo': lo, 'all': table(self.sn, self.plain)}
             self._bk_key = key
         return self._bk
 
@@ -982,20 +970,21 @@ class DiscriminatorEngine:
         else:
             passes = [(slice(0, pair['n']), torch.empty_like(fp)), (slice(pair['n'], 2 * pair['n']), torch.empty_like(fp))]
 
-        def wgrad_all(seg_fn, dy, cout, cin, param, bias=None, bias2=None, **kw):
+        def wgrad_all(seg_fn, dy, s: _SNConv, bias=None, bias2=None, **kw):
+            """The weight (and bias) gradients of layer `s` whose input rows sl are seg_fn(sl), per pass."""
             def dests(gtmp):
                 T = lambda p: self.flat_p.view_of(gtmp, p)                         # noqa: E731
-                return T(param), (T(bias) if bias is not None else None), (T(bias2) if bias2 is not None else None)
+                return T(s.m.weight_orig), (T(bias) if bias is not None else None), (T(bias2) if bias2 is not None else None)
             hq = dy.shape[1] * dy.shape[2] * (4 if kw.get('dy_ups') else 1)          # pixels per image at the conv resolution
             if pair is not None and _PAIR_WGRAD and (pair['n'] * hq) % 128 == 0:
                 # one launch over the 2N batch, one slab set per half; the codes of the two halves are equal
                 seg = seg_fn(slice(None))
                 (g1, b1, b12), second = dests(passes[0][1]), dests(passes[1][1])
-                ops.wgrad(seg, dy, cout, cin, g1, bias_grad=b1, bias_grad2=b12, second=second, **kw)
+                ops.wgrad(seg, dy, s.cout, s.cin, g1, bias_grad=b1, bias_grad2=b12, second=second, **kw)
                 return
             for sl, gtmp in passes:
                 g1, b1, b12 = dests(gtmp)
-                ops.wgrad(seg_fn(sl), dy[sl], cout, cin, g1, bias_grad=b1, bias_grad2=b12, **kw)
+                ops.wgrad(seg_fn(sl), dy[sl], s.cout, s.cin, g1, bias_grad=b1, bias_grad2=b12, **kw)
 
         def fix(tab, sg_off):
             """d/d(W/sigma) -> d/d(weight_orig) with the u, v, sigma THIS forward used (biases are moved as is), for the
@@ -1010,100 +999,103 @@ class DiscriminatorEngine:
                 ops.sn_grad_fix(passes[0][1], gflat, fp, uv, table, nl, sigma[sg_off:], accumulate=accumulate)
 
         bk = self._bucket_tables() if want_w else None
-        cut = self.bucket_cut()
-        split = split and cut > 0                      # (a single residual block: one bucket)
+        blocks, cut = self.plan.blocks, self.plan.bucket_cut
+        split = split and want_w and cut > 0 and _BUCKETS        # (a single residual block: one bucket)
         self._ensure_preps()
         if self._bwd_sigma is not sigma:          # (another forward rebuilt the images since this pass's own)
             self._prep_bwd.run(sigma)             # transposed W / sigma images of THIS pass's sigma
             self._bwd_sigma = sigma
-        I = self.img
-        tl = self.sn_of[self.tail_lin]
-        sg_t = sigma[tl.idx:tl.idx + 1]
-        wl = self.tail_lin.weight_orig
-        red = ops.deferred_reduces()           # the split-K reductions of one bucket: one launch, before its SN fix-up
-        red.__enter__()
-        try:
+        I, S = self.img, self.sn
+        tl = self.tail
+
+        def tail_bwd():
+            sg_t = sigma[tl.idx:tl.idx + 1]
+            wl, bl = tl.m.weight_orig, tl.m.bias
             # a forward that ran the fused tail already holds the tail's input gradient for ITS dlogit (ctx['tail'])
             tail = ctx.get('tail')
             pre_dy = tail[1] if (tail is not None and dlogit is tail[0]) else None
             if pair is None:
                 gt = passes[0][1]
                 if pre_dy is not None and not want_w:
-                    dy = pre_dy
-                else:
-                    dy = ops.dtail_bwd(dlogit, ctx['xt'], ctx['codet'], wl.detach().view(-1), sg_t, ctx['pooled'],
-                                       self.flat_p.view_of(gt, wl).view(-1) if want_w else None,
-                                       self.flat_p.view_of(gt, self.tail_lin.bias) if want_w else None)
+                    return pre_dy
+                return ops.dtail_bwd(dlogit, ctx['xt'], ctx['codet'], wl.detach().view(-1), sg_t, ctx['pooled'],
+                                     self.flat_p.view_of(gt, wl).view(-1) if want_w else None,
+                                     self.flat_p.view_of(gt, bl) if want_w else None)
+            dy = pre_dy if pre_dy is not None else \
+                ops.dtail_bwd(dlogit, ctx['xt'], ctx['codet'], wl.detach().view(-1), sg_t, ctx['pooled'], None, None)
+            # tail weight / bias gradients per half; the fake half's pooled features carry sigma_1 / sigma_2
+            (_, g_a), (_, g_b) = passes
+            with_loss = pre_dy is not None and 'loss' in ctx
+            ops.dtail_pair_wgrad(dlogit, ctx['pooled'], pair['ratio'][tl.idx:tl.idx + 1],
+                                 self.flat_p.view_of(g_a, wl).view(-1), self.flat_p.view_of(g_a, bl).view(-1),
+                                 self.flat_p.view_of(g_b, wl).view(-1), self.flat_p.view_of(g_b, bl).view(-1),
+                                 logit=ctx['logit'] if with_loss else None, loss=ctx['loss'] if with_loss else None)
+            return dy
+
+        def block_bwd(b, bc, dy):
+            """A DisResBlock: the weight gradients of its layers, -> the gradient of its input."""
+            x, c1, code1, code2, code1s = bc['x'], bc['c1'], bc['code1'], bc['code2'], bc['code1s']
+            c1m, c2m = S[b.conv1], S[b.conv2]
+            scm = S[b.shortcut] if b.fused else None
+            if want_w:
+                wgrad_all(lambda sl: Seg(c1[sl], code=U(b.ctrl_h, sl), relu=True), dy, c2m, c2m.m.bias,
+                          scm.m.bias if scm else None, dy_ups=b.pooled, alpha=b.alpha)
+                if scm:
+                    wgrad_all(lambda sl: Seg(x[sl], ksize=1, code=U(b.ctrl_x, sl)), dy, scm, dy_ups=b.pooled, alpha=b.alpha)
+            dc1, _ = ops.conv_fused([Seg(dy, ups=b.pooled)], I[b.c2t], c2m.cin, ocode=code2, gate_x=c1)
+            if want_w:
+                wgrad_all(lambda sl: Seg(x[sl], code=U(b.ctrl_x, sl), relu=True), dc1, c1m, c1m.m.bias)
+            if scm:
+                res, _ = ops.conv_fused([Seg(dy, ksize=1, ups=b.pooled)], I[b.sct], scm.cin, ocode=code1s)
             else:
-                dy = pre_dy if pre_dy is not None else \
-                    ops.dtail_bwd(dlogit, ctx['xt'], ctx['codet'], wl.detach().view(-1), sg_t, ctx['pooled'], None, None)
-                # tail weight / bias gradients per half; the fake half's pooled features carry sigma_1 / sigma_2
-                (_, g_a), (_, g_b) = passes
-                with_loss = pre_dy is not None and 'loss' in ctx
-                ops.dtail_pair_wgrad(dlogit, ctx['pooled'], pair['ratio'][tl.idx:tl.idx + 1],
-                                     self.flat_p.view_of(g_a, wl).view(-1), self.flat_p.view_of(g_a, self.tail_lin.bias).view(-1),
-                                     self.flat_p.view_of(g_b, wl).view(-1), self.flat_p.view_of(g_b, self.tail_lin.bias).view(-1),
-                                     logit=ctx['logit'] if with_loss else None, loss=ctx['loss'] if with_loss else None)
-            for bi in reversed(range(1, len(self.res))):
-                b, bc = self.res[bi], ctx['blocks'][bi]
-                x, c1, code1, code2, pooled, has_sc = bc['x'], bc['c1'], bc['code1'], bc['code2'], bc['pooled'], bc['has_sc']
-                code1s = bc['code1s']
-                i1, i2 = 2 * bi - 1, 2 * bi                        # MC indices of the block's unscaled codes
-                c1m, c2m = self.sn_of[b.conv[2].module], self.sn_of[b.conv[5].module]
-                scm = self.sn_of[b.shortcut[1].module] if has_sc else None
-                a = 0.25 if pooled else 1.0
-                if want_w:
-                    wgrad_all(lambda sl: Seg(c1[sl], code=U(i2, sl), relu=True), dy, c2m.cout, c2m.cin, c2m.m.weight_orig,
-                              c2m.m.bias, scm.m.bias if has_sc else None, dy_ups=pooled, alpha=a)
-                    if has_sc:
-                        wgrad_all(lambda sl: Seg(x[sl], ksize=1, code=U(i1, sl)), dy, scm.cout, scm.cin, scm.m.weight_orig,
-                                  dy_ups=pooled, alpha=a)
-                dc1, _ = ops.conv_fused([Seg(dy, ups=pooled)], I[f'{bi}.c2t'], c2m.cin, ocode=code2, gate_x=c1)
-                if want_w:
-                    wgrad_all(lambda sl: Seg(x[sl], code=U(i1, sl), relu=True), dc1, c1m.cout, c1m.cin, c1m.m.weight_orig, c1m.m.bias)
-                if has_sc:
-                    res, _ = ops.conv_fused([Seg(dy, ksize=1, ups=pooled)], I[f'{bi}.sct'], scm.cin, ocode=code1s)
-                else:
-                    res = dy
-                dy, _ = ops.conv_fused([Seg(dc1)], I[f'{bi}.c1t'], c1m.cin, ocode=code1, gate_x=x, res=res)
-                if want_w and bi == cut and _BUCKETS and split:
-                    # blocks cut .. last and the tail are done: reduce their slabs, fix them up, hand the bucket out
-                    red.__exit__(None, None, None)
-                    fix(bk['hi'], bk['i_cut'])
-                    if _BUCKETS and split:
-                        yield (bk['off_cut'], fp.numel(), False)
-                    red = ops.deferred_reduces()
-                    red.__enter__()
-            # FirstDisResBlock
-            b0, bc = self.res[0], ctx['blocks'][0]
-            c1m, c2m, scm = (self.sn_of[b0.conv[0].module], self.sn_of[b0.conv[3].module], self.sn_of[b0.shortcut[0].module])
+                res = dy
+            dy, _ = ops.conv_fused([Seg(dc1)], I[b.c1t], c1m.cin, ocode=code1, gate_x=x, res=res)
+            return dy
+
+        def first_bwd(dy):
+            """The FirstDisResBlock: its weight gradients, -> d(input image) or None."""
+            b, bc = blocks[0], ctx['blocks'][0]
+            c1m, c2m, scm = S[b.conv1], S[b.conv2], S[b.shortcut]
             c1, code, img = bc['c1'], bc['code'], ctx['img']
             if want_w:
-                wgrad_all(lambda sl: Seg(c1[sl], code=U(0, sl), relu=True), dy, c2m.cout, c2m.cin, c2m.m.weight_orig,
-                          c2m.m.bias, scm.m.bias, dy_ups=True, alpha=0.25)
-                wgrad_all(lambda sl: Seg(img[sl], ksize=1), dy, scm.cout, scm.cin, scm.m.weight_orig, dy_ups=True, alpha=0.25)
-            dc1, _ = ops.conv_fused([Seg(dy, ups=True)], I['0.c2t'], c2m.cin, ocode=code, gate_x=c1)
+                wgrad_all(lambda sl: Seg(c1[sl], code=U(b.ctrl_h, sl), relu=True), dy, c2m, c2m.m.bias, scm.m.bias,
+                          dy_ups=True, alpha=b.alpha)
+                wgrad_all(lambda sl: Seg(img[sl], ksize=1), dy, scm, dy_ups=True, alpha=b.alpha)
+            dc1, _ = ops.conv_fused([Seg(dy, ups=True)], I[b.c2t], c2m.cin, ocode=code, gate_x=c1)
             if want_w:
-                wgrad_all(lambda sl: Seg(img[sl]), dc1, c1m.cout, c1m.cin, c1m.m.weight_orig, c1m.m.bias)
-            dimg = None
-            if need_input_grad:
-                if pair is not None:
-                    raise RuntimeError('input gradients of a paired pass are not needed by the D update and not built')
-                dimg_t, _ = ops.conv_fused([Seg(dc1), Seg(dy, ksize=1, ups=True)], I['0.dimg'], c1m.cin, cy=img.shape[-1])
-                dimg = Nhwc(dimg_t, c1m.cin) if ctx.get('nhwc') else ops.to_nchw(dimg_t, c1m.cin)
-        except BaseException as e:
-            red.__exit__(type(e), e, None)
-            raise
-        red.__exit__(None, None, None)
+                wgrad_all(lambda sl: Seg(img[sl]), dc1, c1m, c1m.m.bias)
+            if not need_input_grad:
+                return None
+            if pair is not None:
+                raise RuntimeError('input gradients of a paired pass are not needed by the D update and not built')
+            dimg_t, _ = ops.conv_fused([Seg(dc1), Seg(dy, ksize=1, ups=True)], I[b.dimg], c1m.cin, cy=img.shape[-1])
+            return Nhwc(dimg_t, c1m.cin) if ctx.get('nhwc') else ops.to_nchw(dimg_t, c1m.cin)
+
+        # the split-K reductions of one bucket run as one launch when its `with` block ends, before its SN fix-up
+        dimg = None
+        with ops.deferred_reduces():
+            dy = tail_bwd()
+            for bi in reversed(range(cut if split else 1, len(blocks))):
+                dy = block_bwd(blocks[bi], ctx['blocks'][bi], dy)
+            if not split:
+                dimg = first_bwd(dy)
+        if split:
+            # blocks cut .. last and the tail are done: their slabs are reduced; fix them up, hand the bucket out
+            fix(bk['hi'], bk['i_cut'])
+            yield (bk['off_cut'], fp.numel(), False)
+            with ops.deferred_reduces():
+                for bi in reversed(range(1, cut)):
+                    dy = block_bwd(blocks[bi], ctx['blocks'][bi], dy)
+                dimg = first_bwd(dy)
         if want_w:
-            if defer_fix and pair is not None and not (_BUCKETS and split) and not accumulate:
+            if defer_fix and pair is not None and not split and not accumulate:
                 # the caller finishes the update itself (FusedAdam.step_fused_sn_pair: fix-up + Adam in one launch per table):
                 # hand it the raw per-half gradients and the spectral-norm state of the two forwards; gflat stays unwritten
                 self.pending_fix = {'g0': passes[0][1], 'g1': passes[1][1], 'uv0': uv, 'uv1': pair['uv2'], 'sigma0': sigma,
                                     'sigma1': pair['sigma2'], 'tables': [(bk['all'], 0)]}
             else:
-                if not (_BUCKETS and split):
+                if not split:
                     fix(bk['hi'], bk['i_cut'])      # single bucket: the late layers were not fixed up mid-pass
                 fix(bk['lo'], 0)
-            yield ((0, bk['off_cut'], True) if (_BUCKETS and split) else (0, fp.numel(), True))
+            yield ((0, bk['off_cut'], True) if split else (0, fp.numel(), True))
         return dimg

@@ -1185,21 +1185,25 @@ class CodeBatch:
             off += n * d.C
         return out
 
-    def labels_of(self, indicator: Tensor):
-        """(label, reps) when `indicator` carries its labels (`onehot_hint`) and run_labels applies, else None."""
+    def _hinted(self, indicator: Tensor):
+        """(label, reps) when `indicator` carries its labels (`onehot_hint`) and run_labels takes them -- int64 device labels
+        that cover the batch, channel counts that are multiples of 4 -- else None."""
         hint = getattr(indicator, '_mcgen_onehot', None)
         if hint is not None and hint[0].shape[0] * hint[1] == indicator.shape[0] and hint[0].is_cuda and hint[0].dtype == torch.int64 \
                 and all(d.C % 4 == 0 for d in (self._ensure() or self._arr)):
             return hint[0], hint[1]
         return None
 
+    def labels_of(self, indicator: Tensor):
+        """(label, reps) when `indicator` carries its labels (`onehot_hint`) and run_labels applies, else None."""
+        return self._hinted(indicator)
+
     def run_any(self, indicator: Tensor, scale: Optional[Tensor] = None, n_half: int = 0):
         """run(), or run_labels() when the indicator carries its labels (`onehot_hint`): the caller built it with
         F.one_hot / ops.onehot_rep, so a row gather gives indicator @ codebook exactly."""
-        hint = getattr(indicator, '_mcgen_onehot', None)
-        if hint is not None and hint[0].shape[0] * hint[1] == indicator.shape[0] and hint[0].is_cuda \
-                and all(d.C % 4 == 0 for d in (self._ensure() or self._arr)):
-            return self.run_labels(hint[0], hint[1], scale, n_half)
+        lab = self._hinted(indicator)
+        if lab is not None:
+            return self.run_labels(lab[0], lab[1], scale, n_half)
         return self.run(indicator, scale, n_half)
 
     def _tables_for(self, n: int, device):

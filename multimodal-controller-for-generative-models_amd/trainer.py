@@ -320,7 +320,7 @@ class GANTrainer:
         return self.loss_d
 
     def d_apply(self):
-        pending = getattr(self.deng, 'pending_fix', None)
+        pending = self.deng.pending_fix
         if pending is not None:
             self.deng.pending_fix = None
             self.opt_d.step_fused_sn_pair(pending)

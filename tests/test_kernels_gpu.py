@@ -426,6 +426,30 @@ def test_label_gather_equals_indicator_product():
         assert torch.equal(rep3, F.one_hot(label, modes).float().repeat(3, 1)) and torch.equal(lab32, label.int().repeat(3))
 
 
+def test_int32_hint_takes_the_indicator_product():
+    """A hinted indicator whose labels are not int64 is not a case for run_labels (which takes int64 only): labels_of says
+    None and run_any falls back to the indicator product -- the codes of run(indicator), bit for bit."""
+    ops = _ops()
+    g = torch.Generator().manual_seed(78)
+
+    class MC:
+        pass
+    m = MC(); m.codebook = (torch.rand(10, 8, generator=g) < 0.5).float().cuda()
+    n, reps = 24, 2
+    label = torch.randint(0, 10, (n,), generator=g).cuda()
+    ind = F.one_hot(label, 10).float().repeat(reps, 1)
+    scale = (torch.rand(1, generator=g) + 0.5).cuda()
+    cb = ops.CodeBatch([m], [0])
+    want = cb.run(ind, scale, n)
+    hinted = ops.onehot_hint(ind.clone(), label.int(), reps)
+    assert cb.labels_of(hinted) is None
+    got = cb.run_any(hinted, scale, n)
+    assert len(got) == 1 and torch.equal(got[0], want[0])
+    # (the same hint with int64 labels is taken: the gather gives the same bits)
+    hinted64 = ops.onehot_hint(ind.clone(), label, reps)
+    assert cb.labels_of(hinted64) is not None and torch.equal(cb.run_any(hinted64, scale, n)[0], want[0])
+
+
 def test_bn_finalize_and_backward():
     ops = _ops()
     g = torch.Generator().manual_seed(31)

@@ -427,6 +427,64 @@ def test_gradients_vs_oracle(fixture, g_hidden, d_hidden, classes, data_name):
     check(got, {k: v for k, v in ref.items()}, 'G-step')
 
 
+def test_single_block_discriminator_gradients_vs_oracle():
+    """A discriminator with ONE residual block (hidden sizes [16]: the FirstDisResBlock and the tail; bucket_cut() == 0) at
+    the small fixture's shapes: the backward pass has no DisResBlock to walk and nothing to split.  Every parameter
+    gradient of one D loss, and the image gradient the generator update takes from D (the G loss differentiated with
+    respect to D's input: what this discriminator contributes to a G step), against autograd on the CPU oracle, to
+    test_gradients_vs_oracle's bound; a pass asked to split still hands out one bucket, with the same gradients."""
+    from oracle import mcgan_oracle as O
+    d = gu.load_npz('mcgan_small.npz')
+    torch.manual_seed(5)
+    m = _build([32] * 4, [16], 10, 'CIFAR10')
+    gen = torch.Generator().manual_seed(6)
+    sd = {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
+    for k in sd:                                            # (init_param zeroes the biases: give the bias paths something)
+        if k.endswith('.bias'):
+            sd[k] = torch.rand(sd[k].shape, generator=gen) * 0.1 - 0.05
+    m.load_state_dict(sd)
+    m.train(True)
+    deng = m.discriminator._engine()
+    assert len(deng.plan.blocks) == 1 and deng.bucket_cut() == 0
+    img, lab = torch.from_numpy(d['img']), torch.from_numpy(d['label'])
+    ind = O.one_hot(lab, 10)
+
+    def check(got, ref, what):
+        bad = []
+        for k, r in ref.items():
+            g = got[k].cpu()
+            err = float((g - r).abs().max())
+            scale = float(r.abs().max()) + 1e-8
+            if err > 2e-4 * scale + 1e-6:
+                bad.append(f'{k}: err {err:.3e} vs scale {scale:.3e}')
+        assert not bad, what + ' mismatches:\n' + '\n'.join(bad)
+
+    fake_img = torch.tanh(torch.randn(img.shape, generator=torch.Generator().manual_seed(9)))
+    ref = _oracle_grads(sd, lambda st: torch.relu(1.0 - O.discriminator_forward(st, img, ind, True)).mean()
+                        + torch.relu(1.0 + O.discriminator_forward(st, fake_img, ind, True)).mean())
+    assert any(k.startswith('discriminator.') for k in ref)
+    loss = torch.relu(1.0 - m.discriminate(img.cuda(), lab.cuda())).mean() \
+        + torch.relu(1.0 + m.discriminate(fake_img.cuda(), lab.cuda())).mean()
+    loss.backward()
+    check({k: p.grad for k, p in m.named_parameters() if p.grad is not None}, ref, 'D-step')
+    # the generator update's half of the pass: the gradient of the G loss with respect to the image D reads
+    m.load_state_dict(sd)
+    x_ref = fake_img.clone().requires_grad_(True)
+    (-O.discriminator_forward({k: v.clone() for k, v in sd.items()}, x_ref, ind, True).mean()).backward()
+    x = fake_img.cuda().requires_grad_(True)
+    (-m.discriminate(x, lab.cuda()).mean()).backward()
+    check({'d image': x.grad}, {'d image': x_ref.grad}, 'G-step')
+    # the engine's own pass, asked for two buckets: one, at the end
+    m.load_state_dict(sd)
+    ref = _oracle_grads(sd, lambda st: O.discriminator_forward(st, img, ind, True).mean())
+    logit, ctx = deng.forward(img.cuda(), ind.cuda(), True)
+    gflat = torch.zeros_like(deng.flat_p.flat)
+    dlogit = torch.full((img.shape[0],), 1.0 / img.shape[0], device='cuda')
+    buckets = list(deng.backward_iter(ctx, dlogit, gflat, False, False, split=True))
+    assert buckets == [(0, gflat.numel(), True)]
+    check({'discriminator.' + k: deng.flat_p.view_of(gflat, p) for k, p in m.discriminator.named_parameters()}, ref, 'engine pass')
+
+
 def test_grouped_generator_passes_match_per_update_passes():
     """GANTrainer runs the five training-mode generator forwards of an iteration (train_gan.py:145-146, one per
     discriminator update, on unchanged generator weights) as ONE pass over 5 N images with BatchNorm statistics per
