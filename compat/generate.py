@@ -7,7 +7,7 @@ pixelcnn_sampler.py) and decodes them with `ae.decode_code`; MCGAN / CGAN / MCVA
   --save_npy True:  output/npy/generated_<model_tag>.npy, scaled (x + 1) / 2 * 255, plus (save_img) one grid of
                     save_per_mode samples per mode (generate.py:60-84);
   otherwise:        grids of 10 / 50 / 100 modes x save_per_mode samples (generate.py:85-104).
-Grids go through compat/utils.save_img (a .npy next to the requested path).  --generate_per_mode N overrides the
+Grids go through compat/utils.save_img (the image, and a .npy next to the requested path).  --generate_per_mode N overrides the
 process_control table (applied after it), so a short run is possible.  --glow_affine / --glow_conv_lu {True,False} pick
 MCGlow's coupling form and 1x1 convolution the same way (compat/_flags.py).  Shared CLI parsing: compat/_single.parse."""
 import torch

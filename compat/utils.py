@@ -66,10 +66,55 @@ def collate(input):
     return input
 
 
+_range = range                  # `range` is a parameter name in the reference's save_img / make_grid signatures
+
+
+def make_grid(img, nrow=10, padding=2, pad_value=0, range=None):
+    """What `torchvision.utils.save_image(img, path, nrow, padding, pad_value, normalize=(range is not None), range=range)`
+    puts into the file, as uint8 [H, W, 3]: `make_grid`, then x * 255 + 0.5 clamped to [0, 255] and truncated.
+    `img` is [N, C, H, W] (tensor or array; [C, H, W] is one image), C = 1 is replicated to 3 channels; with a range,
+    clamp to it, then (x - lo) / (hi - lo + 1e-5).  xmaps = min(nrow, N) images per row, ceil(N / xmaps) rows, cells of
+    (H + padding) x (W + padding) on a canvas of ymaps * (H + p) + p by xmaps * (W + p) + p filled with pad_value, image k
+    at row k // xmaps, column k % xmaps.  As in torchvision, one image alone is returned without a border.  fp32 throughout."""
+    import math
+    import numpy as np
+    x = img.detach().cpu().numpy() if isinstance(img, torch.Tensor) else np.asarray(img)
+    x = x.astype(np.float32)
+    if x.ndim == 3:
+        x = x[None]
+    if x.ndim != 4 or x.shape[1] not in (1, 3):
+        raise ValueError('Not valid image batch: expected [N, 1 or 3, H, W]')
+    if x.shape[1] == 1:
+        x = np.repeat(x, 3, axis=1)
+    if range is not None:
+        lo, hi = np.float32(range[0]), np.float32(range[1])
+        x = (np.clip(x, lo, hi) - lo) / (hi - lo + np.float32(1e-5))
+    n, c, h, w = x.shape
+    if n == 1:
+        grid = x[0]
+    else:
+        xmaps = min(int(nrow), n)
+        ymaps = int(math.ceil(n / xmaps))
+        ch, cw = h + padding, w + padding
+        grid = np.full((c, ymaps * ch + padding, xmaps * cw + padding), pad_value, dtype=np.float32)
+        for k in _range(n):
+            r, q = divmod(k, xmaps)
+            grid[:, r * ch + padding:r * ch + padding + h, q * cw + padding:q * cw + padding + w] = x[k]
+    with np.errstate(invalid='ignore'):                    # a NaN sample (Glow can draw one) casts to an arbitrary byte
+        return np.clip(grid * np.float32(255) + np.float32(0.5), 0, 255).astype(np.uint8).transpose(1, 2, 0)
+
+
 def save_img(img, path, nrow=10, padding=2, pad_value=0, range=None):
-    """utils.py:48-60 needs torchvision.utils.save_image, which this image does not ship: the grid is written as a
-    .npy next to the requested path instead (same tensor, NCHW)."""
+    """utils.py:48-60.  torchvision is not a dependency: the tensor itself goes into a .npy next to the requested path
+    (same tensor, NCHW), and, where Pillow is installed, the grid torchvision.utils.save_image would write goes to
+    `path` (.png, .pdf, ...: whatever Image.save takes for the suffix)."""
     import os
     import numpy as np
     os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
     np.save(os.path.splitext(path)[0] + '.npy', img.detach().cpu().numpy())
+    try:
+        from PIL import Image
+    except ImportError:
+        return
+    Image.init()            # every format plugin: the PDF writer embeds RGB through the JPEG plugin and does not load it itself
+    Image.fromarray(make_grid(img, nrow, padding, pad_value, range)).save(path)
