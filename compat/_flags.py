@@ -22,6 +22,25 @@ def pop_flag(name, argv=None):
     return None
 
 
+OPTIMIZERS = ('SGD', 'RMSprop', 'Adam', 'Adamax')         # train_gan.py:222-236, train_vae.py:151-165
+
+
+def pop_optimizer_flags(argv=None):
+    """--optimizer_name {SGD,RMSprop,Adam,Adamax} / --momentum M -> {cfg key: value} of the flags given.  The drivers set
+    cfg['optimizer_name'] = 'Adam' after their parser ran, as the reference's do (train_vae.py:32, train_gan.py:32), and
+    cfg['momentum'] parses as the int its default is: the two flags are popped first and applied (cfg.update) last."""
+    out = {}
+    v = pop_flag('--optimizer_name', argv)
+    if v is not None:
+        if v not in OPTIMIZERS:
+            raise ValueError('Not valid optimizer name')
+        out['optimizer_name'] = v
+    v = pop_flag('--momentum', argv)
+    if v is not None:
+        out['momentum'] = float(v)
+    return out
+
+
 def pop_glow_flags(argv=None):
     """--glow_affine {True,False} / --glow_conv_lu {True,False} -> {key: bool} of the flags given (none: the table stays)."""
     out = {}

@@ -9,8 +9,9 @@ model-specific overrides on top of this, each citing the lines it restates.
 What differs from the reference, and why (same list as compat/train_gan.py):
   * datasets are device-resident (`compat/data.py`), synthetic when ./data/<name>/<split>.npz is absent;
   * `--engine fused` (default) runs the loop body on `mcgen_amd.trainer.{VAE,Glow,PixelCNN}Trainer` (flat parameter /
-    gradient buffers, fused clip + Adam, HIP-graph replay); `--engine autograd` runs the reference's Python loop body on
-    the nn.Module surface with torch.optim.Adam;
+    gradient buffers, fused clip + optimizer, HIP-graph replay); `--engine autograd` runs the reference's Python loop body
+    on the nn.Module surface with the torch.optim class; either way the optimizer is cfg['optimizer_name'] -- 'Adam' as the
+    reference's drivers set it, or what --optimizer_name / --momentum (compat/_flags.py) say;
   * --world_size > 1 is one process per GPU under torch.distributed.run (RCCL), not nn.DataParallel;
   * the learning rate of the fused optimizer lives in device memory (mcgen_adam's lr_dev), so ReduceLROnPlateau steps
     do not invalidate the captured graphs.
@@ -31,6 +32,7 @@ import torch.optim as optim  # noqa: E402
 
 import models  # noqa: E402,F401
 import data as data_shim  # noqa: E402
+from _flags import pop_optimizer_flags  # noqa: E402
 from config import cfg  # noqa: E402
 from data import fetch_dataset, make_data_loader  # noqa: E402
 from logger import Logger  # noqa: E402
@@ -48,6 +50,7 @@ def parse(overrides):
     """train_vae.py:18-36: every scalar cfg key is a flag, --control_name, then the driver's hard overrides."""
     for k, v in _YML_DEFAULTS.items():
         cfg.setdefault(k, v)
+    optimizer_flags = pop_optimizer_flags()
     ap = argparse.ArgumentParser(description='cfg')
     for k in cfg:
         if isinstance(cfg[k], (str, int, float)) or cfg[k] is None:
@@ -70,6 +73,7 @@ def parse(overrides):
     cfg['weight_decay'] = 0
     cfg['scheduler_name'] = 'ReduceLROnPlateau'
     cfg.update(overrides)
+    cfg.update(optimizer_flags)                   # --optimizer_name / --momentum (compat/_flags.py)
     return extra
 
 
@@ -233,6 +237,12 @@ class Driver:
             print('Experiment: {}'.format(cfg['model_tag']))
             self.run_experiment()
 
+    def make_trainer(self, model, world=1):
+        """The fused counterpart of make_optimizer (train_vae.py:151-165): the trainer builds the optimizer cfg names."""
+        return self.trainer_cls(model, lr=cfg['lr'], weight_decay=cfg['weight_decay'], optimizer=cfg['optimizer_name'],
+                                momentum=cfg['momentum'],
+                                dist_group=(torch.distributed.group.WORLD if world > 1 else None), world_size=world)
+
     def run_experiment(self):
         from mcgen_amd import dist as mdist
         world = int(cfg['world_size'])
@@ -258,8 +268,7 @@ class Driver:
             torch.cuda.manual_seed(seed + rank)
             loader.set_shard(rank, world)
         if self.extra['engine'] == 'fused':
-            self.tr = self.trainer_cls(model, lr=cfg['lr'], weight_decay=cfg['weight_decay'],
-                                       dist_group=(torch.distributed.group.WORLD if world > 1 else None), world_size=world)
+            self.tr = self.make_trainer(model, world)
             optimizer = self.tr.opt
             scheduler = FusedSchedule(optimizer)
         else:

@@ -9,7 +9,8 @@ What differs, and why:
     reference's own `datasets` package needs torchvision): uint8 images + labels, normalised to (-1, 1) and batched
     on the GPU by `mcgen_amd.data.DeviceLoader` (data.py:19-55,65-82: ToTensor + Normalize(0.5, 0.5), shuffle);
   * `--engine fused` (default) runs the loop body as `GraphedGANTrainer` (fused Adam, HIP-graph replay);
-    `--engine autograd` runs the reference's own Python loop on the nn.Module surface with torch.optim.Adam;
+    `--engine autograd` runs the reference's own Python loop on the nn.Module surface with the torch.optim class; either
+    way the optimizer is cfg['optimizer_name'] ('Adam' unless --optimizer_name / --momentum, compat/_flags.py, say otherwise);
   * --world_size > 1 means one process per GPU under torch.distributed.run (RCCL), not nn.DataParallel;
   * test() generates `generate_per_mode` images per class (train_gan.py:197-207).  On COIL100 / Omniglot, with the trained
     feature classifier at ./metrics_tf/res/classifier/ (where the reference keeps it; compat/train_classifier.py writes it),
@@ -35,6 +36,7 @@ import torch.nn.functional as F  # noqa: E402
 
 import models  # noqa: E402  (the compat shim: mcgen_amd's module trees under the reference's names)
 import data as data_shim  # noqa: E402
+from _flags import pop_optimizer_flags  # noqa: E402
 from config import cfg  # noqa: E402
 from data import fetch_dataset, make_data_loader  # noqa: E402
 from logger import Logger  # noqa: E402
@@ -42,6 +44,7 @@ from utils import process_control, process_dataset, save, load  # noqa: E402
 
 
 def parse():
+    optimizer_flags = pop_optimizer_flags()                  # --optimizer_name / --momentum (compat/_flags.py)
     ap = argparse.ArgumentParser(description='cfg')
     for k in cfg:                                            # train_gan.py:19-24: every cfg key is a flag
         if isinstance(cfg[k], (str, int, float)) or cfg[k] is None:
@@ -61,6 +64,8 @@ def parse():
         cfg['control_name'] = ''
     elif cfg.get('control_name'):
         cfg['control'] = {'controller_rate': cfg['control_name'].split('_')[0]}
+    cfg['optimizer_name'] = 'Adam'                           # train_gan.py:32
+    cfg.update(optimizer_flags)
     return extra
 
 
@@ -77,10 +82,25 @@ def make_model():
     return getattr(models, cfg['model_name'])()
 
 
-def make_optimizer(model, lr, betas):                        # train_gan.py:222-236 (Adam branch)
-    if cfg['optimizer_name'] != 'Adam':
-        raise ValueError('Not valid optimizer name')
-    return torch.optim.Adam(model.parameters(), lr=lr, weight_decay=cfg['weight_decay'], betas=betas)
+def make_optimizer(model, lr, betas):                        # train_gan.py:222-236
+    name = cfg['optimizer_name']
+    if name == 'SGD':
+        return torch.optim.SGD(model.parameters(), lr=lr, momentum=cfg['momentum'], weight_decay=cfg['weight_decay'])
+    if name == 'RMSprop':
+        return torch.optim.RMSprop(model.parameters(), lr=lr, momentum=cfg['momentum'], weight_decay=cfg['weight_decay'])
+    if name == 'Adam':
+        return torch.optim.Adam(model.parameters(), lr=lr, weight_decay=cfg['weight_decay'], betas=betas)
+    if name == 'Adamax':
+        return torch.optim.Adamax(model.parameters(), lr=lr, weight_decay=cfg['weight_decay'], betas=betas)
+    raise ValueError('Not valid optimizer name')
+
+
+def make_trainer(model, lr, betas, world=1):
+    """The fused counterpart of make_optimizer: GraphedGANTrainer builds cfg['optimizer_name'] for both networks."""
+    from mcgen_amd.trainer import GraphedGANTrainer
+    return GraphedGANTrainer(model, cfg['classes_size'], lr=lr, betas=betas, optimizer=cfg['optimizer_name'],
+                             momentum=cfg['momentum'], weight_decay=cfg['weight_decay'],
+                             dist_group=(torch.distributed.group.WORLD if world > 1 else None), world_size=world)
 
 
 def make_scheduler(optimizer):                               # train_gan.py:239-256 ('None' and the epoch-stepped ones)
@@ -181,7 +201,6 @@ def run():
     process_control()
     from mcgen_amd import dist as mdist
     from mcgen_amd.checkpoint import make_checkpoint, resume
-    from mcgen_amd.trainer import GraphedGANTrainer
     rank, world, local = mdist.init_from_env() if int(cfg['world_size']) > 1 else (0, 1, 0)
     cfg['device'] = f'cuda:{local}'
     torch.cuda.set_device(local)
@@ -208,8 +227,7 @@ def run():
         loader.set_shard(rank, world, seed)
     path = os.path.join(extra['output_dir'], 'model', f'{cfg["model_tag"]}_checkpoint.pt')
     if extra['engine'] == 'fused':
-        tr = GraphedGANTrainer(model, cfg['classes_size'], lr=2e-4, betas=(0.5, 0.999),
-                               dist_group=(torch.distributed.group.WORLD if world > 1 else None), world_size=world)
+        tr = make_trainer(model, 2e-4, (0.5, 0.999), world)
         optimizer = {'generator': tr.opt_g, 'discriminator': tr.opt_d}
     else:
         tr = None

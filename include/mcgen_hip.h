@@ -493,6 +493,22 @@ int mcgen_sn_fix_pair_adam(const float* g_src0, const float* g_src1, float* p, f
                            float lr, const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, int64_t* step,
                            int advance_step, void* stream);
 
+/* The other optimizers of cfg['optimizer_name'] (train_gan.py:222-236, train_vae.py:151-165) over one flat fp32 buffer
+ * (csrc/optim_ops.hip): torch.optim's single-tensor arithmetic, g' = g + weight_decay * p when weight_decay != 0.
+ * lr, lr_dev and step as in mcgen_adam; every call advances step[0] by one.
+ * mcgen_sgd (no dampening, no Nesterov): buf = momentum * buf + g'; p -= lr * buf.  A zero buf gives torch's first step.
+ *   momentum = 0: buf = NULL and p -= lr * g'.
+ * mcgen_rmsprop (not centered): square_avg = alpha * square_avg + (1 - alpha) * g'^2; avg = sqrt(square_avg) + eps;
+ *   momentum > 0: buf = momentum * buf + g' / avg; p -= lr * buf.   momentum = 0: buf = NULL and p -= lr * g' / avg.
+ * mcgen_adamax: m = beta1 * m + (1 - beta1) * g'; u = max(beta2 * u, |g'| + eps); p -= lr / (1 - beta1^t) * m / u with
+ *   t = step[0] + 1. */
+int mcgen_sgd(float* p, const float* g, float* buf, int64_t n, float lr, const float* lr_dev, float momentum,
+              float weight_decay, int64_t* step, void* stream);
+int mcgen_rmsprop(float* p, const float* g, float* square_avg, float* buf, int64_t n, float lr, const float* lr_dev,
+                  float alpha, float eps, float momentum, float weight_decay, int64_t* step, void* stream);
+int mcgen_adamax(float* p, const float* g, float* m, float* u, int64_t n, float lr, const float* lr_dev, float beta1,
+                 float beta2, float eps, float weight_decay, int64_t* step, void* stream);
+
 /* ---- MCGlow-specific kernels (reference: models/mcglow.py) ------------------------------------------------- */
 /* Block squeeze / unsqueeze (mcglow.py:221-223, 262-265): [N,H,W,C] <-> [N,H/2,W/2,4C], channel c*4 + 2*dh + dw.
  * inverse = 0: x is the big tensor (pitch Cp_big), y the squeezed one (pitch Cp_small); inverse = 1: the other way. */

@@ -1062,6 +1062,34 @@ def adam(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: Tensor, lr, betas=(0.
                                  weight_decay, _p(step), _stream()), 'adam')
 
 
+def sgd(p: Tensor, g: Tensor, buf: Optional[Tensor], step: Tensor, lr, momentum: float = 0.0, weight_decay: float = 0.0):
+    """mcgen_sgd: torch.optim.SGD (no dampening, no Nesterov).  `buf`: the momentum buffer, None when momentum == 0.
+    `step` and `lr` as in ops.adam."""
+    assert step.dtype == torch.int64 and step.numel() == 2
+    lr_f, lr_dev = _lr_args(lr)
+    check(_lib.load().mcgen_sgd(_f32(p), _f32(g), _f32(buf), p.numel(), lr_f, lr_dev, momentum,
+                                weight_decay, _p(step), _stream()), 'sgd')
+
+
+def rmsprop(p: Tensor, g: Tensor, square_avg: Tensor, buf: Optional[Tensor], step: Tensor, lr, alpha: float = 0.99,
+            eps: float = 1e-8, momentum: float = 0.0, weight_decay: float = 0.0):
+    """mcgen_rmsprop: torch.optim.RMSprop (not centered).  `buf`: the momentum buffer, None when momentum == 0.
+    `step` and `lr` as in ops.adam."""
+    assert step.dtype == torch.int64 and step.numel() == 2
+    lr_f, lr_dev = _lr_args(lr)
+    check(_lib.load().mcgen_rmsprop(_f32(p), _f32(g), _f32(square_avg), _f32(buf), p.numel(), lr_f,
+                                    lr_dev, alpha, eps, momentum, weight_decay, _p(step), _stream()), 'rmsprop')
+
+
+def adamax(p: Tensor, g: Tensor, m: Tensor, u: Tensor, step: Tensor, lr, betas=(0.9, 0.999), eps: float = 1e-8,
+           weight_decay: float = 0.0):
+    """mcgen_adamax: torch.optim.Adamax (`m`: exp_avg, `u`: exp_inf).  `step` and `lr` as in ops.adam."""
+    assert step.dtype == torch.int64 and step.numel() == 2
+    lr_f, lr_dev = _lr_args(lr)
+    check(_lib.load().mcgen_adamax(_f32(p), _f32(g), _f32(m), _f32(u), p.numel(), lr_f, lr_dev, betas[0], betas[1], eps,
+                                   weight_decay, _p(step), _stream()), 'adamax')
+
+
 # ---- batched small launches (one launch per network pass instead of one per layer) ----------------------
 def _struct_table(arr, device) -> Tensor:
     return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)

@@ -37,20 +37,19 @@ _FUSE_TAIL = _flag('MCGEN_FUSE_TAIL', '1') != '0'        # D tail forward + hing
 _ONE_GRAPH = _flag('MCGEN_ONE_GRAPH', '1') != '0'        # single rank: the whole loop body as one HIP graph (0: one graph per phase, as a multi-rank run)
 
 
-class FusedAdam:
-    """torch.optim.Adam semantics over one flat parameter buffer: one launch per step."""
+class _FusedOptimizer:
+    """What the fused optimizers share: the learning rate as a device scalar and the step counter's buffer."""
 
-    def __init__(self, flat_state: FlatState, lr=2e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.0):
+    def _init_buffers(self, flat_state: FlatState, lr) -> torch.Tensor:
         self.fs = flat_state
-        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         flat = self.fs.ensure()
-        self.m = torch.zeros_like(flat)
-        self.v = torch.zeros_like(flat)
         self._step_buf = torch.zeros(2, dtype=torch.int64, device=flat.device)     # {step counter, launch ticket} (ops.adam)
         self.step_count = self._step_buf[:1]
         # the learning rate lives in device memory and the kernels read it when they run (mcgen_adam's lr_dev): a
         # scheduler step is one fill_ and the captured graphs stay valid (ADVICE round 3)
         self._lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=flat.device) if flat.is_cuda else None
+        self.lr = lr
+        return flat
 
     @property
     def lr(self):
@@ -62,17 +61,31 @@ class FusedAdam:
         if getattr(self, '_lr_dev', None) is not None:
             self._lr_dev.fill_(self._lr)
 
+    def set_lr(self, lr: float):
+        self.lr = float(lr)
+
+    def _lr_arg(self):
+        return self._lr_dev if self._lr_dev is not None else self._lr
+
+
+class FusedAdam(_FusedOptimizer):
+    """torch.optim.Adam semantics over one flat parameter buffer: one launch per step."""
+
+    def __init__(self, flat_state: FlatState, lr=2e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.0):
+        self.betas, self.eps, self.wd = betas, eps, weight_decay
+        flat = self._init_buffers(flat_state, lr)
+        self.m = torch.zeros_like(flat)
+        self.v = torch.zeros_like(flat)
+
     def hyper(self):
         """The hyper-parameters a launch bakes in as kernel arguments (a captured HIP graph replays the values it was
         captured with: the graphed trainers compare this key on every iteration and re-capture when it moved).  The
         learning rate is NOT among them: it is read from device memory at execution time."""
         return (tuple(float(b) for b in self.betas), float(self.eps), float(self.wd))
 
-    def set_lr(self, lr: float):
-        self.lr = float(lr)
-
-    def _lr_arg(self):
-        return self._lr_dev if self._lr_dev is not None else self._lr
+    def state_tensors(self):
+        """The device tensors that make up the optimizer's state: what a capture warm-up snapshots and restores."""
+        return [self.m, self.v, self.step_count]
 
     def step(self, gflat: torch.Tensor):
         flat = self.fs.ensure()
@@ -138,9 +151,185 @@ class FusedAdam:
             self.step_count.fill_(steps.pop())
 
 
+class _FusedTorchState(_FusedOptimizer):
+    """state_dict() / load_state_dict() of FusedSGD, FusedRMSprop and FusedAdamax in the format of the matching
+    torch.optim class (the reference checkpoints optimizer.state_dict(), train_vae.py:85): a subclass names its state
+    in `_slots()`, its hyper-parameters in `_group()` and takes a loaded group in `_load_group()`."""
+    _has_step = True                     # torch keeps a per-parameter 'step' (SGD does not)
+
+    def _slots(self):                    # [(torch's state key, flat buffer)], in torch's order
+        raise NotImplementedError
+
+    def _group(self):                    # torch's param_groups[0] without 'params'
+        raise NotImplementedError
+
+    def _load_group(self, g):            # refuse what the kernel does not implement, then take the hyper-parameters
+        raise NotImplementedError
+
+    def _momentum_buffer(self):
+        """The momentum buffer exists exactly when momentum > 0 (mcgen_sgd / mcgen_rmsprop take NULL otherwise)."""
+        if self.momentum == 0:
+            self.buf = None
+        elif self.buf is None:
+            self.buf = torch.zeros_like(self.fs.ensure())
+        return self.buf
+
+    def state_tensors(self):
+        """The device tensors that make up the optimizer's state: what a capture warm-up snapshots and restores."""
+        return [t for _, t in self._slots()] + [self.step_count]
+
+    def _bump_params(self):
+        for p in self.fs.tensors:
+            _bump(p)
+
+    def state_dict(self):
+        """{'state': {i: {...}}, 'param_groups': [...]} over the parameters in `model.parameters()` order; 'state' is
+        empty before the first step (and always for SGD without momentum), as torch's is."""
+        self.fs.ensure()
+        state, slots = {}, self._slots()
+        if int(self.step_count) > 0 and (slots or self._has_step):
+            step = self.step_count.to(torch.float32).reshape(())
+            for i, t in enumerate(self.fs.tensors):
+                state[i] = {'step': step.clone()} if self._has_step else {}
+                for key, buf in slots:
+                    state[i][key] = self.fs.view_of(buf, t).clone()
+        return {'state': state, 'param_groups': [dict(self._group(), params=list(range(len(self.fs.tensors))))]}
+
+    def load_state_dict(self, sd):
+        self.fs.ensure()
+        groups = sd['param_groups']
+        if len(groups) != 1 or len(groups[0]['params']) != len(self.fs.tensors):
+            raise ValueError('Not valid optimizer state: expected one parameter group over the network\'s parameters')
+        g = groups[0]
+        if g.get('maximize'):
+            raise ValueError('Not valid optimizer state: maximize is not supported')
+        self._load_group(g)
+        for t in self.state_tensors():
+            t.zero_()
+        steps = set()
+        for key, t in zip(g['params'], self.fs.tensors):
+            st = sd['state'].get(key)
+            if not st:
+                continue
+            for name, buf in self._slots():
+                self.fs.view_of(buf, t).copy_(st[name])
+            steps.add(int(st['step']) if self._has_step else 1)     # (SGD: any state means "has stepped")
+        if len(steps) > 1:
+            raise ValueError('Not valid optimizer state: parameters disagree on the step count')
+        if steps:
+            self.step_count.fill_(steps.pop())
+
+
+class FusedSGD(_FusedTorchState):
+    """torch.optim.SGD (momentum, no dampening, no Nesterov) over one flat parameter buffer: one launch per step
+    (mcgen_sgd).  momentum = 0 keeps no state at all."""
+    _has_step = False
+
+    def __init__(self, flat_state: FlatState, lr=1e-3, momentum=0.0, weight_decay=0.0):
+        self.momentum, self.wd, self.buf = momentum, weight_decay, None
+        self._init_buffers(flat_state, lr)
+        self._momentum_buffer()
+
+    def hyper(self):
+        """What a launch bakes in as kernel arguments (see FusedAdam.hyper): not the learning rate."""
+        return (float(self.momentum), float(self.wd))
+
+    def _slots(self):
+        buf = self._momentum_buffer()
+        return [] if buf is None else [('momentum_buffer', buf)]
+
+    def step(self, gflat: torch.Tensor):
+        ops.sgd(self.fs.ensure(), gflat, self._momentum_buffer(), self._step_buf, self._lr_arg(), self.momentum, self.wd)
+        self._bump_params()
+
+    def _group(self):
+        return {'lr': self.lr, 'momentum': self.momentum, 'dampening': 0, 'weight_decay': self.wd, 'nesterov': False,
+                'maximize': False, 'foreach': None, 'differentiable': False, 'fused': None}
+
+    def _load_group(self, g):
+        if g.get('nesterov') or g.get('dampening', 0) != 0:
+            raise ValueError('Not valid optimizer state: nesterov / dampening are not supported')
+        self.lr, self.momentum, self.wd = g['lr'], g['momentum'], g['weight_decay']
+
+
+class FusedRMSprop(_FusedTorchState):
+    """torch.optim.RMSprop (not centered) over one flat parameter buffer: one launch per step (mcgen_rmsprop)."""
+
+    def __init__(self, flat_state: FlatState, lr=1e-2, alpha=0.99, eps=1e-8, momentum=0.0, weight_decay=0.0):
+        self.alpha, self.eps, self.momentum, self.wd, self.buf = alpha, eps, momentum, weight_decay, None
+        flat = self._init_buffers(flat_state, lr)
+        self.sq = torch.zeros_like(flat)
+        self._momentum_buffer()
+
+    def hyper(self):
+        """What a launch bakes in as kernel arguments (see FusedAdam.hyper): not the learning rate."""
+        return (float(self.alpha), float(self.eps), float(self.momentum), float(self.wd))
+
+    def _slots(self):
+        buf = self._momentum_buffer()
+        return [('square_avg', self.sq)] + ([] if buf is None else [('momentum_buffer', buf)])
+
+    def step(self, gflat: torch.Tensor):
+        ops.rmsprop(self.fs.ensure(), gflat, self.sq, self._momentum_buffer(), self._step_buf, self._lr_arg(), self.alpha,
+                    self.eps, self.momentum, self.wd)
+        self._bump_params()
+
+    def _group(self):
+        return {'lr': self.lr, 'momentum': self.momentum, 'alpha': self.alpha, 'eps': self.eps, 'centered': False,
+                'weight_decay': self.wd, 'capturable': False, 'foreach': None, 'maximize': False, 'differentiable': False}
+
+    def _load_group(self, g):
+        if g.get('centered'):
+            raise ValueError('Not valid optimizer state: centered is not supported')
+        self.lr, self.momentum, self.alpha, self.eps, self.wd = g['lr'], g['momentum'], g['alpha'], g['eps'], g['weight_decay']
+
+
+class FusedAdamax(_FusedTorchState):
+    """torch.optim.Adamax over one flat parameter buffer: one launch per step (mcgen_adamax; `m`: exp_avg, `u`: exp_inf)."""
+
+    def __init__(self, flat_state: FlatState, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        self.betas, self.eps, self.wd = betas, eps, weight_decay
+        flat = self._init_buffers(flat_state, lr)
+        self.m = torch.zeros_like(flat)
+        self.u = torch.zeros_like(flat)
+
+    def hyper(self):
+        """What a launch bakes in as kernel arguments (see FusedAdam.hyper): not the learning rate."""
+        return (tuple(float(b) for b in self.betas), float(self.eps), float(self.wd))
+
+    def _slots(self):
+        return [('exp_avg', self.m), ('exp_inf', self.u)]
+
+    def step(self, gflat: torch.Tensor):
+        ops.adamax(self.fs.ensure(), gflat, self.m, self.u, self._step_buf, self._lr_arg(), self.betas, self.eps, self.wd)
+        self._bump_params()
+
+    def _group(self):
+        return {'lr': self.lr, 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': self.wd, 'foreach': None,
+                'maximize': False, 'differentiable': False, 'capturable': False}
+
+    def _load_group(self, g):
+        self.lr, self.betas, self.eps, self.wd = g['lr'], tuple(g['betas']), g['eps'], g['weight_decay']
+
+
+def make_fused_optimizer(name: str, flat_state: FlatState, lr, betas=(0.9, 0.999), momentum=0.0, weight_decay=0.0):
+    """The fused counterpart of the reference's make_optimizer (train_gan.py:222-236, train_vae.py:151-165): the same
+    arguments reach the same optimizers (momentum: SGD and RMSprop; betas: Adam and Adamax)."""
+    if name == 'SGD':
+        return FusedSGD(flat_state, lr=lr, momentum=momentum, weight_decay=weight_decay)
+    if name == 'RMSprop':
+        return FusedRMSprop(flat_state, lr=lr, momentum=momentum, weight_decay=weight_decay)
+    if name == 'Adam':
+        return FusedAdam(flat_state, lr=lr, betas=betas, weight_decay=weight_decay)
+    if name == 'Adamax':
+        return FusedAdamax(flat_state, lr=lr, betas=betas, weight_decay=weight_decay)
+    raise ValueError('Not valid optimizer name')
+
+
 class GANTrainer:
     def __init__(self, model, classes: int, lr=2e-4, betas=(0.5, 0.999), d_iters: int = 5, g_iters: int = 1,
-                 dist_group=None, world_size: int = 1, grad_wire_dtype: Optional[torch.dtype] = None):
+                 dist_group=None, world_size: int = 1, grad_wire_dtype: Optional[torch.dtype] = None,
+                 optimizer: str = 'Adam', momentum: float = 0.0, weight_decay: float = 0.0):
         self.model = model
         self.grad_wire_dtype = grad_wire_dtype            # torch.bfloat16: gradient buckets cross the links as bf16 (dist.allreduce_mean_)
         self._ov = None                                   # overlap bookkeeping (overlap_begin / overlap_end)
@@ -150,8 +339,9 @@ class GANTrainer:
         self.deng = model.discriminator._engine()
         self.geng.flat_p.ensure()
         self.deng._ensure_flat()
-        self.opt_g = FusedAdam(self.geng.flat_p, lr, betas)
-        self.opt_d = FusedAdam(self.deng.flat_p, lr, betas)
+        # cfg['optimizer_name'] of train_gan.py:222-236: both networks take the same optimizer, as in the reference
+        self.opt_g = make_fused_optimizer(optimizer, self.geng.flat_p, lr, betas, momentum, weight_decay)
+        self.opt_d = make_fused_optimizer(optimizer, self.deng.flat_p, lr, betas, momentum, weight_decay)
         self.grad_g = torch.zeros_like(self.geng.flat_p.flat)
         self.grad_d = torch.zeros_like(self.deng.flat_p.flat)
         self.group, self.world = dist_group, world_size
@@ -345,8 +535,14 @@ class GANTrainer:
         self.opt_g.step(self.grad_g)
         self.geng.refresh_images(force=True)
 
+    @property
+    def _fuse_d(self) -> bool:
+        """The one-launch spectral-norm fix + update of a paired D pass exists for Adam only: any other optimizer takes
+        the fixed gradient from grad_d (the route a multi-rank run takes)."""
+        return _FUSE_D_ADAM and hasattr(self.opt_d, 'step_fused_sn_pair')
+
     def d_update(self, img, ind, fake, ind2=None, x2=None, codes=None):
-        for lo, hi, _last in self.d_compute_iter(img, ind, fake, ind2, x2, codes, fuse=_FUSE_D_ADAM):
+        for lo, hi, _last in self.d_compute_iter(img, ind, fake, ind2, x2, codes, fuse=self._fuse_d):
             self._reduce_bucket(self.grad_d, lo, hi)
         self._join_comm()
         self.d_apply()
@@ -457,15 +653,16 @@ class GraphedGANTrainer(GANTrainer):
     # ---- state snapshot around the warm-up --------------------------------------------------------
     def _snapshot(self):
         sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        opt = [(o.m.clone(), o.v.clone(), o.step_count.clone()) for o in (self.opt_g, self.opt_d)]
+        opt = [[t.clone() for t in o.state_tensors()] for o in (self.opt_g, self.opt_d)]
         return sd, opt
 
     def _restore(self, snap):
         sd, opt = snap
         with torch.no_grad():
             self.model.load_state_dict(sd)
-            for o, (m, v, st) in zip((self.opt_g, self.opt_d), opt):
-                o.m.copy_(m); o.v.copy_(v); o.step_count.copy_(st)
+            for o, saved in zip((self.opt_g, self.opt_d), opt):
+                for t, s in zip(o.state_tensors(), saved):
+                    t.copy_(s)
         self.geng.flat_p.ensure()
         self.deng._ensure_flat()
         self.geng.refresh_images(force=True)
@@ -475,8 +672,7 @@ class GraphedGANTrainer(GANTrainer):
     # (bench.py re-loads the initial training state every few iterations so that the discriminator never saturates on
     # the synthetic data: a saturated hinge loss makes every discriminator backward pass multiply all-zero gradients.)
     def _state_tensors(self):
-        ts = [self.geng.flat_p.ensure(), self.opt_g.m, self.opt_g.v, self.opt_g.step_count,
-              self.opt_d.m, self.opt_d.v, self.opt_d.step_count]
+        ts = [self.geng.flat_p.ensure()] + self.opt_g.state_tensors() + self.opt_d.state_tensors()
         ts += list(self.deng._ensure_flat())
         ts += [b for b in self.model.generator.buffers() if b.dtype != torch.int64 or b.dim() == 0]
         seen, out = set(), []
@@ -594,8 +790,8 @@ class GraphedGANTrainer(GANTrainer):
 
         def d_iter(j):
             if _NHWC_PAIR:
-                return self.d_compute_iter(None, self.s_ind, None, self.s_ind2, x2=self.s_x2s[j], codes=self.s_codes, fuse=_FUSE_D_ADAM)
-            return self.d_compute_iter(self.s_img, self.s_ind, self.s_fake, self.s_ind2, fuse=_FUSE_D_ADAM)
+                return self.d_compute_iter(None, self.s_ind, None, self.s_ind2, x2=self.s_x2s[j], codes=self.s_codes, fuse=self._fuse_d)
+            return self.d_compute_iter(self.s_img, self.s_ind, self.s_fake, self.s_ind2, fuse=self._fuse_d)
 
         self.g_all = None
         if self.world == 1 and _ONE_GRAPH and fg == self.d_iters and self.g_iters == 1:
@@ -721,13 +917,14 @@ class _FlatTrainer:
     clip and the optimizer are one launch each and a data-parallel run all-reduces one bucket.  `capture` records
     forward+backward and clip+Adam as two HIP graphs; the all-reduce of a multi-rank run sits between the replays."""
 
-    def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), weight_decay=0.0, max_norm=1.0, dist_group=None, world_size=1):
+    def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), weight_decay=0.0, max_norm=1.0, dist_group=None, world_size=1,
+                 optimizer='Adam', momentum=0.0):
         self.model = model
         self.params = [p for p in model.parameters() if p.requires_grad]
         self.fs = FlatState(self.params)
         flat = self.fs.ensure()
         self.gflat = torch.zeros_like(flat)
-        self.opt = FusedAdam(self.fs, lr=lr, betas=betas, weight_decay=weight_decay)
+        self.opt = make_fused_optimizer(optimizer, self.fs, lr, betas, momentum, weight_decay)   # train_vae.py:151-165
         self.max_norm = max_norm
         self.group, self.world = dist_group, world_size
         self.grad_norm = None
@@ -762,7 +959,7 @@ class _FlatTrainer:
         self._bind_grads()
         self.statics = statics
         sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        opt = (self.opt.m.clone(), self.opt.v.clone(), self.opt.step_count.clone())
+        opt = [t.clone() for t in self.opt.state_tensors()]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), torch.no_grad():
@@ -774,7 +971,8 @@ class _FlatTrainer:
         torch.cuda.synchronize()
         with torch.no_grad():
             self.model.load_state_dict(sd)
-            self.opt.m.copy_(opt[0]); self.opt.v.copy_(opt[1]); self.opt.step_count.copy_(opt[2])
+            for t, s in zip(self.opt.state_tensors(), opt):
+                t.copy_(s)
         self.fs.ensure()
         self._bind_grads()
         torch.cuda.synchronize()
@@ -794,7 +992,7 @@ class _FlatTrainer:
     def _replay(self, *inputs, rand=None):
         """`inputs` fill the leading statics; `rand` (optional) replaces the in-graph redraw of the last one."""
         if self._hyper_key != self.opt.hyper():
-            raise RuntimeError('optimizer hyper-parameters changed after capture(): the captured Adam launch holds the old '
+            raise RuntimeError('optimizer hyper-parameters changed after capture(): the captured optimizer launch holds the old '
                                'values -- call capture() again')
         for s, v in zip(self.statics, inputs):
             s.copy_(v, non_blocking=True)
