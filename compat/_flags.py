@@ -41,6 +41,32 @@ def pop_optimizer_flags(argv=None):
     return out
 
 
+def pop_ema_flags(argv=None):
+    """--ema_decay D / --ema_start K (train_gan.py) -> {'ema_decay': float, 'ema_start': int}; 0 / 0 when not given: no
+    averaged generator.  K counts generator updates: the average copies the parameters until K updates are done."""
+    d, k = pop_flag('--ema_decay', argv), pop_flag('--ema_start', argv)
+    out = {'ema_decay': 0.0 if d is None else float(d), 'ema_start': 0 if k is None else int(k)}
+    if not 0.0 <= out['ema_decay'] < 1.0 or out['ema_start'] < 0:
+        raise ValueError('Not valid --ema_decay / --ema_start: decay in [0, 1), start >= 0')
+    return out
+
+
+def pop_use_ema(argv=None):
+    """--use_ema {True,False} (the sampling drivers) -> bool, False when not given."""
+    v = pop_flag('--use_ema', argv)
+    if v is None:
+        return False
+    if v not in ('True', 'False'):
+        raise ValueError('Not valid --use_ema: {} (True or False)'.format(v))
+    return v == 'True'
+
+
+def check_use_ema(use_ema, model_name):
+    """--use_ema is a flag of the GAN models: only compat/train_gan.py keeps an averaged generator."""
+    if use_ema and model_name not in ('mcgan', 'cgan'):
+        raise ValueError('Not valid model name: --use_ema is a flag of mcgan / cgan')
+
+
 def pop_glow_flags(argv=None):
     """--glow_affine {True,False} / --glow_conv_lu {True,False} -> {key: bool} of the flags given (none: the table stays)."""
     out = {}

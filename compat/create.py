@@ -18,7 +18,7 @@ import models
 import data as data_shim
 from _single import cfg, parse
 from data import fetch_dataset
-from _flags import apply_glow_flags, pop_glow_flags
+from _flags import apply_glow_flags, check_use_ema, pop_glow_flags, pop_use_ema
 from generate import SAMPLE_PER_ITER, _draw, _pop_flag
 from utils import process_control, process_dataset, resume, save, save_img
 
@@ -96,6 +96,9 @@ def load_models_with_epoch(extra):
         ae.train(False)
     model = eval('models.{}().to(cfg["device"])'.format(cfg['model_name']))
     last_epoch, model, _, _, _ = resume(model, cfg['model_tag'], load_tag='best')
+    if extra.get('use_ema'):                              # the averaged generator of a checkpoint trained with --ema_decay
+        from generate import overlay_ema
+        overlay_ema(model, cfg['model_tag'])
     if cfg.get('compute_dtype') == 'bfloat16':
         for m in (model, ae):
             if m is not None and hasattr(m, 'set_compute_dtype'):
@@ -108,11 +111,15 @@ def load_models(extra):
     return load_models_with_epoch(extra)[:3]
 
 
-def main(run_experiment, overrides=None):
-    """create.py:25-35, the loop every evaluation driver of the reference repeats: one `run_experiment(extra)` per seed."""
+def main(run_experiment, overrides=None, accepts_ema=False):
+    """create.py:25-35, the loop every evaluation driver of the reference repeats: one `run_experiment(extra)` per seed.
+    `accepts_ema`: the driver loads a model, so it takes --use_ema {True,False} (mcgan / cgan: sample the averaged generator)."""
     per_mode = _pop_flag('--generate_per_mode')
     glow_flags = pop_glow_flags()                         # --glow_affine / --glow_conv_lu (mcglow)
+    use_ema = pop_use_ema() if accepts_ema else False
     extra = parse(overrides or {})
+    check_use_ema(use_ema, cfg['model_name'])
+    extra['use_ema'] = use_ema
     if cfg['control_name'] == 'None':                     # the baselines take no control (create.py:19-22)
         cfg['control'] = {}
         cfg['control_name'] = ''
@@ -138,4 +145,4 @@ def run_experiment(extra):
 
 
 if __name__ == '__main__':
-    main(run_experiment)
+    main(run_experiment, accepts_ema=True)

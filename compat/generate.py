@@ -9,16 +9,17 @@ pixelcnn_sampler.py) and decodes them with `ae.decode_code`; MCGAN / CGAN / MCVA
   otherwise:        grids of 10 / 50 / 100 modes x save_per_mode samples (generate.py:85-104).
 Grids go through compat/utils.save_img (the image, and a .npy next to the requested path).  --generate_per_mode N overrides the
 process_control table (applied after it), so a short run is possible.  --glow_affine / --glow_conv_lu {True,False} pick
-MCGlow's coupling form and 1x1 convolution the same way (compat/_flags.py).  Shared CLI parsing: compat/_single.parse."""
+MCGlow's coupling form and 1x1 convolution the same way (compat/_flags.py).  --use_ema True (mcgan / cgan) samples the
+averaged generator of a checkpoint trained with --ema_decay.  Shared CLI parsing: compat/_single.parse."""
 import torch
 
 import _single  # noqa: F401  (sys.path)
 import models
 import data as data_shim
-from _flags import apply_glow_flags, pop_flag, pop_glow_flags
+from _flags import apply_glow_flags, check_use_ema, pop_flag, pop_glow_flags, pop_use_ema
 from _single import cfg, parse
 from data import fetch_dataset
-from utils import process_control, process_dataset, resume, save, save_img
+from utils import load, process_control, process_dataset, resume, save, save_img
 
 SAMPLE_PER_ITER = 1000                                    # generate.py:57
 
@@ -61,6 +62,14 @@ def generate(model, ae=None):
                          nrow=save_num_mode, range=(-1, 1))
 
 
+def overlay_ema(model, model_tag, load_tag='best'):
+    """--use_ema True: the checkpoint's averaged generator (its 'generator_ema', written by train_gan.py --ema_decay) laid
+    over the generator that `resume` just loaded."""
+    from mcgen_amd.checkpoint import overlay_averaged_generator
+    path = './output/model/{}_{}.pt'.format(model_tag, load_tag)
+    model.generator.load_state_dict(overlay_averaged_generator(model.generator.state_dict(), load(path)))
+
+
 def run_experiment(extra):
     """generate.py:40-51."""
     seed = int(cfg['model_tag'].split('_')[0])
@@ -76,6 +85,8 @@ def run_experiment(extra):
         ae.train(False)
     model = eval('models.{}().to(cfg["device"])'.format(cfg['model_name']))
     _, model, _, _, _ = resume(model, cfg['model_tag'], load_tag='best')
+    if extra.get('use_ema'):
+        overlay_ema(model, cfg['model_tag'])
     if cfg.get('compute_dtype') == 'bfloat16':
         for m in (model, ae):
             if m is not None and hasattr(m, 'set_compute_dtype'):
@@ -86,7 +97,10 @@ def run_experiment(extra):
 def main():
     per_mode = _pop_flag('--generate_per_mode')
     glow_flags = pop_glow_flags()
+    use_ema = pop_use_ema()
     extra = parse({})
+    check_use_ema(use_ema, cfg['model_name'])
+    extra['use_ema'] = use_ema
     if cfg['control_name'] == 'None':                     # the baselines take no control (generate.py:19-22)
         cfg['control'] = {}
         cfg['control_name'] = ''

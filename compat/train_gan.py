@@ -20,7 +20,11 @@ What differs, and why:
     classifier file -- it logs the pixel statistics of the generated set under 'test/GeneratedMean', 'test/GeneratedStd': a
     STAND-IN, named as such in its log line, with no pivot (the `cgan` baseline's latest checkpoint is then its best);
   * the checkpoint is the reference's dict INCLUDING `scheduler_dict` (torch MultiStepLR state, train_gan.py:239-240) and the
-    pickled `logger.Logger`, so `--resume_mode 1` of the reference's own driver can read a file written here.
+    pickled `logger.Logger`, so `--resume_mode 1` of the reference's own driver can read a file written here;
+  * --ema_decay D (default 0: off) keeps an exponential moving average of the generator's weights and BatchNorm running
+    statistics (trainer.FusedEMA, csrc/ema_ops.hip), updated behind every generator step; --ema_start K copies instead of
+    averaging for the first K generator updates.  test() then runs on the averaged generator (metric names unchanged), and
+    the checkpoint gains one top-level key, 'generator_ema'; `model_dict` keeps the live weights.  The reference has none.
 """
 import argparse
 import os
@@ -36,7 +40,7 @@ import torch.nn.functional as F  # noqa: E402
 
 import models  # noqa: E402  (the compat shim: mcgen_amd's module trees under the reference's names)
 import data as data_shim  # noqa: E402
-from _flags import pop_optimizer_flags  # noqa: E402
+from _flags import pop_ema_flags, pop_optimizer_flags  # noqa: E402
 from config import cfg  # noqa: E402
 from data import fetch_dataset, make_data_loader  # noqa: E402
 from logger import Logger  # noqa: E402
@@ -45,6 +49,7 @@ from utils import process_control, process_dataset, save, load  # noqa: E402
 
 def parse():
     optimizer_flags = pop_optimizer_flags()                  # --optimizer_name / --momentum (compat/_flags.py)
+    ema_flags = pop_ema_flags()                              # --ema_decay / --ema_start: the averaged generator (off at 0)
     ap = argparse.ArgumentParser(description='cfg')
     for k in cfg:                                            # train_gan.py:19-24: every cfg key is a flag
         if isinstance(cfg[k], (str, int, float)) or cfg[k] is None:
@@ -56,6 +61,7 @@ def parse():
     ap.add_argument('--generate_per_mode', default=None, type=int)
     a = vars(ap.parse_args())
     extra = {k: a.pop(k) for k in ('engine', 'synthetic_size', 'output_dir', 'generate_per_mode')}
+    extra.update(ema_flags)
     for k in list(a):
         if k in cfg or k == 'control_name':
             cfg[k] = a[k]
@@ -95,11 +101,12 @@ def make_optimizer(model, lr, betas):                        # train_gan.py:222-
     raise ValueError('Not valid optimizer name')
 
 
-def make_trainer(model, lr, betas, world=1):
-    """The fused counterpart of make_optimizer: GraphedGANTrainer builds cfg['optimizer_name'] for both networks."""
+def make_trainer(model, lr, betas, world=1, ema_decay=0.0, ema_start=0):
+    """The fused counterpart of make_optimizer: GraphedGANTrainer builds cfg['optimizer_name'] for both networks, and the
+    averaged generator when ema_decay > 0."""
     from mcgen_amd.trainer import GraphedGANTrainer
     return GraphedGANTrainer(model, cfg['classes_size'], lr=lr, betas=betas, optimizer=cfg['optimizer_name'],
-                             momentum=cfg['momentum'], weight_decay=cfg['weight_decay'],
+                             momentum=cfg['momentum'], weight_decay=cfg['weight_decay'], ema_decay=ema_decay, ema_start=ema_start,
                              dist_group=(torch.distributed.group.WORLD if world > 1 else None), world_size=world)
 
 
@@ -227,16 +234,19 @@ def run():
         loader.set_shard(rank, world, seed)
     path = os.path.join(extra['output_dir'], 'model', f'{cfg["model_tag"]}_checkpoint.pt')
     if extra['engine'] == 'fused':
-        tr = make_trainer(model, 2e-4, (0.5, 0.999), world)
+        tr = make_trainer(model, 2e-4, (0.5, 0.999), world, extra['ema_decay'], extra['ema_start'])
         optimizer = {'generator': tr.opt_g, 'discriminator': tr.opt_d}
     else:
+        if extra['ema_decay']:
+            raise ValueError('Not valid engine: --ema_decay needs --engine fused')
         tr = None
         optimizer = {'generator': make_optimizer(model.generator, 2e-4, (0.5, 0.999)),
                      'discriminator': make_optimizer(model.discriminator, 2e-4, (0.5, 0.999))}
     scheduler = {k: (FusedSchedule(o) if tr is not None else make_scheduler(o)) for k, o in optimizer.items()}
+    ema = tr.ema if tr is not None else None                 # None: no averaged generator, the checkpoint keeps today's keys
     last_epoch, logger = 1, None
     if int(cfg['resume_mode']) == 1 and os.path.exists(path):                  # train_gan.py:80-81,258-282
-        last_epoch, logger = resume(path, model, optimizer, scheduler)
+        last_epoch, logger = resume(path, model, optimizer, scheduler, ema=ema)
         if tr is not None:
             tr.geng.refresh_images(force=True)
         print(f'Resume from {last_epoch}')
@@ -264,12 +274,16 @@ def run():
                                 '{:.0f} images/s'.format(rate)]}, 'train', mean=False)
         if rank == 0:
             logger.write('train', ['Loss', 'Loss_D', 'Loss_G'])
-        test(model, per_mode, logger, epoch, scorer)
+        if ema is not None:
+            with tr.ema_weights():                           # scorer and stand-in alike describe the averaged generator
+                test(model, per_mode, logger, epoch, scorer)
+        else:
+            test(model, per_mode, logger, epoch, scorer)
         for sch in scheduler.values():                                         # train_gan.py:105-106
             sch.step()
         logger.safe(False)
         if rank == 0:
-            save(make_checkpoint(model, optimizer, epoch + 1, cfg, scheduler=scheduler, logger=logger), path)   # train_gan.py:111-119
+            save(make_checkpoint(model, optimizer, epoch + 1, cfg, scheduler=scheduler, logger=logger, ema=ema), path)   # train_gan.py:111-119
             if scorer is not None:                                             # train_gan.py:119-122
                 cfg['pivot'], best = pivot_update(cfg['pivot'], logger.mean['test/{}'.format(cfg['pivot_metric'])])
                 if best:

@@ -56,4 +56,4 @@ def run_experiment(extra):
 
 
 if __name__ == '__main__':
-    main(run_experiment)
+    main(run_experiment, accepts_ema=True)       # --use_ema: transit on the averaged generator (mcgan / cgan)

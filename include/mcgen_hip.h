@@ -509,6 +509,18 @@ int mcgen_rmsprop(float* p, const float* g, float* square_avg, float* buf, int64
 int mcgen_adamax(float* p, const float* g, float* m, float* u, int64_t n, float lr, const float* lr_dev, float beta1,
                  float beta2, float eps, float weight_decay, int64_t* step, void* stream);
 
+/* The averaged generator (csrc/ema_ops.hip): one launch over a flat fp32 range of n >= 1 elements; the ranges may start
+ * at any 4-byte aligned address (16-byte accesses where both bases share their offset inside a 16-byte line) and must
+ * not overlap.
+ * mcgen_ema_update: t = step[0], read when the kernel runs (step: int64[2] = {counter, ticket = 0}, as mcgen_adam's).
+ *   t < start: ema[i] = p[i], bit for bit;  otherwise ema[i] = decay * ema[i] + (1.0f - decay) * p[i].
+ *   advance = 1: the launch increments step[0] when its last block is done; an update that covers its state with several
+ *   launches passes 1 on the last one only, so the count advances once per update.
+ * mcgen_swap_f32: a[i] <-> b[i], bit for bit. */
+int mcgen_ema_update(float* ema, const float* p, int64_t n, float decay, int64_t start, int64_t* step, int advance,
+                     void* stream);
+int mcgen_swap_f32(float* a, float* b, int64_t n, void* stream);
+
 /* ---- MCGlow-specific kernels (reference: models/mcglow.py) ------------------------------------------------- */
 /* Block squeeze / unsqueeze (mcglow.py:221-223, 262-265): [N,H,W,C] <-> [N,H/2,W/2,4C], channel c*4 + 2*dh + dw.
  * inverse = 0: x is the big tensor (pitch Cp_big), y the squeezed one (pitch Cp_small); inverse = 1: the other way. */

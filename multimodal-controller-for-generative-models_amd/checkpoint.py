@@ -72,9 +72,11 @@ def _opt_state(opt):
     return opt.state_dict()
 
 
-def make_checkpoint(model, optimizer, epoch: int, cfg: Optional[dict] = None, scheduler=None, logger=None) -> Dict[str, Any]:
+def make_checkpoint(model, optimizer, epoch: int, cfg: Optional[dict] = None, scheduler=None, logger=None, ema=None) -> Dict[str, Any]:
     """The dict train_gan.py:112-118 saves (epoch = number of finished epochs).  Tensors are moved to the CPU so the
-    file loads anywhere, as the reference's map_location does on load."""
+    file loads anywhere, as the reference's map_location does on load.  `ema` (trainer.FusedEMA, or None): its state_dict
+    goes under one more top-level key, 'generator_ema', which every loader of the reference's format ignores; without
+    it the dict has exactly the reference's keys."""
     def cpu(sd):
         if isinstance(sd, dict):
             return {k: cpu(v) for k, v in sd.items()}
@@ -84,6 +86,24 @@ def make_checkpoint(model, optimizer, epoch: int, cfg: Optional[dict] = None, sc
     out = {'cfg': dict(cfg) if cfg is not None else None, 'epoch': epoch, 'model_dict': cpu(dict(model.state_dict())),
            'optimizer_dict': cpu(_opt_state(optimizer)),
            'scheduler_dict': cpu(_opt_state(scheduler)) if scheduler is not None else None, 'logger': logger}
+    if ema is not None:
+        out['generator_ema'] = cpu(ema.state_dict())
+    return out
+
+
+def overlay_averaged_generator(generator_state: Dict[str, Any], checkpoint: Dict[str, Any]) -> Dict[str, Any]:
+    """`generator_state` (model.generator.state_dict()) with the checkpoint's averaged parameters and BatchNorm running
+    statistics laid over it -- what --use_ema loads into the generator.  Every other entry (codebooks,
+    num_batches_tracked) stays as it is.  Raises ValueError when the checkpoint was trained without an average."""
+    ema = checkpoint.get('generator_ema')
+    if ema is None:
+        raise ValueError('Not valid checkpoint: no averaged generator (train with --ema_decay)')
+    out = dict(generator_state)
+    for kind in ('params', 'buffers'):
+        for k, v in ema[kind].items():
+            if k not in out or tuple(out[k].shape) != tuple(v.shape):
+                raise ValueError('Not valid checkpoint: averaged {} does not fit the generator'.format(k))
+            out[k] = v.to(device=out[k].device, dtype=out[k].dtype)
     return out
 
 
@@ -91,11 +111,18 @@ def save_checkpoint(path: str, model, optimizer, epoch: int, cfg: Optional[dict]
     save(make_checkpoint(model, optimizer, epoch, cfg, scheduler, logger), path)
 
 
-def resume(path: str, model, optimizer=None, scheduler=None):
+def resume(path: str, model, optimizer=None, scheduler=None, ema=None):
     """train_gan.py:258-282: load model / optimizer / scheduler state; returns (last_epoch, logger).  Raises
-    FileNotFoundError where the reference silently starts from scratch -- the caller decides."""
+    FileNotFoundError where the reference silently starts from scratch -- the caller decides.  `ema` (trainer.FusedEMA):
+    restored from 'generator_ema'; a file without the key starts the average over from the resumed parameters."""
     ck = load(path)
     model.load_state_dict(ck['model_dict'])
+    if ema is not None:
+        if ck.get('generator_ema') is not None:
+            ema.load_state_dict(ck['generator_ema'])
+        else:
+            print('No averaged generator in {}: the average starts from the resumed parameters'.format(path))
+            ema.reset()
     if optimizer is not None:
         if isinstance(optimizer, dict):
             for k, o in optimizer.items():

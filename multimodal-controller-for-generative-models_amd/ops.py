@@ -1090,6 +1090,22 @@ def adamax(p: Tensor, g: Tensor, m: Tensor, u: Tensor, step: Tensor, lr, betas=(
                                    weight_decay, _p(step), _stream()), 'adamax')
 
 
+def ema_update(ema: Tensor, p: Tensor, step: Tensor, decay: float, start: int = 0, advance: bool = True):
+    """mcgen_ema_update over two flat fp32 ranges of one length: ema = p (bit for bit) while step[0] < start, else
+    ema = decay * ema + (1 - decay) * p.  `step`: int64[2] {counter, ticket} as in ops.adam, read when the kernel runs;
+    `advance`: this launch increments the counter (the last launch of an update that takes several)."""
+    assert step.dtype == torch.int64 and step.numel() == 2
+    assert ema.numel() == p.numel()
+    check(_lib.load().mcgen_ema_update(_f32(ema), _f32(p), p.numel(), decay, int(start), _p(step), int(advance),
+                                       _stream()), 'ema_update')
+
+
+def swap_(a: Tensor, b: Tensor):
+    """mcgen_swap_f32: exchange two flat fp32 ranges of one length in place, bit for bit (no third buffer, no pointer moves)."""
+    assert a.numel() == b.numel()
+    check(_lib.load().mcgen_swap_f32(_f32(a), _f32(b), a.numel(), _stream()), 'swap_f32')
+
+
 # ---- batched small launches (one launch per network pass instead of one per layer) ----------------------
 def _struct_table(arr, device) -> Tensor:
     return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)

@@ -16,6 +16,7 @@ nn.DataParallel (train_gan.py:96-98).
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Optional, Sequence
 
 import torch
@@ -326,10 +327,128 @@ def make_fused_optimizer(name: str, flat_state: FlatState, lr, betas=(0.9, 0.999
     raise ValueError('Not valid optimizer name')
 
 
+def ema_state_dict(decay, start, step, params, buffers):
+    """The checkpoint form of an averaged network: {'decay', 'start', 'step', 'params': {name: tensor}, 'buffers':
+    {name: tensor}} -- `params` / `buffers`: (name, tensor) pairs, cloned here."""
+    return {'decay': float(decay), 'start': int(start), 'step': int(step),
+            'params': {k: v.detach().clone() for k, v in params},
+            'buffers': {k: v.detach().clone() for k, v in buffers}}
+
+
+def ema_load_into(sd, params, buffers):
+    """Copy an `ema_state_dict` into the (name, tensor) pairs `params` / `buffers`; -> (decay, start, step).  The names and
+    shapes must be the dict's own."""
+    for kind, pairs in (('params', list(params)), ('buffers', list(buffers))):
+        have = sd[kind]
+        if set(have) != {k for k, _ in pairs}:
+            raise ValueError(f'Not valid averaged state: {kind} do not match the network\'s')
+        for k, t in pairs:
+            if tuple(have[k].shape) != tuple(t.shape):
+                raise ValueError(f'Not valid averaged state: shape of {k}')
+            t.copy_(have[k])
+    return float(sd['decay']), int(sd['start']), int(sd['step'])
+
+
+def ema_buffers(module):
+    """{name: tensor} of a network's float BatchNorm running statistics, named as in module.state_dict(): what the
+    averaged network keeps its own copy of (codebooks and num_batches_tracked are not averaged)."""
+    return {k: b for k, b in module.named_buffers()
+            if b.is_floating_point() and k.rsplit('.', 1)[-1] in ('running_mean', 'running_var')}
+
+
+class FusedEMA:
+    """An exponential moving average of a network: of its parameters (one FlatState) and of its float BatchNorm running
+    statistics, which are flattened here once (the averaged network runs in eval mode on running statistics, so averaged
+    weights need averaged statistics).  update() is two launches of mcgen_ema_update -- one when there are no buffers --
+    which read the update count from device memory, so a captured update stays valid: update k (from 0) copies while
+    k < start and averages with `decay` from then on.  `names`: the parameters' names, in flat_state.tensors order;
+    `buffers`: {name: tensor}; `on_swap`: called after the averaged values went into or out of the live tensors."""
+
+    def __init__(self, flat_state: FlatState, buffers, decay: float, start: int = 0, names: Optional[Sequence[str]] = None,
+                 on_swap=None):
+        if not 0.0 <= float(decay) < 1.0 or int(start) < 0:
+            raise ValueError('Not valid averaging: decay in [0, 1) and start >= 0')
+        self.decay, self.start = float(decay), int(start)
+        self.fs = flat_state
+        flat = self.fs.ensure()
+        self.names = list(names) if names is not None else [str(i) for i in range(len(self.fs.tensors))]
+        assert len(self.names) == len(self.fs.tensors)
+        buffers = dict(buffers)
+        self.buffer_names = list(buffers)
+        self.bfs = FlatState(list(buffers.values())) if buffers else None
+        self.avg_p = flat.detach().clone()
+        self.avg_b = self.bfs.ensure().detach().clone() if self.bfs is not None else None
+        self._step_buf = torch.zeros(2, dtype=torch.int64, device=flat.device)     # {update counter, launch ticket} (ops.adam)
+        self.step_count = self._step_buf[:1]
+        self.on_swap = on_swap
+
+    def hyper(self):
+        """(decay, start): kernel arguments of the update launches -- a captured graph replays the values it was captured
+        with, so the graphed trainers treat a change like an optimizer-hyper change (FusedAdam.hyper)."""
+        return (self.decay, self.start)
+
+    def state_tensors(self):
+        """The device tensors that make up the state: what a capture warm-up snapshots and restores."""
+        return [self.avg_p] + ([self.avg_b] if self.avg_b is not None else []) + [self.step_count]
+
+    def update(self):
+        flat = self.fs.ensure()
+        if self.bfs is None:
+            ops.ema_update(self.avg_p, flat, self._step_buf, self.decay, self.start, advance=True)
+            return
+        # the count advances once per update: on the last launch
+        ops.ema_update(self.avg_p, flat, self._step_buf, self.decay, self.start, advance=False)
+        ops.ema_update(self.avg_b, self.bfs.ensure(), self._step_buf, self.decay, self.start, advance=True)
+
+    def _swap(self):
+        ops.swap_(self.avg_p, self.fs.ensure())
+        if self.bfs is not None:
+            ops.swap_(self.avg_b, self.bfs.ensure())
+        for t in self.fs.tensors + (self.bfs.tensors if self.bfs is not None else []):
+            _bump(t)
+        if self.on_swap is not None:
+            self.on_swap()
+
+    @contextlib.contextmanager
+    def swapped(self):
+        """Inside the context the live tensors hold the averaged values (and the average's buffers the live ones): an
+        in-place exchange, no pointer a captured graph holds moves.  Every swapped tensor's version is bumped both times."""
+        self._swap()
+        try:
+            yield self
+        finally:
+            self._swap()
+
+    def _named(self):
+        params = list(zip(self.names, self.fs.views(self.avg_p)))
+        buffers = list(zip(self.buffer_names, self.bfs.views(self.avg_b))) if self.bfs is not None else []
+        return params, buffers
+
+    def state_dict(self):
+        """{'decay', 'start', 'step', 'params': {name: tensor}, 'buffers': {name: tensor}} (ema_state_dict)."""
+        self.fs.ensure()
+        params, buffers = self._named()
+        return ema_state_dict(self.decay, self.start, int(self.step_count), params, buffers)
+
+    def load_state_dict(self, sd):
+        self.fs.ensure()
+        params, buffers = self._named()
+        self.decay, self.start, step = ema_load_into(sd, params, buffers)
+        self.step_count.fill_(step)
+
+    def reset(self):
+        """Start the average over from the current parameters and statistics (a resume from a file without one)."""
+        self.avg_p.copy_(self.fs.ensure())
+        if self.bfs is not None:
+            self.avg_b.copy_(self.bfs.ensure())
+        self._step_buf.zero_()
+
+
 class GANTrainer:
     def __init__(self, model, classes: int, lr=2e-4, betas=(0.5, 0.999), d_iters: int = 5, g_iters: int = 1,
                  dist_group=None, world_size: int = 1, grad_wire_dtype: Optional[torch.dtype] = None,
-                 optimizer: str = 'Adam', momentum: float = 0.0, weight_decay: float = 0.0):
+                 optimizer: str = 'Adam', momentum: float = 0.0, weight_decay: float = 0.0,
+                 ema_decay: float = 0.0, ema_start: int = 0):
         self.model = model
         self.grad_wire_dtype = grad_wire_dtype            # torch.bfloat16: gradient buckets cross the links as bf16 (dist.allreduce_mean_)
         self._ov = None                                   # overlap bookkeeping (overlap_begin / overlap_end)
@@ -350,6 +469,28 @@ class GANTrainer:
         self._cgan = bool(getattr(model, 'label_embedding', False))
         if self._cgan and world_size > 1:
             raise ValueError('CGAN training runs on one GPU: its gradients are not bucketed for a data-parallel exchange')
+        # the averaged generator (opt-in): updated right behind every generator optimizer step (g_apply).  A multi-rank run
+        # needs no exchange for it: every rank averages the same parameters.
+        self.ema = None
+        if ema_decay:
+            gen = model.generator
+            name_of = {id(p): k for k, p in gen.named_parameters()}
+            self.ema = FusedEMA(self.geng.flat_p, ema_buffers(gen), ema_decay, ema_start,
+                                names=[name_of[id(p)] for p in self.geng.flat_p.tensors],
+                                on_swap=lambda: self.geng.refresh_images(force=True))
+
+    def ema_weights(self):
+        """Context manager: inside it the generator holds its averaged parameters and running statistics (for scoring and
+        sampling in eval mode).  The weight images are rebuilt eagerly on entry AND on exit: a replayed compute graph does
+        not look at the image cache, so the live weights' images must be back before the next replay."""
+        if self.ema is None:
+            raise ValueError('Not valid averaging: the trainer was built with ema_decay = 0')
+        return self.ema.swapped()
+
+    def _hyper(self):
+        """What the captured launches bake in (see FusedAdam.hyper, FusedEMA.hyper)."""
+        key = (self.opt_g.hyper(), self.opt_d.hyper())
+        return key if self.ema is None else key + (self.ema.hyper(),)
 
     # ---- data-parallel gradient exchange: two buckets per network, started under the backward pass -------------
     # The engines' backward passes hand out each network's flat gradient in two contiguous buckets: the LATE layers
@@ -533,6 +674,8 @@ class GANTrainer:
 
     def g_apply(self):
         self.opt_g.step(self.grad_g)
+        if self.ema is not None:
+            self.ema.update()
         self.geng.refresh_images(force=True)
 
     @property
@@ -653,14 +796,18 @@ class GraphedGANTrainer(GANTrainer):
     # ---- state snapshot around the warm-up --------------------------------------------------------
     def _snapshot(self):
         sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        opt = [[t.clone() for t in o.state_tensors()] for o in (self.opt_g, self.opt_d)]
+        opt = [[t.clone() for t in o.state_tensors()] for o in self._stateful()]
         return sd, opt
+
+    def _stateful(self):
+        """The optimizers, and the averaged generator when there is one: what moves with a step besides the model."""
+        return (self.opt_g, self.opt_d) + ((self.ema,) if self.ema is not None else ())
 
     def _restore(self, snap):
         sd, opt = snap
         with torch.no_grad():
             self.model.load_state_dict(sd)
-            for o, saved in zip((self.opt_g, self.opt_d), opt):
+            for o, saved in zip(self._stateful(), opt):
                 for t, s in zip(o.state_tensors(), saved):
                     t.copy_(s)
         self.geng.flat_p.ensure()
@@ -675,6 +822,8 @@ class GraphedGANTrainer(GANTrainer):
         ts = [self.geng.flat_p.ensure()] + self.opt_g.state_tensors() + self.opt_d.state_tensors()
         ts += list(self.deng._ensure_flat())
         ts += [b for b in self.model.generator.buffers() if b.dtype != torch.int64 or b.dim() == 0]
+        if self.ema is not None:
+            ts += self.ema.state_tensors()
         seen, out = set(), []
         for t in ts:                                  # (codebooks are buffers too: constant, copied all the same; aliases once)
             if t.data_ptr() not in seen:
@@ -739,7 +888,7 @@ class GraphedGANTrainer(GANTrainer):
         with torch.cuda.graph(self.g_draw, pool=self.g_all.pool(), capture_error_mode=_CAPTURE_MODE):
             self.s_zall.normal_()
         self._graphs = True
-        self._hyper_key = (self.opt_g.hyper(), self.opt_d.hyper())
+        self._hyper_key = self._hyper()
 
     def capture(self, img: torch.Tensor, label: torch.Tensor, warmup: int = 1):
         if self._cgan:
@@ -814,7 +963,7 @@ class GraphedGANTrainer(GANTrainer):
             with torch.cuda.graph(self.g_draw, pool=self.g_all.pool(), capture_error_mode=_CAPTURE_MODE):
                 self.s_zall.normal_()
             self._graphs = True
-            self._hyper_key = (self.opt_g.hyper(), self.opt_d.hyper())
+            self._hyper_key = self._hyper()
             return
         self.g_zd, self.g_gf, self.g_z, self.g_ga = G(), G(), G(), G()
         with torch.cuda.graph(self.g_gf, capture_error_mode=_CAPTURE_MODE):
@@ -849,7 +998,7 @@ class GraphedGANTrainer(GANTrainer):
         with torch.cuda.graph(self.g_ga, pool=pool, capture_error_mode=_CAPTURE_MODE):
             self.g_apply()
         self._graphs = True
-        self._hyper_key = (self.opt_g.hyper(), self.opt_d.hyper())
+        self._hyper_key = self._hyper()
 
     def eager_iteration(self, img, label):
         return GANTrainer.train_iteration(self, img, label)
@@ -858,7 +1007,7 @@ class GraphedGANTrainer(GANTrainer):
         """Replays the captured step; `zs` (d_iters + g_iters latent batches) replaces the in-graph latent draws."""
         if self._graphs is None:
             return super().train_iteration(img, label, zs)
-        if self._hyper_key != (self.opt_g.hyper(), self.opt_d.hyper()):
+        if self._hyper_key != self._hyper():
             # betas / eps / weight decay changed since the capture (a resumed optimizer state): the apply graphs hold the
             # old values as kernel arguments -- capture again (state is snapshotted and restored around it).  The learning
             # rate is read from device memory when the kernels run: a scheduler step needs no re-capture.
