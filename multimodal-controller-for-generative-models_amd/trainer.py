@@ -1,5 +1,11 @@
-"""The MCGAN train step (counterpart of the loop body of the reference's
-``train_gan.py:139-176``) driven directly on the fused engines, plus the fused Adam.
+"""The train steps, driven directly on the fused engines, and what they step with:
+
+* the fused optimizers (Adam, SGD, RMSprop, Adamax: torch.optim semantics and state_dict format over one flat buffer)
+  and the averaged network (``FusedEMA``);
+* the GAN step of MCGAN and CGAN (``GANTrainer``; ``GraphedGANTrainer`` replays it from HIP graphs), the counterpart of
+  the loop body of the reference's ``train_gan.py:139-176``.  The body is written once (``GANTrainer._step``); the eager
+  trainer, the capture warm-up and the one-graph capture call it, the per-bucket capture cuts the same pieces apart;
+* the single-network steps (``_FlatTrainer``: Glow, PixelCNN, VAE, VQ-VAE, classifier).
 
 Per data batch: ``d_iters`` (5) discriminator updates -- D(real), G(z) in training mode,
 D(G(z).detach()), hinge loss, backward, Adam(D) -- then ``g_iters`` (1) generator updates --
@@ -69,91 +75,8 @@ class _FusedOptimizer:
         return self._lr_dev if self._lr_dev is not None else self._lr
 
 
-class FusedAdam(_FusedOptimizer):
-    """torch.optim.Adam semantics over one flat parameter buffer: one launch per step."""
-
-    def __init__(self, flat_state: FlatState, lr=2e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.0):
-        self.betas, self.eps, self.wd = betas, eps, weight_decay
-        flat = self._init_buffers(flat_state, lr)
-        self.m = torch.zeros_like(flat)
-        self.v = torch.zeros_like(flat)
-
-    def hyper(self):
-        """The hyper-parameters a launch bakes in as kernel arguments (a captured HIP graph replays the values it was
-        captured with: the graphed trainers compare this key on every iteration and re-capture when it moved).  The
-        learning rate is NOT among them: it is read from device memory at execution time."""
-        return (tuple(float(b) for b in self.betas), float(self.eps), float(self.wd))
-
-    def state_tensors(self):
-        """The device tensors that make up the optimizer's state: what a capture warm-up snapshots and restores."""
-        return [self.m, self.v, self.step_count]
-
-    def step(self, gflat: torch.Tensor):
-        flat = self.fs.ensure()
-        ops.adam(flat, gflat, self.m, self.v, self._step_buf, self._lr_arg(), self.betas, self.eps, self.wd)
-        for p in self.fs.tensors:
-            _bump(p)
-
-    def step_fused_sn_pair(self, pending):
-        """The discriminator's update straight from the raw per-half gradients of a paired pass (DiscriminatorEngine.
-        backward_iter(defer_fix=True)): spectral-norm fix + Adam in one launch per layer table (ops.sn_fix_pair_adam)."""
-        flat = self.fs.ensure()
-        tables = [t for t in pending['tables'] if t[0][1] > 0]
-        for i, ((table, nl), sg_off) in enumerate(tables):
-            ops.sn_fix_pair_adam(pending['g0'], pending['g1'], flat, self.m, self.v, pending['uv0'], pending['uv1'], table, nl,
-                                 pending['sigma0'][sg_off:], pending['sigma1'][sg_off:], self._step_buf, self._lr_arg(), self.betas,
-                                 self.eps, self.wd, i == 0)
-        for p in self.fs.tensors:
-            _bump(p)
-
-    # ---- torch.optim.Adam's state_dict format (train_gan.py:114-115,268-269: the reference checkpoints
-    # optimizer['generator'].state_dict() and loads it back with load_state_dict) --------------------------------
-    def state_dict(self):
-        """{'state': {i: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [...]} over the parameters in
-        `model.parameters()` order -- loads into a torch.optim.Adam built on the same parameters, and vice versa.
-        'state' is empty before the first step, as torch's is."""
-        self.fs.ensure()
-        state = {}
-        if int(self.step_count) > 0:
-            step = self.step_count.to(torch.float32).reshape(())
-            for i, t in enumerate(self.fs.tensors):
-                state[i] = {'step': step.clone(), 'exp_avg': self.fs.view_of(self.m, t).clone(),
-                            'exp_avg_sq': self.fs.view_of(self.v, t).clone()}
-        group = {'lr': self.lr, 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': self.wd, 'amsgrad': False,
-                 'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None,
-                 'decoupled_weight_decay': False, 'params': list(range(len(self.fs.tensors)))}
-        return {'state': state, 'param_groups': [group]}
-
-    def load_state_dict(self, sd):
-        self.fs.ensure()
-        if 'param_groups' not in sd:                     # round-1 private format {'m', 'v', 'step', ...}
-            self.m.copy_(sd['m']); self.v.copy_(sd['v']); self.step_count.copy_(sd['step'])
-            self.lr, self.betas, self.eps, self.wd = sd['lr'], tuple(sd['betas']), sd['eps'], sd['weight_decay']
-            return
-        groups = sd['param_groups']
-        if len(groups) != 1 or len(groups[0]['params']) != len(self.fs.tensors):
-            raise ValueError('Not valid optimizer state: expected one parameter group over the network\'s parameters')
-        g = groups[0]
-        if g.get('amsgrad') or g.get('maximize'):
-            raise ValueError('Not valid optimizer state: amsgrad / maximize are not supported')
-        self.lr, self.betas, self.eps, self.wd = g['lr'], tuple(g['betas']), g['eps'], g['weight_decay']
-        self.m.zero_(); self.v.zero_(); self.step_count.zero_()
-        steps = set()
-        for key, t in zip(g['params'], self.fs.tensors):
-            st = sd['state'].get(key)
-            if st is None:
-                continue
-            self.fs.view_of(self.m, t).copy_(st['exp_avg'])
-            self.fs.view_of(self.v, t).copy_(st['exp_avg_sq'])
-            steps.add(int(st['step']))
-        if len(steps) > 1:
-            raise ValueError('Not valid optimizer state: parameters disagree on the step count')
-        if steps:
-            self.step_count.fill_(steps.pop())
-
-
 class _FusedTorchState(_FusedOptimizer):
-    """state_dict() / load_state_dict() of FusedSGD, FusedRMSprop and FusedAdamax in the format of the matching
+    """state_dict() / load_state_dict() of the fused optimizers in the format of the matching
     torch.optim class (the reference checkpoints optimizer.state_dict(), train_vae.py:85): a subclass names its state
     in `_slots()`, its hyper-parameters in `_group()` and takes a loaded group in `_load_group()`."""
     _has_step = True                     # torch keeps a per-parameter 'step' (SGD does not)
@@ -219,6 +142,59 @@ class _FusedTorchState(_FusedOptimizer):
             raise ValueError('Not valid optimizer state: parameters disagree on the step count')
         if steps:
             self.step_count.fill_(steps.pop())
+
+
+class FusedAdam(_FusedTorchState):
+    """torch.optim.Adam semantics over one flat parameter buffer: one launch per step."""
+
+    def __init__(self, flat_state: FlatState, lr=2e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.0):
+        self.betas, self.eps, self.wd = betas, eps, weight_decay
+        flat = self._init_buffers(flat_state, lr)
+        self.m = torch.zeros_like(flat)
+        self.v = torch.zeros_like(flat)
+
+    def hyper(self):
+        """The hyper-parameters a launch bakes in as kernel arguments (a captured HIP graph replays the values it was
+        captured with: the graphed trainers compare this key on every iteration and re-capture when it moved).  The
+        learning rate is NOT among them: it is read from device memory at execution time."""
+        return (tuple(float(b) for b in self.betas), float(self.eps), float(self.wd))
+
+    def _slots(self):
+        return [('exp_avg', self.m), ('exp_avg_sq', self.v)]
+
+    def step(self, gflat: torch.Tensor):
+        flat = self.fs.ensure()
+        ops.adam(flat, gflat, self.m, self.v, self._step_buf, self._lr_arg(), self.betas, self.eps, self.wd)
+        self._bump_params()
+
+    def step_fused_sn_pair(self, pending):
+        """The discriminator's update straight from the raw per-half gradients of a paired pass (DiscriminatorEngine.
+        backward_iter(defer_fix=True)): spectral-norm fix + Adam in one launch per layer table (ops.sn_fix_pair_adam)."""
+        flat = self.fs.ensure()
+        tables = [t for t in pending['tables'] if t[0][1] > 0]
+        for i, ((table, nl), sg_off) in enumerate(tables):
+            ops.sn_fix_pair_adam(pending['g0'], pending['g1'], flat, self.m, self.v, pending['uv0'], pending['uv1'], table, nl,
+                                 pending['sigma0'][sg_off:], pending['sigma1'][sg_off:], self._step_buf, self._lr_arg(), self.betas,
+                                 self.eps, self.wd, i == 0)
+        self._bump_params()
+
+    # (train_gan.py:114-115,268-269: the reference checkpoints optimizer['generator'].state_dict() and loads it back)
+    def _group(self):
+        return {'lr': self.lr, 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': self.wd, 'amsgrad': False,
+                'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None,
+                'decoupled_weight_decay': False}
+
+    def _load_group(self, g):
+        if g.get('amsgrad'):
+            raise ValueError('Not valid optimizer state: amsgrad is not supported')
+        self.lr, self.betas, self.eps, self.wd = g['lr'], tuple(g['betas']), g['eps'], g['weight_decay']
+
+    def load_state_dict(self, sd):
+        if 'param_groups' in sd:
+            return super().load_state_dict(sd)
+        self.fs.ensure()                                 # round-1 private format {'m', 'v', 'step', ...}
+        self.m.copy_(sd['m']); self.v.copy_(sd['v']); self.step_count.copy_(sd['step'])
+        self.lr, self.betas, self.eps, self.wd = sd['lr'], tuple(sd['betas']), sd['eps'], sd['weight_decay']
 
 
 class FusedSGD(_FusedTorchState):
@@ -444,6 +420,37 @@ class FusedEMA:
         self._step_buf.zero_()
 
 
+def _graph(fn, pool=None):
+    """`fn()` captured into a new HIP graph (in the memory pool of an earlier one, if given)."""
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, pool=pool, capture_error_mode=_CAPTURE_MODE):
+        fn()
+    return g
+
+
+def _rehearse(model, stateful, body, times: int, settle):
+    """A capture's warm-up, rolled back: `times` runs of `body` on a side stream, then model.state_dict() and the
+    state_tensors() of the `stateful` objects go back to what they were and `settle()` re-derives what follows them.  So a
+    capture leaves the model, the optimizer state and every buffer as it found them (the capture itself records launches,
+    it does not execute them)."""
+    sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    saved = [[t.clone() for t in o.state_tensors()] for o in stateful]
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(max(1, times)):
+            body()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        model.load_state_dict(sd)
+        for o, ts in zip(stateful, saved):
+            for t, s in zip(o.state_tensors(), ts):
+                t.copy_(s)
+    settle()
+    torch.cuda.synchronize()
+
+
 class GANTrainer:
     def __init__(self, model, classes: int, lr=2e-4, betas=(0.5, 0.999), d_iters: int = 5, g_iters: int = 1,
                  dist_group=None, world_size: int = 1, grad_wire_dtype: Optional[torch.dtype] = None,
@@ -465,10 +472,11 @@ class GANTrainer:
         self.grad_d = torch.zeros_like(self.deng.flat_p.flat)
         self.group, self.world = dist_group, world_size
         self.latent = model.latent_size
-        # CGAN (models/cgan.py): labels go to the engines' embedding kernels; no codes, no paired D pass (see _cgan_iteration)
+        # CGAN (models/cgan.py): labels go to the engines' embedding kernels; no codes, no paired D pass (see _CGANPieces)
         self._cgan = bool(getattr(model, 'label_embedding', False))
         if self._cgan and world_size > 1:
             raise ValueError('CGAN training runs on one GPU: its gradients are not bucketed for a data-parallel exchange')
+        self._pieces = (_CGANPieces if self._cgan else _MCGANPieces)(self)      # the model's parts of the step (_step)
         # the averaged generator (opt-in): updated right behind every generator optimizer step (g_apply).  A multi-rank run
         # needs no exchange for it: every rank averages the same parameters.
         self.ema = None
@@ -546,12 +554,6 @@ class GANTrainer:
                 hidden += max(0.0, min(dur, before_join))
         return {'comm_us': comm, 'overlap_us': hidden, 'exposed_us': comm - hidden}
 
-    def _allreduce(self, g: torch.Tensor):
-        """Whole-buffer exchange on the compute stream (kept for callers that do not bucket)."""
-        if self.world > 1:
-            from .dist import allreduce_mean_
-            allreduce_mean_(g, self.world, self.group, self.grad_wire_dtype)
-
     # ---- the generator passes of the discriminator updates -----------------------------------------
     def fake_groups(self, n: int) -> int:
         """How many of the d_iters generator forwards of an iteration run as ONE pass.  The generator's weights do not
@@ -588,15 +590,6 @@ class GANTrainer:
             v[1:, :n].copy_(v[0, :n].unsqueeze(0).expand(groups - 1, -1, -1, -1, -1))
         return buf, [Nhwc(buf[j * 2 * n:(j + 1) * 2 * n], c) for j in range(groups)]
 
-    def pair_buffer(self, img: torch.Tensor):
-        """-> `Nhwc` [2N, H, W, 8] whose first half holds `img` (NCHW fp32), converted now (one paired batch)."""
-        return self.pair_buffers(img, 1)[1][0]
-
-    @staticmethod
-    def pair_set_fake(x2: 'Nhwc', fakes: 'Nhwc', j: int):
-        n = x2.t.shape[0] // 2
-        x2.t[n:].copy_(fakes.t[j * n:(j + 1) * n])
-
     def indicators(self, label: torch.Tensor, groups: int, out: Optional[torch.Tensor] = None, lab32: Optional[torch.Tensor] = None):
         """F.one_hot(label, classes).float() (mcgan.py:196,201) max(2, groups) times back to back, ONE launch: the
         indicator of the batch, of the paired 2N batch and of the grouped generator pass are prefixes of it.
@@ -618,7 +611,7 @@ class GANTrainer:
     def d_compute_iter(self, img, ind, fake, ind2=None, x2=None, codes=None, fuse=False):
         """`fake`: this update's generated batch (NCHW fp32, detached).  `ind2` (optional): the indicator twice,
         [2N, modes] -- constant over the D updates of an iteration, so the caller builds it once.  `x2` (optional, instead
-        of img / fake): real (+) fake as `pair_buffer` / `pair_set_fake` left them."""
+        of img / fake): one paired batch of `pair_buffers`, real (+) fake."""
         if x2 is not None and not _PAIR_D:
             n = x2.t.shape[0] // 2
             img, fake, x2 = Nhwc(x2.t[:n], x2.c), Nhwc(x2.t[n:], x2.c), None
@@ -703,117 +696,140 @@ class GANTrainer:
         (parity runs); drawn on the device when None.  Returns (D_loss, G_loss) device scalars of the
         last D and G update, as the reference logs them (train_gan.py:177)."""
         self.model.train(True)
-        if self._cgan:
-            return self._cgan_iteration(img, label, zs)
         n = img.shape[0]
         zi = iter(zs) if zs is not None else None
-        draw = (lambda: next(zi)) if zi is not None else (lambda: torch.randn(n, self.latent, device=img.device))
-        d_loss = g_loss = None
-        fg = self.fake_groups(n)
-        ind, ind2, ind_rep = self.indicators(label, fg)
-        fakes = None
-        xbuf, x2s = self.pair_buffers(img, fg) if _NHWC_PAIR else (None, None)
-        codes = self.deng.pair_codes(ind2) if (_NHWC_PAIR and _PAIR_D) else None     # the labels' codes: once for the d_iters updates
+        one = (lambda: next(zi)) if zi is not None else (lambda: torch.randn(n, self.latent, device=img.device))
+        return self._step(img, label, lambda count: torch.cat([one() for _ in range(count)]) if count > 1 else one())
+
+    def _step(self, img, label, draw, statics=None):
+        """The loop body, written once: the eager iteration, the capture warm-up and the one-graph capture are this function;
+        the per-bucket capture cuts the same pieces apart where the body reduces a bucket (GraphedGANTrainer.capture).
+        `draw(count)` -> the next `count` latent batches as one [count * N, latent] tensor; `statics`: see
+        `_MCGANPieces.stage`.  Returns (D_loss, G_loss) of the last updates."""
+        p = self._pieces
+        fg = self.fake_groups(img.shape[0])
+        inputs = p.stage(img, label, fg, statics)
         for k in range(self.d_iters):
             if k % fg == 0:
-                z_cat = torch.cat([draw() for _ in range(fg)]) if fg > 1 else draw()
-                fakes = self.g_fakes(ind_rep, z_cat, fg, nhwc=_NHWC_PAIR, pair_out=xbuf)
-            j = k % fg
-            if _NHWC_PAIR:
-                d_loss = self.d_update(None, ind, None, ind2, x2=x2s[j], codes=codes)
-            else:
-                d_loss = self.d_update(img, ind, fakes[j * n:(j + 1) * n], ind2)
-        for _ in range(self.g_iters):
-            g_loss = self.g_update(ind, draw())
-        return d_loss, g_loss
-
-
-    # ---- CGAN: the same loop body on label-embedding engines (cgan_engine.py) ---------------------------------------
-    # D(real) and D(fake) are two passes, each with its own power iteration, as in the reference (MCGAN's paired pass folds
-    # the sigma ratio into its MultimodalController codes, which CGAN does not have); the d_iters generator forwards still
-    # run as one grouped pass with per-group BatchNorm statistics.
-    def _cgan_fakes(self, label_rep, z_cat, groups: int) -> Nhwc:
-        fake, _ = self.geng.forward(z_cat, None, True, groups=groups, nhwc=True, label=label_rep)
-        return fake
-
-    def _cgan_d_compute(self, real: Nhwc, fake: Nhwc, label):
-        d_real, ctx_r = self.deng.forward(real, None, True, label=label)
-        d_fake, ctx_f = self.deng.forward(fake, None, True, label=label)
-        self.loss_d, dreal, dfake = ops.hinge_d(d_real.view(-1), d_fake.view(-1))
-        # (the fake pass first: its transposed weight images are the current ones; the sum is the same either way)
-        self.deng.backward(ctx_f, dfake, self.grad_d, False, False)
-        self.deng.backward(ctx_r, dreal, self.grad_d, True, False)
-
-    def _cgan_g_compute(self, label, z):
-        fake, gctx = self.geng.forward(z, None, True, nhwc=True, label=label)
-        d_fake, dctx = self.deng.forward(fake, None, True, tail_loss='g' if _FUSE_TAIL else None, label=label)
-        self.loss_g, dfake = ops.hinge_g(d_fake.view(-1))
-        if 'tail' in dctx:
-            dfake = dctx['tail'][0]
-        dimg = self.deng.backward(dctx, dfake, None, False, True)
-        self.geng.backward(gctx, dimg, self.grad_g, False)
-
-    def _cgan_real(self, img):
-        c = img.shape[1]
-        return Nhwc(ops.to_nhwc(img.detach().contiguous(), self.deng.dtype), c)
-
-    def _cgan_iteration(self, img, label, zs=None):
-        n = img.shape[0]
-        zi = iter(zs) if zs is not None else None
-        draw = (lambda: next(zi)) if zi is not None else (lambda: torch.randn(n, self.latent, device=img.device))
-        fg = self.fake_groups(n)
-        label_rep = label.repeat(fg) if fg > 1 else label
-        real = self._cgan_real(img)
-        fakes = None
-        for k in range(self.d_iters):
-            if k % fg == 0:
-                z_cat = torch.cat([draw() for _ in range(fg)]) if fg > 1 else draw()
-                fakes = self._cgan_fakes(label_rep, z_cat, fg)
-            j = k % fg
-            self._cgan_d_compute(real, Nhwc(fakes.t[j * n:(j + 1) * n], fakes.c), label)
+                p.fake_pass(inputs, draw(fg))
+            for lo, hi, _last in p.d_compute_iter(inputs, k % fg, self._fuse_d):
+                self._reduce_bucket(self.grad_d, lo, hi)
+            self._join_comm()
             self.d_apply()
         for _ in range(self.g_iters):
-            self._cgan_g_compute(label, draw())
+            for lo, hi, _last in p.g_compute_iter(inputs, draw(1)):
+                self._reduce_bucket(self.grad_g, lo, hi)
+            self._join_comm()
             self.g_apply()
         return self.loss_d, self.loss_g
 
 
+class _MCGANPieces:
+    """MCGAN's parts of the step (GANTrainer._step): MultimodalController indicators and codes, and D(real) with D(fake) as one
+    paired pass.  The `_NHWC_PAIR = 0` / `_PAIR_D = 0` legs live here and in GANTrainer.d_compute_iter, nowhere else."""
+    bucketed = True                      # the compute generators yield gradient buckets: a data-parallel run exchanges them
+
+    def __init__(self, trainer):
+        self.t = trainer
+
+    def statics(self, img, fg):
+        """The persistent buffers a capture stages into: the indicators (of the batch / of the paired 2N batch / of the
+        generator pass: prefixes of one buffer), their int32 labels and, on the NCHW leg, the generated batches.  (The
+        paired batches are persistent as they are: pair_buffers keeps its buffer.)"""
+        n, reps = img.shape[0], max(2, fg)
+        s = {'indall': torch.empty((reps * n, self.t.classes), dtype=torch.float32, device=img.device),
+             'lab32': torch.empty(reps * n, dtype=torch.int32, device=img.device)}
+        if not _NHWC_PAIR:
+            s['fakes'] = img.new_empty((fg * n,) + tuple(img.shape[1:]))
+        return s
+
+    def stage(self, img, label, fg, statics=None):
+        """The iteration's inputs in the engines' layouts.  `statics` (self.statics(), a capture): where to put them; None
+        allocates."""
+        t, s = self.t, statics or {}
+        ind, ind2, ind_rep = t.indicators(label, fg, out=s.get('indall'), lab32=s.get('lab32'))
+        # real (+) generated batches of the fg discriminator updates that share a generator pass
+        xbuf, x2s = t.pair_buffers(img, fg) if _NHWC_PAIR else (None, None)
+        codes = t.deng.pair_codes(ind2) if (_NHWC_PAIR and _PAIR_D) else None     # the labels' codes: once for the d_iters updates
+        return {'img': img, 'ind': ind, 'ind2': ind2, 'ind_rep': ind_rep, 'xbuf': xbuf, 'x2s': x2s, 'codes': codes,
+                'fakes': None, 'fakes_buf': s.get('fakes'), 'fg': fg}
+
+    def fake_pass(self, inputs, z_cat):
+        """The generator forwards of `fg` discriminator updates: into the paired batches' second halves, or NCHW."""
+        i = inputs
+        fakes = self.t.g_fakes(i['ind_rep'], z_cat, i['fg'], nhwc=i['xbuf'] is not None, pair_out=i['xbuf'])
+        if i['xbuf'] is None:
+            keep = i['fakes_buf']                     # (a capture: the D graphs of every pass read the persistent buffer)
+            i['fakes'] = fakes if keep is None else keep.copy_(fakes)
+
+    def d_compute_iter(self, inputs, j, fuse):
+        i = inputs
+        if i['x2s'] is not None:
+            return self.t.d_compute_iter(None, i['ind'], None, i['ind2'], x2=i['x2s'][j], codes=i['codes'], fuse=fuse)
+        n = i['img'].shape[0]
+        return self.t.d_compute_iter(i['img'], i['ind'], i['fakes'][j * n:(j + 1) * n], i['ind2'], fuse=fuse)
+
+    def g_compute_iter(self, inputs, z):
+        return self.t.g_compute_iter(inputs['ind'], z)
+
+
+class _CGANPieces:
+    """CGAN's parts of the step, on label-embedding engines (cgan_engine.py).  D(real) and D(fake) are two passes, each with
+    its own power iteration, as in the reference (MCGAN's paired pass folds the sigma ratio into its MultimodalController
+    codes, which CGAN does not have); the d_iters generator forwards still run as one grouped pass with per-group BatchNorm
+    statistics.  Gradients come whole, not in buckets: one GPU, and a capture is always one graph."""
+    bucketed = False
+
+    def __init__(self, trainer):
+        self.t = trainer
+
+    def statics(self, img, fg):
+        return None                          # (one graph: what stage() allocates under the capture stays the graph's)
+
+    def stage(self, img, label, fg, statics=None):
+        label_rep = label.repeat(fg) if fg > 1 else label
+        real = Nhwc(ops.to_nhwc(img.detach().contiguous(), self.t.deng.dtype), img.shape[1])
+        return {'label': label, 'label_rep': label_rep, 'real': real, 'fakes': None, 'fg': fg}
+
+    def fake_pass(self, inputs, z_cat):
+        inputs['fakes'], _ = self.t.geng.forward(z_cat, None, True, groups=inputs['fg'], nhwc=True, label=inputs['label_rep'])
+
+    def d_compute_iter(self, inputs, j, fuse):
+        t, label, fakes = self.t, inputs['label'], inputs['fakes']
+        n = label.shape[0]
+        d_real, ctx_r = t.deng.forward(inputs['real'], None, True, label=label)
+        d_fake, ctx_f = t.deng.forward(Nhwc(fakes.t[j * n:(j + 1) * n], fakes.c), None, True, label=label)
+        t.loss_d, dreal, dfake = ops.hinge_d(d_real.view(-1), d_fake.view(-1))
+        # (the fake pass first: its transposed weight images are the current ones; the sum is the same either way)
+        t.deng.backward(ctx_f, dfake, t.grad_d, False, False)
+        t.deng.backward(ctx_r, dreal, t.grad_d, True, False)
+        yield 0, t.grad_d.numel(), True
+
+    def g_compute_iter(self, inputs, z):
+        t, label = self.t, inputs['label']
+        fake, gctx = t.geng.forward(z, None, True, nhwc=True, label=label)
+        d_fake, dctx = t.deng.forward(fake, None, True, tail_loss='g' if _FUSE_TAIL else None, label=label)
+        t.loss_g, dfake = ops.hinge_g(d_fake.view(-1))
+        if 'tail' in dctx:
+            dfake = dctx['tail'][0]
+        dimg = t.deng.backward(dctx, dfake, None, False, True)
+        t.geng.backward(gctx, dimg, t.grad_g, False)
+        yield 0, t.grad_g.numel(), True
+
+
 class GraphedGANTrainer(GANTrainer):
-    """Same step, captured once into HIP graphs and replayed: the step is a few hundred short
-    launches, so replay removes the host launch cost.  Five graphs -- latent refresh, D compute, D apply,
-    G compute, G apply -- so that the gradient all-reduce of a multi-rank run sits BETWEEN replays, on the
-    same stream, and no collective is ever captured; the latent refresh is its own graph so that a parity run
-    can inject latents (`zs`) into the very replays the benchmark times.
+    """Same step (`_step`), captured once into HIP graphs and replayed: the step is a few hundred short
+    launches, so replay removes the host launch cost.  On one GPU the body is ONE graph; otherwise it is cut into
+    graphs per piece and gradient bucket (`_capture_buckets`), so that the gradient all-reduce of a multi-rank run
+    sits BETWEEN replays, on the same stream, and no collective is ever captured.  The latent refresh is a graph of
+    its own either way, so that a parity run can inject latents (`zs`) into the very replays the benchmark times.
 
     `capture` leaves the model, the optimizer state and every buffer exactly as it found them: its warm-up
-    updates run on a snapshot that is restored before the capture (a capture records launches, it does not
-    execute them)."""
+    iterations are rolled back before the capture (`_rehearse`)."""
 
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self._graphs = None
-
-    # ---- state snapshot around the warm-up --------------------------------------------------------
-    def _snapshot(self):
-        sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        opt = [[t.clone() for t in o.state_tensors()] for o in self._stateful()]
-        return sd, opt
-
-    def _stateful(self):
-        """The optimizers, and the averaged generator when there is one: what moves with a step besides the model."""
-        return (self.opt_g, self.opt_d) + ((self.ema,) if self.ema is not None else ())
-
-    def _restore(self, snap):
-        sd, opt = snap
-        with torch.no_grad():
-            self.model.load_state_dict(sd)
-            for o, saved in zip(self._stateful(), opt):
-                for t, s in zip(o.state_tensors(), saved):
-                    t.copy_(s)
-        self.geng.flat_p.ensure()
-        self.deng._ensure_flat()
-        self.geng.refresh_images(force=True)
-        self.geng.warm_caps()                       # (load_state_dict bumped the codebooks' versions)
 
     # ---- device-side snapshot: every tensor a train iteration writes, restored by a handful of flat copies ----------
     # (bench.py re-loads the initial training state every few iterations so that the discriminator never saturates on
@@ -843,162 +859,90 @@ class GraphedGANTrainer(GANTrainer):
             _bump(t)
         self.geng.refresh_images(force=True)          # G's weight images follow its parameters (D's are rebuilt per pass)
 
-    def _capture_cgan(self, img: torch.Tensor, label: torch.Tensor, warmup: int = 1):
-        """The CGAN loop body as ONE graph (single rank), behind the latent-draw graph, as the MCGAN one-graph form."""
-        n = img.shape[0]
-        dev = img.device
-        fg = self.fake_groups(n)
-        self._fg = fg
+    def _stateful(self):
+        """The optimizers, and the averaged generator when there is one: what moves with a step besides the model."""
+        return (self.opt_g, self.opt_d) + ((self.ema,) if self.ema is not None else ())
+
+    def _settle(self):
+        """What follows a restored state_dict: the flat buffers, G's weight images, the codebooks' caches."""
+        self.geng.flat_p.ensure()
+        self.deng._ensure_flat()
+        self.geng.refresh_images(force=True)
+        self.geng.warm_caps()                       # (load_state_dict bumped the codebooks' versions)
+
+    def _static_draw(self):
+        """-> draw(count) for `_step` over the latent buffer: consecutive slices, so the body's order is the layout."""
+        n, at = self.s_img.shape[0], [0]
+
+        def draw(count):
+            at[0] += count * n
+            return self.s_zall[at[0] - count * n:at[0]]
+        return draw
+
+    def capture(self, img: torch.Tensor, label: torch.Tensor, warmup: int = 1):
+        p, n = self._pieces, img.shape[0]
+        fg = self._fg = self.fake_groups(n)
         passes = (self.d_iters + fg - 1) // fg                  # generator passes of the D updates, fg latent batches each
-        self._cgan_zd = passes * fg
-        self.s_img = img.clone()
-        self.s_label = label.clone()
-        self.s_zall = torch.randn((passes * fg + self.g_iters) * n, self.latent, device=dev)
-        self.s_zd, self.s_z = self.s_zall[:passes * fg * n], self.s_zall[passes * fg * n:]
+        self.s_img, self.s_label = img.clone(), label.clone()
+        # the iteration's latents in the body's order: fg batches per generator pass, then one per generator update
+        self.s_zall = torch.randn((passes * fg + self.g_iters) * n, self.latent, device=img.device)
+        statics = self._statics = p.statics(self.s_img, fg)    # (kept: the graphs write them on every replay)
         self.model.train(True)
 
         def body():
-            label_rep = self.s_label.repeat(fg) if fg > 1 else self.s_label
-            real = self._cgan_real(self.s_img)
-            fakes = None
-            for k in range(self.d_iters):
-                if k % fg == 0:
-                    fakes = self._cgan_fakes(label_rep, self.s_zd[k * n:(k + fg) * n], fg)
-                j = k % fg
-                self._cgan_d_compute(real, Nhwc(fakes.t[j * n:(j + 1) * n], fakes.c), self.s_label)
-                self.d_apply()
-            for i in range(self.g_iters):
-                self._cgan_g_compute(self.s_label, self.s_z[i * n:(i + 1) * n])
-                self.g_apply()
+            self._step(self.s_img, self.s_label, self._static_draw(), statics)
 
-        snap = self._snapshot()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                body()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self._restore(snap)
-        torch.cuda.synchronize()
-        G = torch.cuda.CUDAGraph
-        self.g_draw, self.g_all = G(), G()
-        with torch.cuda.graph(self.g_all, capture_error_mode=_CAPTURE_MODE):
-            body()
-        with torch.cuda.graph(self.g_draw, pool=self.g_all.pool(), capture_error_mode=_CAPTURE_MODE):
-            self.s_zall.normal_()
-        self._graphs = True
-        self._hyper_key = self._hyper()
-
-    def capture(self, img: torch.Tensor, label: torch.Tensor, warmup: int = 1):
-        if self._cgan:
-            return self._capture_cgan(img, label, warmup)
-        n = img.shape[0]
-        dev = img.device
-        fg = self.fake_groups(n)
-        self._fg = fg
-        self.s_img = img.clone()
-        self.s_label = label.clone()
-        self.s_indall = torch.empty((max(2, fg) * n, self.classes), dtype=torch.float32, device=dev)
-        # indicator of the batch / of the paired 2N batch / of the generator pass(es): prefixes of one buffer
-        self.s_lab32 = torch.empty(max(2, fg) * n, dtype=torch.int32, device=dev)
-        self.s_ind, self.s_ind2, self.s_indg = self.indicators(self.s_label, fg, out=self.s_indall, lab32=self.s_lab32)
-        # latents of the fg discriminator updates and of the generator update: one buffer, one draw per iteration
-        self.s_zall = torch.randn((fg + 1) * n, self.latent, device=dev)
-        self.s_zd, self.s_z = self.s_zall[:fg * n], self.s_zall[fg * n:]
-        # real (+) generated batches of the fg discriminator updates that share a generator pass
-        self.s_xbuf, self.s_x2s = self.pair_buffers(self.s_img, fg) if _NHWC_PAIR else (None, None)
-        self.s_fake = None if _NHWC_PAIR else torch.empty_like(self.s_img)
-        self.model.train(True)
-        snap = self._snapshot()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                fakes = self.g_fakes(self.s_indg, self.s_zd, fg, nhwc=_NHWC_PAIR, pair_out=self.s_xbuf)
-                if _NHWC_PAIR:
-                    self.d_update(None, self.s_ind, None, self.s_ind2, x2=self.s_x2s[0],
-                                  codes=self.deng.pair_codes(self.s_ind2) if _PAIR_D else None)
-                else:
-                    self.s_fake.copy_(fakes[:n])
-                    self.d_update(self.s_img, self.s_ind, self.s_fake, self.s_ind2)
-                self.g_update(self.s_ind, self.s_z)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self._restore(snap)
-        torch.cuda.synchronize()
-        G = torch.cuda.CUDAGraph
-
-        def generator_pass():
-            """The iteration's inputs in the engines' layouts, then the fg generator forwards of the D updates."""
-            self.indicators(self.s_label, fg, out=self.s_indall, lab32=self.s_lab32)
-            if _NHWC_PAIR:
-                self.pair_buffers(self.s_img, fg)                            # the real batch -> every first half of s_xbuf
-                self.s_codes = self.deng.pair_codes(self.s_ind2) if _PAIR_D else None
-            self.s_fakes = self.g_fakes(self.s_indg, self.s_zd, fg, nhwc=_NHWC_PAIR, pair_out=self.s_xbuf)
-
-        def d_iter(j):
-            if _NHWC_PAIR:
-                return self.d_compute_iter(None, self.s_ind, None, self.s_ind2, x2=self.s_x2s[j], codes=self.s_codes, fuse=self._fuse_d)
-            return self.d_compute_iter(self.s_img, self.s_ind, self.s_fake, self.s_ind2, fuse=self._fuse_d)
-
-        self.g_all = None
-        if self.world == 1 and _ONE_GRAPH and fg == self.d_iters and self.g_iters == 1:
+        _rehearse(self.model, self._stateful(), body, warmup, self._settle)
+        if not p.bucketed or (self.world == 1 and _ONE_GRAPH and fg == self.d_iters and self.g_iters == 1):
             # Single rank: nothing sits between the replays (no collective), so the whole loop body is ONE graph -- input
             # staging, the 5 N generator pass, the d_iters discriminator updates (compute, fused fix + Adam) and the
             # generator update -- behind a small graph that redraws the latents (kept apart so that a parity run can inject
             # them).  The ~15 graph launches per iteration of the bucketed form cost ~8.5 us of idle device time each.
-            self.g_draw, self.g_all = G(), G()
-            with torch.cuda.graph(self.g_all, capture_error_mode=_CAPTURE_MODE):
-                generator_pass()
-                for k in range(self.d_iters):
-                    if not _NHWC_PAIR:
-                        self.s_fake.copy_(self.s_fakes[k * n:(k + 1) * n])
-                    for _ in d_iter(k):
-                        pass
-                    self.d_apply()
-                for _ in self.g_compute_iter(self.s_ind, self.s_z):
-                    pass
-                self.g_apply()
-            with torch.cuda.graph(self.g_draw, pool=self.g_all.pool(), capture_error_mode=_CAPTURE_MODE):
-                self.s_zall.normal_()
-            self._graphs = True
-            self._hyper_key = self._hyper()
-            return
-        self.g_zd, self.g_gf, self.g_z, self.g_ga = G(), G(), G(), G()
-        with torch.cuda.graph(self.g_gf, capture_error_mode=_CAPTURE_MODE):
-            generator_pass()
-        pool = self.g_gf.pool()
+            self.g_all = _graph(body)
+            self.g_draw = _graph(self.s_zall.normal_, self.g_all.pool())
+        else:
+            self.g_all = None
+            self._capture_buckets(statics, fg, passes)
+        self._graphs = True
+        self._hyper_key = self._hyper()
 
-        def capture_buckets(gen):
+    def _capture_buckets(self, statics, fg, passes):
+        """The body's pieces as graphs of their own, cut where `_step` reduces a bucket or draws latents: a graph per
+        generator pass (the first stages the inputs), per gradient bucket, per optimizer step and per latent draw, so that
+        the all-reduces of a multi-rank run sit BETWEEN replays and no collective is ever captured."""
+        p, draw = self._pieces, self._static_draw()
+        zd = [draw(fg) for _ in range(passes)]
+        zg = [draw(1) for _ in range(self.g_iters)]
+
+        def staged_pass():
+            # (set while capturing, kept afterwards: the later graphs read these tensors, `codes` among them, which live in
+            # the graphs' memory pool only as long as something holds them)
+            self._inputs = p.stage(self.s_img, self.s_label, fg, statics)
+            p.fake_pass(self._inputs, zd[0])
+        first = _graph(staged_pass)
+        pool = first.pool()
+
+        def bucket_graphs(gen):
             """One graph per gradient bucket: graph k holds the launches up to the point where bucket k is final (the
             generators flag their last bucket, behind which they launch nothing more)."""
-            graphs = []
-            last = False
+            graphs, last = [], False
             while not last:
-                gk = G()
+                gk = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(gk, pool=pool, capture_error_mode=_CAPTURE_MODE):
                     lo, hi, last = next(gen)
                 graphs.append((gk, (lo, hi)))
             return graphs
-        # one set of compute graphs per paired batch of the generator pass (each reads its own slot of s_xbuf)
+        self.g_gf = [first] + [_graph(lambda z=z: p.fake_pass(self._inputs, z), pool) for z in zd[1:]]
+        # one set of compute graphs per batch of a generator pass (each reads its own slot of the paired buffer)
         # (the apply graph of a set is captured right behind it: a fused single-rank update reads that set's raw gradients)
         self.g_dc, self.g_da = [], []
-        for j in range(fg if _NHWC_PAIR else 1):
-            self.g_dc.append(capture_buckets(d_iter(j)))
-            ga = G()
-            with torch.cuda.graph(ga, pool=pool, capture_error_mode=_CAPTURE_MODE):
-                self.d_apply()
-            self.g_da.append(ga)
-        with torch.cuda.graph(self.g_zd, pool=pool, capture_error_mode=_CAPTURE_MODE):
-            self.s_zd.normal_()
-        with torch.cuda.graph(self.g_z, pool=pool, capture_error_mode=_CAPTURE_MODE):
-            self.s_z.normal_()
-        self.g_gc = capture_buckets(self.g_compute_iter(self.s_ind, self.s_z))
-        with torch.cuda.graph(self.g_ga, pool=pool, capture_error_mode=_CAPTURE_MODE):
-            self.g_apply()
-        self._graphs = True
-        self._hyper_key = self._hyper()
+        for j in range(fg):
+            self.g_dc.append(bucket_graphs(p.d_compute_iter(self._inputs, j, self._fuse_d)))
+            self.g_da.append(_graph(self.d_apply, pool))
+        self.g_zd = [_graph(z.normal_, pool) for z in zd]
+        self.g_z = [_graph(z.normal_, pool) for z in zg]
+        self.g_gc = [bucket_graphs(p.g_compute_iter(self._inputs, z)) for z in zg]
+        self.g_ga = _graph(self.g_apply, pool)
 
     def eager_iteration(self, img, label):
         return GANTrainer.train_iteration(self, img, label)
@@ -1014,45 +958,32 @@ class GraphedGANTrainer(GANTrainer):
             self.capture(img, label)
         self.s_img.copy_(img, non_blocking=True)
         self.s_label.copy_(label, non_blocking=True)
-        n, fg = img.shape[0], self._fg
-        zi = iter(zs) if zs is not None else None
-        if self._cgan:
-            if zi is None:
-                self.g_draw.replay()
-            else:
-                self.s_zall.copy_(torch.cat([next(zi) for _ in range(self._cgan_zd + self.g_iters)]), non_blocking=True)
-            self.g_all.replay()
-            return self.loss_d, self.loss_g
+        if zs is not None:
+            rows = self.s_zall.shape[0] // img.shape[0]            # passes * fg + g_iters (= d_iters + g_iters for today's fg)
+            zs = list(zs)[:rows]
+            if len(zs) < rows:
+                raise ValueError(f'Not valid latents: the captured step takes {rows} latent batches, got {len(zs)}')
+            self.s_zall.copy_(torch.cat(zs), non_blocking=True)
         if self.g_all is not None:
-            if zi is None:
+            if zs is None:
                 self.g_draw.replay()
-            else:
-                self.s_zd.copy_(torch.cat([next(zi) for _ in range(fg)]) if fg > 1 else next(zi), non_blocking=True)
-                self.s_z.copy_(next(zi), non_blocking=True)
             self.g_all.replay()
             return self.loss_d, self.loss_g
+        fg = self._fg
         for k in range(self.d_iters):
             if k % fg == 0:
-                if zi is None:
-                    self.g_zd.replay()
-                else:
-                    self.s_zd.copy_(torch.cat([next(zi) for _ in range(fg)]) if fg > 1 else next(zi), non_blocking=True)
-                self.g_gf.replay()
-            j = k % fg
-            if not _NHWC_PAIR:
-                self.s_fake.copy_(self.s_fakes[j * n:(j + 1) * n], non_blocking=True)
-            js = j if _NHWC_PAIR else 0
-            for gk, (lo, hi) in self.g_dc[js]:
+                if zs is None:
+                    self.g_zd[k // fg].replay()
+                self.g_gf[k // fg].replay()
+            for gk, (lo, hi) in self.g_dc[k % fg]:
                 gk.replay()
                 self._reduce_bucket(self.grad_d, lo, hi)
             self._join_comm()
-            self.g_da[js].replay()
-        for _ in range(self.g_iters):
-            if zi is None:
-                self.g_z.replay()
-            else:
-                self.s_z.copy_(next(zi), non_blocking=True)
-            for gk, (lo, hi) in self.g_gc:
+            self.g_da[k % fg].replay()
+        for i in range(self.g_iters):
+            if zs is None:
+                self.g_z[i].replay()
+            for gk, (lo, hi) in self.g_gc[i]:
                 gk.replay()
                 self._reduce_bucket(self.grad_g, lo, hi)
             self._join_comm()
@@ -1107,34 +1038,23 @@ class _FlatTrainer:
         self.model.train(True)
         self._bind_grads()
         self.statics = statics
-        sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        opt = [t.clone() for t in self.opt.state_tensors()]
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(max(1, warmup)):
-                self._compute(*statics)
+
+        def compute():
+            self.loss = self._compute(*statics)
+
+        def body():
+            with torch.no_grad():
+                compute()
                 self._allreduce()
                 self._apply()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
+
+        _rehearse(self.model, (self.opt,), body, warmup, self._bind_grads)
         with torch.no_grad():
-            self.model.load_state_dict(sd)
-            for t, s in zip(self.opt.state_tensors(), opt):
-                t.copy_(s)
-        self.fs.ensure()
-        self._bind_grads()
-        torch.cuda.synchronize()
-        self.g_r, self.g_c, self.g_a = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.no_grad():
-            with torch.cuda.graph(self.g_c, capture_error_mode=_CAPTURE_MODE):
-                self.loss = self._compute(*statics)
+            self.g_c = _graph(compute)
             self._has_refresh = type(self)._refresh is not _FlatTrainer._refresh
             if self._has_refresh:
-                with torch.cuda.graph(self.g_r, pool=self.g_c.pool(), capture_error_mode=_CAPTURE_MODE):
-                    self._refresh()
-            with torch.cuda.graph(self.g_a, pool=self.g_c.pool(), capture_error_mode=_CAPTURE_MODE):
-                self._apply()
+                self.g_r = _graph(self._refresh, self.g_c.pool())
+            self.g_a = _graph(self._apply, self.g_c.pool())
         self._graphs = True
         self._hyper_key = self.opt.hyper()
 
