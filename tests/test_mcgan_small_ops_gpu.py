@@ -1,7 +1,9 @@
 """The MCGAN kernels of csrc/small_ops.hip one at a time: spectral-norm power iteration (four-kernel, rounds and fused
 forms), the spectral-norm gradient fix, the fused discriminator update (fix of both halves + Adam), Adam, the BatchNorm
 statistics and backward, and column sums.  Shapes are the CIFAR-10 and COIL100 discriminator / generator sizes and the
-size thresholds at which each kernel's unrolled or multi-pass loop starts.
+size thresholds at which each kernel's unrolled or multi-pass loop starts.  test_mcgan_tail_code_ops_gpu.py does the same
+for the discriminator tail, the hinge losses, tanh backward, the codes, the compaction maps and the layout kernels; the two
+files together cover every kernel of small_ops.hip except the weight-image builders, which test_weight_image_gpu.py covers.
 
 Every reference is float64 on the CPU (tests/small_ops_ref.py, itself checked against torch in
 test_small_ops_ref_cpu.py), computed from exactly the fp32 values the kernel read.  Each bound is derived from the output
