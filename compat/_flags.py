@@ -41,6 +41,20 @@ def pop_optimizer_flags(argv=None):
     return out
 
 
+LOSS_TYPES = ('Hinge', 'BCE')                             # train_gan.py:148-156,168-174
+
+
+def pop_loss_type_flags(argv=None):
+    """--loss_type {Hinge,BCE} -> {'loss_type': value} if given.  The driver sets cfg['loss_type'] = 'Hinge' after its
+    parser ran, as the reference does (train_gan.py:55): the flag is popped first and applied (cfg.update) last."""
+    v = pop_flag('--loss_type', argv)
+    if v is None:
+        return {}
+    if v not in LOSS_TYPES:
+        raise ValueError('Not valid loss type')
+    return {'loss_type': v}
+
+
 def pop_ema_flags(argv=None):
     """--ema_decay D / --ema_start K (train_gan.py) -> {'ema_decay': float, 'ema_start': int}; 0 / 0 when not given: no
     averaged generator.  K counts generator updates: the average copies the parameters until K updates are done."""

@@ -25,6 +25,8 @@ What differs, and why:
     statistics (trainer.FusedEMA, csrc/ema_ops.hip), updated behind every generator step; --ema_start K copies instead of
     averaging for the first K generator updates.  test() then runs on the averaged generator (metric names unchanged), and
     the checkpoint gains one top-level key, 'generator_ema'; `model_dict` keeps the live weights.  The reference has none.
+  * cfg['loss_type'] ('Hinge', train_gan.py:55) is a flag here, --loss_type {Hinge,BCE} (compat/_flags.py): both engines
+    take it (train_gan.py:148-156,168-174) and it lands in the checkpoint's cfg; the model tag has no loss in it.
 """
 import argparse
 import os
@@ -40,7 +42,7 @@ import torch.nn.functional as F  # noqa: E402
 
 import models  # noqa: E402  (the compat shim: mcgen_amd's module trees under the reference's names)
 import data as data_shim  # noqa: E402
-from _flags import pop_ema_flags, pop_optimizer_flags  # noqa: E402
+from _flags import pop_ema_flags, pop_loss_type_flags, pop_optimizer_flags  # noqa: E402
 from config import cfg  # noqa: E402
 from data import fetch_dataset, make_data_loader  # noqa: E402
 from logger import Logger  # noqa: E402
@@ -50,6 +52,7 @@ from utils import process_control, process_dataset, save, load  # noqa: E402
 def parse():
     optimizer_flags = pop_optimizer_flags()                  # --optimizer_name / --momentum (compat/_flags.py)
     ema_flags = pop_ema_flags()                              # --ema_decay / --ema_start: the averaged generator (off at 0)
+    loss_flags = pop_loss_type_flags()                       # --loss_type {Hinge,BCE}
     ap = argparse.ArgumentParser(description='cfg')
     for k in cfg:                                            # train_gan.py:19-24: every cfg key is a flag
         if isinstance(cfg[k], (str, int, float)) or cfg[k] is None:
@@ -72,6 +75,8 @@ def parse():
         cfg['control'] = {'controller_rate': cfg['control_name'].split('_')[0]}
     cfg['optimizer_name'] = 'Adam'                           # train_gan.py:32
     cfg.update(optimizer_flags)
+    cfg['loss_type'] = 'Hinge'                               # train_gan.py:55
+    cfg.update(loss_flags)
     return extra
 
 
@@ -107,7 +112,7 @@ def make_trainer(model, lr, betas, world=1, ema_decay=0.0, ema_start=0):
     from mcgen_amd.trainer import GraphedGANTrainer
     return GraphedGANTrainer(model, cfg['classes_size'], lr=lr, betas=betas, optimizer=cfg['optimizer_name'],
                              momentum=cfg['momentum'], weight_decay=cfg['weight_decay'], ema_decay=ema_decay, ema_start=ema_start,
-                             dist_group=(torch.distributed.group.WORLD if world > 1 else None), world_size=world)
+                             loss_type=cfg['loss_type'], dist_group=(torch.distributed.group.WORLD if world > 1 else None), world_size=world)
 
 
 def make_scheduler(optimizer):                               # train_gan.py:239-256 ('None' and the epoch-stepped ones)
@@ -146,13 +151,25 @@ def train_autograd(loader, model, optimizer, epoch):
             d_x = model.discriminate(img, label)
             generated = model.generate(label)
             d_gz = model.discriminate(generated.detach(), label)
-            d_loss = F.relu(1.0 - d_x).mean() + F.relu(1.0 + d_gz).mean()
+            if cfg['loss_type'] == 'BCE':                    # train_gan.py:148-156
+                d_loss = F.binary_cross_entropy_with_logits(d_x, torch.ones((img.size(0), 1), device=cfg['device'])) + \
+                    F.binary_cross_entropy_with_logits(d_gz, torch.zeros((img.size(0), 1), device=cfg['device']))
+            elif cfg['loss_type'] == 'Hinge':
+                d_loss = F.relu(1.0 - d_x).mean() + F.relu(1.0 + d_gz).mean()
+            else:
+                raise ValueError('Not valid loss type')
             d_loss.backward()
             optimizer['discriminator'].step()
         for _ in range(cfg['iter']['generator']):
             optimizer['discriminator'].zero_grad(); optimizer['generator'].zero_grad()
             generated = model.generate(label)
-            g_loss = -model.discriminate(generated, label).mean()
+            d_gz2 = model.discriminate(generated, label)
+            if cfg['loss_type'] == 'BCE':                    # train_gan.py:168-174
+                g_loss = F.binary_cross_entropy_with_logits(d_gz2, torch.ones((img.size(0), 1), device=cfg['device']))
+            elif cfg['loss_type'] == 'Hinge':
+                g_loss = -d_gz2.mean()
+            else:
+                raise ValueError('Not valid loss type')
             g_loss.backward()
             optimizer['generator'].step()
         last = (float(d_loss), float(g_loss))

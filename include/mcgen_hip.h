@@ -470,6 +470,28 @@ int mcgen_dtail_pair_wgrad_loss(const float* dlogit, const float* pooled, const 
 int mcgen_hinge_d(const float* real, const float* fake, int N, float* loss, float* dreal, float* dfake, void* stream);
 int mcgen_hinge_g(const float* fake, int N, float* loss, float* dfake, void* stream);
 
+/* cfg['loss_type'] of the GAN loop (train_gan.py:55,148-156,168-174).  HINGE through any entry below gives the bits of
+ * the hinge entry above it (it forwards).  BCE is binary_cross_entropy_with_logits against ones / zeros, N samples per
+ * half, softplus(a) = max(a, 0) + log1p(exp(-|a|)), sigmoid(a) = 1 / (1 + exp(-a)) (finite for every finite logit):
+ *   d: loss = mean softplus(-real) + mean softplus(fake);  dreal = -sigmoid(-real) / N;  dfake = sigmoid(fake) / N
+ *   g: loss = mean softplus(-fake);                        dfake = -sigmoid(-fake) / N
+ * An unknown loss_type, a null pointer, N <= 0 (mcgen_dtail_loss_fused: also an odd N in mode 0, C % 8 != 0, C > 2048)
+ * is refused before any launch. */
+#define MCGEN_GAN_LOSS_HINGE 0
+#define MCGEN_GAN_LOSS_BCE 1
+int mcgen_gan_loss_d(const float* real, const float* fake, int N, int loss_type,
+                     float* loss, float* dreal, float* dfake, void* stream);
+int mcgen_gan_loss_g(const float* fake, int N, int loss_type, float* loss, float* dfake, void* stream);
+/* mcgen_dtail_hinge_fused with the loss chosen: dlogit[n] is the derivative above at the sample's own logit (mode 0: a
+ * paired batch, [0, N/2) real, [N/2, N) generated, N even; mode 1: the generator update, any N), bit for bit what
+ * mcgen_gan_loss_d / mcgen_gan_loss_g write for the same logits. */
+int mcgen_dtail_loss_fused(const void* x, int dtype, const float* code, const float* w, const float* b, const float* sigma,
+                           float* pooled, float* logit, float* dlogit, void* dx, int N, int HW, int C, int mode,
+                           int loss_type, void* stream);
+/* mcgen_dtail_pair_wgrad_loss with the loss chosen: `loss` is mcgen_gan_loss_d's value on the same 2N logits, bit for bit */
+int mcgen_dtail_pair_wgrad_gan_loss(const float* dlogit, const float* pooled, const float* ratio, const float* logit, int N, int C,
+                                    float* dw1, float* db1, float* dw2, float* db2, float* loss, int loss_type, void* stream);
+
 /* dx = dy * (1 - y*y)      (nn.Tanh backward, mcgan.py:60) */
 int mcgen_tanh_bwd(const void* dy, const void* y, void* dx, int dtype, int64_t n, void* stream);
 

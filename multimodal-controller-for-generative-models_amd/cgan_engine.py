@@ -294,9 +294,9 @@ class CDiscriminatorEngine(DiscriminatorEngine):
 
     # ---- forward ---------------------------------------------------------------------------------
     def forward(self, x_nchw, indicator: Optional[Tensor], train: bool, tail_loss: Optional[str] = None,
-                label: Optional[Tensor] = None):
-        """cgan.py:164-170.  `tail_loss` 'g' (the generator update): the tail's launch also forms d(hinge_g)/d(logit) and
-        the tail's input gradient (ctx['tail']), as DiscriminatorEngine.forward."""
+                label: Optional[Tensor] = None, loss_type: str = 'Hinge'):
+        """cgan.py:164-170.  `tail_loss` 'g' (the generator update): the tail's launch also forms d(G loss)/d(logit) of
+        `loss_type` ('Hinge' | 'BCE') and the tail's input gradient (ctx['tail']), as DiscriminatorEngine.forward."""
         sigma, uv = self._power_iter(train)
         lab = _labels(indicator, label)
         dt = self.dtype
@@ -338,8 +338,9 @@ class CDiscriminatorEngine(DiscriminatorEngine):
         if tail_loss is not None and ops.dtail_hinge_ok(x):
             if tail_loss != 'g':
                 raise McgenError("CGAN discriminator: tail_loss 'g' only (there is no paired pass)")
-            logit, pooled_feat, dlogit, dxt = ops.dtail_hinge_fused(x, None, wl, tl.m.bias, sigma[tl.idx:tl.idx + 1], 'g')
+            logit, pooled_feat, dlogit, dxt = ops.dtail_loss_fused(x, None, wl, tl.m.bias, sigma[tl.idx:tl.idx + 1], 'g', loss_type)
             ctx['tail'] = (dlogit, dxt)
+            ctx['loss_type'] = loss_type
         else:
             logit, pooled_feat = ops.dtail_fwd(x, None, wl, tl.m.bias, sigma[tl.idx:tl.idx + 1])
         ctx.update(xt=x, pooled=pooled_feat)

@@ -1,6 +1,6 @@
 // Memory-bound helpers around the fused convolutions (gfx950): layout conversion, weight-image
 // construction, MultimodalController code lookup, BatchNorm statistics finalisation and backward,
-// spectral-norm power iteration, discriminator tail, hinge losses, tanh backward, Adam.
+// spectral-norm power iteration, discriminator tail, GAN losses (hinge, BCE), tanh backward, Adam.
 #include "mcgen_common.h"
 #include <string.h>
 
@@ -989,7 +989,14 @@ void dtail_fwd_vec_kernel(const T* __restrict__ x, const float* __restrict__ cod
 // samples [0, N/2) real, [N/2, N) generated): -1/(N/2) where 1 - logit > 0, +1/(N/2) where 1 + logit > 0; hinge_g
 // (train_gan.py:172): -1/N -- so the input gradient of the tail (mcgan.py:158-165: ReLU -> MC -> sum pool -> SN linear)
 // follows in the same workgroup.  The loss VALUE needs every sample: mcgen_dtail_pair_wgrad_loss / mcgen_hinge_g add it.
-template <typename T>
+// LOSS = MCGEN_GAN_LOSS_BCE (train_gan.py:149-152,169-170, binary_cross_entropy_with_logits against ones / zeros): the
+// same places hold -sigmoid(-logit) / count (real, and the generator update) and +sigmoid(logit) / count (generated);
+// gan_dl_* are shared with bce_d_kernel / bce_g_kernel, so the fused and the stand-alone derivative agree bit for bit.
+__device__ __forceinline__ float gan_sigmoid(float a) { return 1.f / (1.f + expf(-a)); }          // expf -> inf gives 0
+__device__ __forceinline__ float gan_softplus(float a) { return fmaxf(a, 0.f) + log1pf(expf(-fabsf(a))); }
+__device__ __forceinline__ float gan_dl_ones(float lg, float inv) { return -gan_sigmoid(-lg) * inv; }   // target 1
+__device__ __forceinline__ float gan_dl_zeros(float lg, float inv) { return gan_sigmoid(lg) * inv; }    // target 0
+template <typename T, int LOSS = MCGEN_GAN_LOSS_HINGE>
 __global__ __launch_bounds__(256)
 void dtail_fused_kernel(const T* __restrict__ x, const float* __restrict__ code, const float* __restrict__ w,
                         const float* __restrict__ b, const float* __restrict__ sigma, float* pooled, float* logit,
@@ -1027,7 +1034,11 @@ void dtail_fused_kernel(const T* __restrict__ x, const float* __restrict__ code,
         const float lg = part + b[0];
         logit[n] = lg;
         float dl;
-        if (mode == 0) {
+        if (LOSS == MCGEN_GAN_LOSS_BCE) {
+            const int h = N / 2;
+            if (mode == 0) dl = (n < h) ? gan_dl_ones(lg, 1.f / (float)h) : gan_dl_zeros(lg, 1.f / (float)h);
+            else dl = gan_dl_ones(lg, 1.f / (float)N);
+        } else if (mode == 0) {
             const int h = N / 2;
             dl = (n < h) ? ((1.f - lg) > 0.f ? -1.f / (float)h : 0.f) : ((1.f + lg) > 0.f ? 1.f / (float)h : 0.f);
         } else dl = -1.f / (float)N;
@@ -1114,6 +1125,33 @@ __global__ void hinge_g_kernel(const float* fake, int N, float* loss, float* dfa
     for (int i = threadIdx.x; i < N; i += blockDim.x) { a += fake[i]; dfake[i] = -inv; }
     a = block_sum(a, red);
     if (threadIdx.x == 0) loss[0] = -a * inv;
+}
+// The non-saturating GAN loss (train_gan.py:149-152,169-170: binary_cross_entropy_with_logits against ones / zeros).
+// d: loss = mean softplus(-real) + mean softplus(fake); g: loss = mean softplus(-fake).  One block, as the hinge pair.
+__global__ void bce_d_kernel(const float* real, const float* fake, int N, float* loss, float* dreal, float* dfake) {
+    __shared__ float red[32];
+    float a = 0.f, b = 0.f;
+    const float inv = 1.f / (float)N;
+    for (int i = threadIdx.x; i < N; i += blockDim.x) {
+        const float r = real[i], f = fake[i];
+        a += gan_softplus(-r); b += gan_softplus(f);
+        dreal[i] = gan_dl_ones(r, inv);
+        dfake[i] = gan_dl_zeros(f, inv);
+    }
+    a = block_sum(a, red); b = block_sum(b, red);
+    if (threadIdx.x == 0) loss[0] = a * inv + b * inv;
+}
+__global__ void bce_g_kernel(const float* fake, int N, float* loss, float* dfake) {
+    __shared__ float red[32];
+    float a = 0.f;
+    const float inv = 1.f / (float)N;
+    for (int i = threadIdx.x; i < N; i += blockDim.x) {
+        const float f = fake[i];
+        a += gan_softplus(-f);
+        dfake[i] = gan_dl_ones(f, inv);
+    }
+    a = block_sum(a, red);
+    if (threadIdx.x == 0) loss[0] = a * inv;
 }
 template <typename T>
 __global__ void tanh_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ y, T* __restrict__ dx, size_t n) {
@@ -1682,6 +1720,7 @@ extern "C" int mcgen_dtail_bwd(const float* dlogit, const void* x, int dtype, co
 
 // Paired discriminator pass: tail weight / bias gradients of the two halves of a 2N batch in one launch (blockIdx.y =
 // half); the second half's pooled features carry sigma_1 / sigma_2, which `ratio` divides out of its weight gradient.
+template <int LOSS>
 __global__ __launch_bounds__(256)
 void dtail_pair_w_kernel(const float* __restrict__ dlogit, const float* __restrict__ pooled, const float* __restrict__ ratio,
                          float* dw1, float* db1, float* dw2, float* db2, int N, int C,
@@ -1689,11 +1728,15 @@ void dtail_pair_w_kernel(const float* __restrict__ dlogit, const float* __restri
     __shared__ float sh[4][64];
     if (loss && blockIdx.x == gridDim.x - 1) {
         // the extra block of a launch that also owes the hinge loss (train_gan.py:154): hinge_d_kernel's sums, same order
+        // (LOSS = MCGEN_GAN_LOSS_BCE, train_gan.py:149-152: bce_d_kernel's)
         if (blockIdx.y == 0) {
             float* red = &sh[0][0];
             const float* real = logit; const float* fake = logit + N;
             float a = 0.f, f = 0.f;
-            for (int i = threadIdx.x; i < N; i += blockDim.x) { a += fmaxf(1.f - real[i], 0.f); f += fmaxf(1.f + fake[i], 0.f); }
+            for (int i = threadIdx.x; i < N; i += blockDim.x) {
+                if (LOSS == MCGEN_GAN_LOSS_BCE) { a += gan_softplus(-real[i]); f += gan_softplus(fake[i]); }
+                else { a += fmaxf(1.f - real[i], 0.f); f += fmaxf(1.f + fake[i], 0.f); }
+            }
             a = block_sum(a, red); f = block_sum(f, red + 32);
             const float inv = 1.f / (float)N;
             if (threadIdx.x == 0) loss[0] = a * inv + f * inv;
@@ -1729,14 +1772,14 @@ void dtail_pair_w_kernel(const float* __restrict__ dlogit, const float* __restri
 extern "C" int mcgen_dtail_pair_wgrad(const float* dlogit, const float* pooled, const float* ratio, int N, int C,
                                       float* dw1, float* db1, float* dw2, float* db2, void* stream) {
     MCGEN_CHECK(dlogit && pooled && ratio && dw1 && db1 && dw2 && db2 && N > 0 && C > 0, "dtail_pair_wgrad: bad arguments");
-    hipLaunchKernelGGL(dtail_pair_w_kernel, dim3((C + 63) / 64, 2), dim3(256), 0, STREAM(stream), dlogit, pooled, ratio, dw1, db1, dw2, db2, N, C);
+    hipLaunchKernelGGL(dtail_pair_w_kernel<MCGEN_GAN_LOSS_HINGE>, dim3((C + 63) / 64, 2), dim3(256), 0, STREAM(stream), dlogit, pooled, ratio, dw1, db1, dw2, db2, N, C);
     MCGEN_LAUNCH_CHECK("dtail_pair_wgrad"); return 0;
 }
 
 extern "C" int mcgen_dtail_pair_wgrad_loss(const float* dlogit, const float* pooled, const float* ratio, const float* logit, int N, int C,
                                            float* dw1, float* db1, float* dw2, float* db2, float* loss, void* stream) {
     MCGEN_CHECK(dlogit && pooled && ratio && logit && dw1 && db1 && dw2 && db2 && loss && N > 0 && C > 0, "dtail_pair_wgrad_loss: bad arguments");
-    hipLaunchKernelGGL(dtail_pair_w_kernel, dim3((C + 63) / 64 + 1, 2), dim3(256), 0, STREAM(stream), dlogit, pooled, ratio, dw1, db1, dw2, db2, N, C, logit, loss);
+    hipLaunchKernelGGL(dtail_pair_w_kernel<MCGEN_GAN_LOSS_HINGE>, dim3((C + 63) / 64 + 1, 2), dim3(256), 0, STREAM(stream), dlogit, pooled, ratio, dw1, db1, dw2, db2, N, C, logit, loss);
     MCGEN_LAUNCH_CHECK("dtail_pair_wgrad_loss"); return 0;
 }
 extern "C" int mcgen_dtail_hinge_fused(const void* x, int dtype, const float* code, const float* w, const float* b, const float* sigma,
@@ -1760,6 +1803,53 @@ extern "C" int mcgen_hinge_g(const float* fake, int N, float* loss, float* dfake
     MCGEN_CHECK(fake && loss && dfake && N > 0, "hinge_g: bad arguments");
     hipLaunchKernelGGL(hinge_g_kernel, dim3(1), dim3(256), 0, STREAM(stream), fake, N, loss, dfake);
     MCGEN_LAUNCH_CHECK("hinge_g"); return 0;
+}
+
+// ---- loss-typed entries (cfg['loss_type'] of train_gan.py:55,148-156,168-174): HINGE forwards to the entries above ----
+#define GAN_LOSS_KNOWN(lt) ((lt) == MCGEN_GAN_LOSS_HINGE || (lt) == MCGEN_GAN_LOSS_BCE)
+extern "C" int mcgen_gan_loss_d(const float* real, const float* fake, int N, int loss_type,
+                                float* loss, float* dreal, float* dfake, void* stream) {
+    MCGEN_CHECK(GAN_LOSS_KNOWN(loss_type), "gan_loss_d: unknown loss_type %d (MCGEN_GAN_LOSS_HINGE or MCGEN_GAN_LOSS_BCE)", loss_type);
+    MCGEN_CHECK(real && fake && loss && dreal && dfake, "gan_loss_d: null pointer");
+    MCGEN_CHECK(N > 0, "gan_loss_d: N must be positive");
+    if (loss_type == MCGEN_GAN_LOSS_HINGE) return mcgen_hinge_d(real, fake, N, loss, dreal, dfake, stream);
+    hipLaunchKernelGGL(bce_d_kernel, dim3(1), dim3(256), 0, STREAM(stream), real, fake, N, loss, dreal, dfake);
+    MCGEN_LAUNCH_CHECK("gan_loss_d"); return 0;
+}
+extern "C" int mcgen_gan_loss_g(const float* fake, int N, int loss_type, float* loss, float* dfake, void* stream) {
+    MCGEN_CHECK(GAN_LOSS_KNOWN(loss_type), "gan_loss_g: unknown loss_type %d (MCGEN_GAN_LOSS_HINGE or MCGEN_GAN_LOSS_BCE)", loss_type);
+    MCGEN_CHECK(fake && loss && dfake, "gan_loss_g: null pointer");
+    MCGEN_CHECK(N > 0, "gan_loss_g: N must be positive");
+    if (loss_type == MCGEN_GAN_LOSS_HINGE) return mcgen_hinge_g(fake, N, loss, dfake, stream);
+    hipLaunchKernelGGL(bce_g_kernel, dim3(1), dim3(256), 0, STREAM(stream), fake, N, loss, dfake);
+    MCGEN_LAUNCH_CHECK("gan_loss_g"); return 0;
+}
+extern "C" int mcgen_dtail_loss_fused(const void* x, int dtype, const float* code, const float* w, const float* b, const float* sigma,
+                                      float* pooled, float* logit, float* dlogit, void* dx, int N, int HW, int C, int mode,
+                                      int loss_type, void* stream) {
+    MCGEN_CHECK(GAN_LOSS_KNOWN(loss_type), "dtail_loss_fused: unknown loss_type %d (MCGEN_GAN_LOSS_HINGE or MCGEN_GAN_LOSS_BCE)", loss_type);
+    MCGEN_CHECK(x && w && b && sigma && pooled && logit && dlogit && dx, "dtail_loss_fused: null pointer");
+    MCGEN_CHECK(N > 0 && HW > 0, "dtail_loss_fused: N and HW must be positive");
+    MCGEN_CHECK(C > 0 && C % 8 == 0 && C / 8 <= 256, "dtail_loss_fused: C must be a multiple of 8, at most 2048");
+    MCGEN_CHECK(mode == 1 || (mode == 0 && N % 2 == 0), "dtail_loss_fused: mode 0 (the discriminator loss over a paired batch, N even) or 1 (the generator loss)");
+    if (loss_type == MCGEN_GAN_LOSS_HINGE)
+        return mcgen_dtail_hinge_fused(x, dtype, code, w, b, sigma, pooled, logit, dlogit, dx, N, HW, C, mode, stream);
+    const int pl = 256 / (C / 8);
+    const size_t lds = (size_t)pl * C * sizeof(float);
+    DISPATCH_T(dtype,
+        hipLaunchKernelGGL((dtail_fused_kernel<float, MCGEN_GAN_LOSS_BCE>), dim3(N), dim3(256), lds, STREAM(stream), (const float*)x, code, w, b, sigma, pooled, logit, dlogit, (float*)dx, N, HW, C, mode),
+        hipLaunchKernelGGL((dtail_fused_kernel<bf16_t, MCGEN_GAN_LOSS_BCE>), dim3(N), dim3(256), lds, STREAM(stream), (const bf16_t*)x, code, w, b, sigma, pooled, logit, dlogit, (bf16_t*)dx, N, HW, C, mode));
+    MCGEN_LAUNCH_CHECK("dtail_loss_fused"); return 0;
+}
+extern "C" int mcgen_dtail_pair_wgrad_gan_loss(const float* dlogit, const float* pooled, const float* ratio, const float* logit, int N, int C,
+                                               float* dw1, float* db1, float* dw2, float* db2, float* loss, int loss_type, void* stream) {
+    MCGEN_CHECK(GAN_LOSS_KNOWN(loss_type), "dtail_pair_wgrad_gan_loss: unknown loss_type %d (MCGEN_GAN_LOSS_HINGE or MCGEN_GAN_LOSS_BCE)", loss_type);
+    MCGEN_CHECK(dlogit && pooled && ratio && logit && dw1 && db1 && dw2 && db2 && loss, "dtail_pair_wgrad_gan_loss: null pointer");
+    MCGEN_CHECK(N > 0 && C > 0, "dtail_pair_wgrad_gan_loss: N and C must be positive");
+    if (loss_type == MCGEN_GAN_LOSS_HINGE)
+        return mcgen_dtail_pair_wgrad_loss(dlogit, pooled, ratio, logit, N, C, dw1, db1, dw2, db2, loss, stream);
+    hipLaunchKernelGGL(dtail_pair_w_kernel<MCGEN_GAN_LOSS_BCE>, dim3((C + 63) / 64 + 1, 2), dim3(256), 0, STREAM(stream), dlogit, pooled, ratio, dw1, db1, dw2, db2, N, C, logit, loss);
+    MCGEN_LAUNCH_CHECK("dtail_pair_wgrad_gan_loss"); return 0;
 }
 extern "C" int mcgen_tanh_bwd(const void* dy, const void* y, void* dx, int dtype, int64_t n, void* stream) {
     MCGEN_CHECK(dy && y && dx && n > 0, "tanh_bwd: bad arguments");

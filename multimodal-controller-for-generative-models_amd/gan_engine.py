@@ -777,10 +777,11 @@ class DiscriminatorEngine:
     def _power_iter(self, train: bool):
         return self._power_iters(1, train)[0]
 
-    def forward(self, x_nchw: Tensor, indicator: Tensor, train: bool, tail_loss: Optional[str] = None):
-        """`tail_loss` 'g' (the generator update, train_gan.py:172): the tail's launch also forms d(hinge_g)/d(logit) and the
-        tail's input gradient (ops.dtail_hinge_fused); ctx['tail'] = (dlogit, d tail input) is what `backward_iter` then
-        starts from -- pass ctx['tail'][0] as its dlogit."""
+    def forward(self, x_nchw: Tensor, indicator: Tensor, train: bool, tail_loss: Optional[str] = None,
+                loss_type: str = 'Hinge'):
+        """`tail_loss` 'g' (the generator update, train_gan.py:168-172): the tail's launch also forms d(G loss)/d(logit) of
+        `loss_type` ('Hinge' | 'BCE') and the tail's input gradient (ops.dtail_loss_fused); ctx['tail'] = (dlogit, d tail
+        input) is what `backward_iter` then starts from -- pass ctx['tail'][0] as its dlogit."""
         sigma, uv = self._power_iter(train)
         ctx = {'n': x_nchw.shape[0], 'sigma': sigma, 'uv': uv, 'blocks': [], 'pair': None, 'train': train}
         lab = self._codes.labels_of(indicator) if _PREP_CODES else None
@@ -789,7 +790,8 @@ class DiscriminatorEngine:
             ctx['codes_job'] = (self._codes, lab[0], lab[1], None, 0, lambda outs: ctx.__setitem__('codes', outs))
         else:
             ctx['codes'] = self._codes.run_any(indicator)
-        return self._forward_body(x_nchw, ctx, lambda mc_i, sn_idx: ctx['codes'][mc_i] if mc_i is not None else None, tail_loss)
+        return self._forward_body(x_nchw, ctx, lambda mc_i, sn_idx: ctx['codes'][mc_i] if mc_i is not None else None, tail_loss,
+                                  loss_type)
 
     def pair_codes(self, ind2: Tensor):
         """The UNSCALED MultimodalController codes of a paired pass ([2N, C] per MC: what the weight gradients multiply their
@@ -797,7 +799,7 @@ class DiscriminatorEngine:
         return self._codes.run_any(ind2)
 
     def forward_pair(self, real_nchw: Tensor, fake_nchw: Tensor, indicator: Tensor, ind2: Optional[Tensor] = None,
-                     x2: Optional[Nhwc] = None, codes=None, tail_loss: Optional[str] = None):
+                     x2: Optional[Nhwc] = None, codes=None, tail_loss: Optional[str] = None, loss_type: str = 'Hinge'):
         """D(real) and D(fake) of one discriminator update (train_gan.py:144-150) as ONE pass over the 2N batch.
         The two forwards of the reference differ only in the spectral-norm state (each runs its own power iteration,
         which depends on the weights alone): conv(x; W / sigma_2) = (sigma_1 / sigma_2) * conv(x; W / sigma_1), so the
@@ -805,8 +807,9 @@ class DiscriminatorEngine:
         MultimodalController codes (the prologue multiply sits after the ReLU, i.e. directly on the conv input).
         `x2` (optional, then real / fake are ignored): the 2N batch real (+) fake already in the engine's layout.
         `codes` (optional): `pair_codes(ind2)`, computed once for several updates on the same labels.
-        `tail_loss` 'd_pair': the tail's launch also forms d(hinge_d)/d(logit) of the 2N batch and the tail's input gradient
-        (ctx['tail']); `backward_iter` writes the loss value into ctx['loss'] (train_gan.py:154)."""
+        `tail_loss` 'd_pair': the tail's launch also forms d(D loss)/d(logit) of the 2N batch for `loss_type` ('Hinge' |
+        'BCE') and the tail's input gradient (ctx['tail']); `backward_iter` writes that loss's value into ctx['loss']
+        (train_gan.py:148-154)."""
         n = x2.shape[0] // 2 if x2 is not None else real_nchw.shape[0]
         (sigma1, uv1), (sigma2, uv2) = self._power_iters(2, True)
         ratio = self._sn_ratio if self._sn_ratio is not None else sigma1 / sigma2
@@ -831,9 +834,9 @@ class DiscriminatorEngine:
             ctx['codes_job'] = (self._codes_pair, lab[0], lab[1], ratio, n, lambda outs: scaled.update(zip(uses, outs)))
         else:
             scaled.update(zip(uses, self._codes_pair.run_any(ind2, ratio, n)))     # all scaled codes of the pass: one launch
-        return self._forward_body(x, ctx, lambda mc_i, sn_idx: scaled[(mc_i, sn_idx)], tail_loss)
+        return self._forward_body(x, ctx, lambda mc_i, sn_idx: scaled[(mc_i, sn_idx)], tail_loss, loss_type)
 
-    def _forward_body(self, x_nchw: Tensor, ctx, code_of, tail_loss: Optional[str] = None):
+    def _forward_body(self, x_nchw: Tensor, ctx, code_of, tail_loss: Optional[str] = None, loss_type: str = 'Hinge'):
         dt = self.dtype
         n = x_nchw.shape[0]
         sigma = ctx['sigma']
@@ -891,9 +894,10 @@ class DiscriminatorEngine:
         if tail_loss is not None and ops.dtail_hinge_ok(x):
             if (tail_loss == 'd_pair') != (ctx['pair'] is not None):
                 raise McgenError("tail_loss: 'd_pair' goes with forward_pair, 'g' with forward")
-            logit, pooled_feat, dlogit, dxt = ops.dtail_hinge_fused(x, codet, tl.m.weight_orig.detach().view(-1), tl.m.bias,
-                                                                    sigma[tl.idx:tl.idx + 1], tail_loss)
+            logit, pooled_feat, dlogit, dxt = ops.dtail_loss_fused(x, codet, tl.m.weight_orig.detach().view(-1), tl.m.bias,
+                                                                   sigma[tl.idx:tl.idx + 1], tail_loss, loss_type)
             ctx['tail'] = (dlogit, dxt)
+            ctx['loss_type'] = loss_type             # (backward_iter's tail-gradient launch writes the matching loss value)
             if tail_loss == 'd_pair':
                 ctx['loss'] = torch.empty(1, dtype=torch.float32, device=x.device)
                 ctx['logit'] = logit
@@ -1029,7 +1033,8 @@ class DiscriminatorEngine:
             ops.dtail_pair_wgrad(dlogit, ctx['pooled'], pair['ratio'][tl.idx:tl.idx + 1],
                                  self.flat_p.view_of(g_a, wl).view(-1), self.flat_p.view_of(g_a, bl).view(-1),
                                  self.flat_p.view_of(g_b, wl).view(-1), self.flat_p.view_of(g_b, bl).view(-1),
-                                 logit=ctx['logit'] if with_loss else None, loss=ctx['loss'] if with_loss else None)
+                                 logit=ctx['logit'] if with_loss else None, loss=ctx['loss'] if with_loss else None,
+                                 loss_type=ctx.get('loss_type', 'Hinge'))
             return dy
 
         def block_bwd(b, bc, dy):

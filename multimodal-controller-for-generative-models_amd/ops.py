@@ -930,18 +930,40 @@ def dtail_hinge_fused(x: Tensor, code: Optional[Tensor], w: Tensor, b: Tensor, s
     return both[0], pooled, both[1], dx
 
 
+def gan_loss_id(loss_type: str) -> int:
+    """cfg['loss_type'] (train_gan.py:55) -> MCGEN_GAN_LOSS_*; anything else is the reference's error (train_gan.py:156)."""
+    if loss_type not in ('Hinge', 'BCE'):
+        raise ValueError('Not valid loss type')
+    return _lib.CONSTANTS['MCGEN_GAN_LOSS_HINGE' if loss_type == 'Hinge' else 'MCGEN_GAN_LOSS_BCE']
+
+
+def dtail_loss_fused(x: Tensor, code: Optional[Tensor], w: Tensor, b: Tensor, sigma: Tensor, mode: str, loss_type: str):
+    """`dtail_hinge_fused` with the loss chosen (mcgen_dtail_loss_fused): 'Hinge' gives its bits, 'BCE' forms
+    d(binary_cross_entropy_with_logits)/d(logit) of train_gan.py:149-152 ('d_pair') / 169-170 ('g') from the sample's logit.
+    -> (logit [N], pooled [N, C], dlogit [N], dx like x)"""
+    n, c = x.shape[0], x.shape[-1]
+    hw = x.numel() // (n * c)
+    pooled = torch.empty((n, c), dtype=torch.float32, device=x.device)
+    both = torch.empty((2, n), dtype=torch.float32, device=x.device)
+    dx = torch.empty_like(x)
+    check(_lib.load().mcgen_dtail_loss_fused(_p(x), _dt(x.dtype), _f32(code), _f32(w), _f32(b), _f32(sigma), _f32(pooled),
+                                             both[0].data_ptr(), both[1].data_ptr(), _p(dx), n, hw, c,
+                                             {'d_pair': 0, 'g': 1}[mode], gan_loss_id(loss_type), _stream()), 'dtail_loss_fused')
+    return both[0], pooled, both[1], dx
+
+
 def dtail_pair_wgrad(dlogit: Tensor, pooled: Tensor, ratio: Tensor, dw1: Tensor, db1: Tensor, dw2: Tensor, db2: Tensor,
-                     logit: Optional[Tensor] = None, loss: Optional[Tensor] = None):
+                     logit: Optional[Tensor] = None, loss: Optional[Tensor] = None, loss_type: str = 'Hinge'):
     """Tail weight / bias gradients of the two halves of a paired discriminator pass (dw2 divided by ratio[0]); with
-    `logit` [2N] and `loss` [1] the launch also writes the discriminator's hinge loss (train_gan.py:154)."""
+    `logit` [2N] and `loss` [1] the launch also writes the discriminator's loss of `loss_type` (train_gan.py:148-154)."""
     n2, c = pooled.shape
     for t in (dw1, db1, dw2, db2):
         if not t.is_contiguous() or t.dtype != torch.float32:
             raise _lib.McgenError('dtail_pair_wgrad: outputs must be contiguous fp32')
     if loss is not None:
-        check(_lib.load().mcgen_dtail_pair_wgrad_loss(_f32(dlogit), _f32(pooled), _f32(ratio), _f32(logit.contiguous()), n2 // 2, c,
-                                                      _f32(dw1), _f32(db1), _f32(dw2), _f32(db2), _f32(loss), _stream()),
-              'dtail_pair_wgrad_loss')
+        check(_lib.load().mcgen_dtail_pair_wgrad_gan_loss(_f32(dlogit), _f32(pooled), _f32(ratio), _f32(logit.contiguous()), n2 // 2, c,
+                                                          _f32(dw1), _f32(db1), _f32(dw2), _f32(db2), _f32(loss),
+                                                          gan_loss_id(loss_type), _stream()), 'dtail_pair_wgrad_gan_loss')
         return
     check(_lib.load().mcgen_dtail_pair_wgrad(_f32(dlogit), _f32(pooled), _f32(ratio), n2 // 2, c,
                                              _f32(dw1), _f32(db1), _f32(dw2), _f32(db2), _stream()), 'dtail_pair_wgrad')
@@ -963,6 +985,27 @@ def hinge_g(fake: Tensor):
     n = fake.numel()
     out = torch.empty(1 + n, dtype=torch.float32, device=fake.device)
     check(_lib.load().mcgen_hinge_g(_f32(fake), n, out.data_ptr(), out[1:].data_ptr(), _stream()), 'hinge_g')
+    return out[0], out[1:]
+
+
+def gan_loss_d(real: Tensor, fake: Tensor, loss_type: str, both: bool = False):
+    """`hinge_d` with the loss chosen ('Hinge' | 'BCE', train_gan.py:148-154): (loss, d loss / d real, d loss / d fake),
+    `both`: also the two gradients as one contiguous [2N] tensor."""
+    n = real.numel()
+    out = torch.empty(1 + 2 * n, dtype=torch.float32, device=real.device)
+    check(_lib.load().mcgen_gan_loss_d(_f32(real), _f32(fake), n, gan_loss_id(loss_type), out.data_ptr(),
+                                       out[1:1 + n].data_ptr(), out[1 + n:].data_ptr(), _stream()), 'gan_loss_d')
+    if both:
+        return out[0], out[1:1 + n], out[1 + n:], out[1:]
+    return out[0], out[1:1 + n], out[1 + n:]
+
+
+def gan_loss_g(fake: Tensor, loss_type: str):
+    """`hinge_g` with the loss chosen (train_gan.py:168-172): (loss, d loss / d fake)."""
+    n = fake.numel()
+    out = torch.empty(1 + n, dtype=torch.float32, device=fake.device)
+    check(_lib.load().mcgen_gan_loss_g(_f32(fake), n, gan_loss_id(loss_type), out.data_ptr(), out[1:].data_ptr(), _stream()),
+          'gan_loss_g')
     return out[0], out[1:]
 
 

@@ -40,7 +40,7 @@ _NHWC_PAIR = _flag('MCGEN_NHWC_PAIR', '1') != '0'    # engine-to-engine images s
 _PAIR_D = _flag('MCGEN_PAIR_D', '1') != '0'      # real + fake discriminator passes batched (see d_compute)
 _GROUP_G = _flag('MCGEN_GROUP_G', '1') != '0'    # the d_iters generator forwards of an iteration as one pass (fake_groups)
 _FUSE_D_ADAM = _flag('MCGEN_FUSE_D_ADAM', '1') != '0'     # single rank: spectral-norm gradient fix + Adam of a paired D update in one launch
-_FUSE_TAIL = _flag('MCGEN_FUSE_TAIL', '1') != '0'        # D tail forward + hinge derivative + tail input gradient in one launch
+_FUSE_TAIL = _flag('MCGEN_FUSE_TAIL', '1') != '0'        # D tail forward + loss derivative + tail input gradient in one launch
 _ONE_GRAPH = _flag('MCGEN_ONE_GRAPH', '1') != '0'        # single rank: the whole loop body as one HIP graph (0: one graph per phase, as a multi-rank run)
 
 
@@ -455,8 +455,11 @@ class GANTrainer:
     def __init__(self, model, classes: int, lr=2e-4, betas=(0.5, 0.999), d_iters: int = 5, g_iters: int = 1,
                  dist_group=None, world_size: int = 1, grad_wire_dtype: Optional[torch.dtype] = None,
                  optimizer: str = 'Adam', momentum: float = 0.0, weight_decay: float = 0.0,
-                 ema_decay: float = 0.0, ema_start: int = 0):
+                 ema_decay: float = 0.0, ema_start: int = 0, loss_type: str = 'Hinge'):
         self.model = model
+        # cfg['loss_type'] of train_gan.py:55,148-156,168-174; fixed here: a captured graph bakes its launches in
+        ops.gan_loss_id(loss_type)                        # (raises the reference's ValueError('Not valid loss type'))
+        self.loss_type = loss_type
         self.grad_wire_dtype = grad_wire_dtype            # torch.bfloat16: gradient buckets cross the links as bf16 (dist.allreduce_mean_)
         self._ov = None                                   # overlap bookkeeping (overlap_begin / overlap_end)
         self.classes = classes
@@ -497,7 +500,7 @@ class GANTrainer:
 
     def _hyper(self):
         """What the captured launches bake in (see FusedAdam.hyper, FusedEMA.hyper)."""
-        key = (self.opt_g.hyper(), self.opt_d.hyper())
+        key = (self.opt_g.hyper(), self.opt_d.hyper(), self.loss_type)
         return key if self.ema is None else key + (self.ema.hyper(),)
 
     # ---- data-parallel gradient exchange: two buckets per network, started under the backward pass -------------
@@ -618,15 +621,16 @@ class GANTrainer:
         if _PAIR_D:
             # D(real) and D(fake) as one pass over the 2N batch (DiscriminatorEngine.forward_pair): the spectral-norm
             # power iterations of the two reference forwards depend on the weights alone and run first, in order
-            logits, ctx = self.deng.forward_pair(img, fake, ind, ind2, x2=x2, codes=codes, tail_loss='d_pair' if _FUSE_TAIL else None)
+            logits, ctx = self.deng.forward_pair(img, fake, ind, ind2, x2=x2, codes=codes, tail_loss='d_pair' if _FUSE_TAIL else None,
+                                                 loss_type=self.loss_type)
             n = ind.shape[0]
             lg = logits.view(-1)
             if 'tail' in ctx:
-                # the tail's launch formed d(hinge_d)/d(logit) and the tail's input gradient; the loss value comes out of the
+                # the tail's launch formed d(D loss)/d(logit) and the tail's input gradient; the loss value comes out of the
                 # backward pass's tail-gradient launch (two launches where there were four)
                 self.loss_d, dboth = ctx['loss'][0], ctx['tail'][0]
             else:
-                self.loss_d, _, _, dboth = ops.hinge_d(lg[:n], lg[n:], both=True)      # d(real) and d(fake) side by side
+                self.loss_d, _, _, dboth = ops.gan_loss_d(lg[:n], lg[n:], self.loss_type, both=True)      # d(real) and d(fake) side by side
             # `fuse` (single rank): the raw per-half gradients stay as they are -- d_apply turns them into the update in one
             # fused launch per layer table (spectral-norm fix + Adam) and self.grad_d is not written
             yield from self.deng.backward_iter(ctx, dboth, self.grad_d, False, False, split=self.world > 1,
@@ -634,7 +638,7 @@ class GANTrainer:
             return
         d_real, ctx_r = self.deng.forward(img, ind, True)
         d_fake, ctx_f = self.deng.forward(fake, ind, True)
-        self.loss_d, dreal, dfake = ops.hinge_d(d_real.view(-1), d_fake.view(-1))
+        self.loss_d, dreal, dfake = ops.gan_loss_d(d_real.view(-1), d_fake.view(-1), self.loss_type)
         self.deng.backward(ctx_r, dreal, self.grad_d, False, False)
         yield from self.deng.backward_iter(ctx_f, dfake, self.grad_d, True, False, split=self.world > 1)   # final once the second pass added
 
@@ -653,8 +657,8 @@ class GANTrainer:
 
     def g_compute_iter(self, ind, z):
         fake, gctx = self.geng.forward(z, ind, True, nhwc=_NHWC_PAIR)  # (engine to engine: images and their gradient stay NHWC)
-        d_fake, dctx = self.deng.forward(fake, ind, True, tail_loss='g' if _FUSE_TAIL else None)
-        self.loss_g, dfake = ops.hinge_g(d_fake.view(-1))
+        d_fake, dctx = self.deng.forward(fake, ind, True, tail_loss='g' if _FUSE_TAIL else None, loss_type=self.loss_type)
+        self.loss_g, dfake = ops.gan_loss_g(d_fake.view(-1), self.loss_type)
         if 'tail' in dctx:
             dfake = dctx['tail'][0]                      # (the same values; the tail's input gradient exists already)
         dimg = self.deng.backward(dctx, dfake, None, False, True)
@@ -799,7 +803,7 @@ class _CGANPieces:
         n = label.shape[0]
         d_real, ctx_r = t.deng.forward(inputs['real'], None, True, label=label)
         d_fake, ctx_f = t.deng.forward(Nhwc(fakes.t[j * n:(j + 1) * n], fakes.c), None, True, label=label)
-        t.loss_d, dreal, dfake = ops.hinge_d(d_real.view(-1), d_fake.view(-1))
+        t.loss_d, dreal, dfake = ops.gan_loss_d(d_real.view(-1), d_fake.view(-1), t.loss_type)
         # (the fake pass first: its transposed weight images are the current ones; the sum is the same either way)
         t.deng.backward(ctx_f, dfake, t.grad_d, False, False)
         t.deng.backward(ctx_r, dreal, t.grad_d, True, False)
@@ -808,8 +812,9 @@ class _CGANPieces:
     def g_compute_iter(self, inputs, z):
         t, label = self.t, inputs['label']
         fake, gctx = t.geng.forward(z, None, True, nhwc=True, label=label)
-        d_fake, dctx = t.deng.forward(fake, None, True, tail_loss='g' if _FUSE_TAIL else None, label=label)
-        t.loss_g, dfake = ops.hinge_g(d_fake.view(-1))
+        d_fake, dctx = t.deng.forward(fake, None, True, tail_loss='g' if _FUSE_TAIL else None, label=label,
+                                      loss_type=t.loss_type)
+        t.loss_g, dfake = ops.gan_loss_g(d_fake.view(-1), t.loss_type)
         if 'tail' in dctx:
             dfake = dctx['tail'][0]
         dimg = t.deng.backward(dctx, dfake, None, False, True)
