@@ -65,6 +65,20 @@ def pop_ema_flags(argv=None):
     return out
 
 
+def pop_lecam_flags(argv=None):
+    """--lecam_lambda L / --lecam_decay D / --lecam_start K (train_gan.py) -> {'lecam_lambda': float, 'lecam_decay': float,
+    'lecam_start': int}; 0 / 0.99 / 0 when not given: no regulariser.  K counts discriminator updates: the term is off
+    until K updates are done, the anchors move from the first."""
+    lam, d, k = pop_flag('--lecam_lambda', argv), pop_flag('--lecam_decay', argv), pop_flag('--lecam_start', argv)
+    out = {'lecam_lambda': 0.0 if lam is None else float(lam), 'lecam_decay': 0.99 if d is None else float(d),
+           'lecam_start': 0 if k is None else int(k)}
+    if not 0.0 <= out['lecam_lambda'] < float('inf') or not 0.0 <= out['lecam_decay'] < 1.0 or out['lecam_start'] < 0:
+        raise ValueError('Not valid --lecam_lambda / --lecam_decay / --lecam_start: lambda >= 0, decay in [0, 1), start >= 0')
+    if out['lecam_lambda'] == 0 and (d is not None or k is not None):
+        raise ValueError('Not valid --lecam_decay / --lecam_start: they go with --lecam_lambda > 0')
+    return out
+
+
 def pop_use_ema(argv=None):
     """--use_ema {True,False} (the sampling drivers) -> bool, False when not given."""
     v = pop_flag('--use_ema', argv)

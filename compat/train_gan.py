@@ -27,6 +27,9 @@ What differs, and why:
     the checkpoint gains one top-level key, 'generator_ema'; `model_dict` keeps the live weights.  The reference has none.
   * cfg['loss_type'] ('Hinge', train_gan.py:55) is a flag here, --loss_type {Hinge,BCE} (compat/_flags.py): both engines
     take it (train_gan.py:148-156,168-174) and it lands in the checkpoint's cfg; the model tag has no loss in it.
+  * --lecam_lambda L (with --lecam_decay, --lecam_start; --engine fused only) adds the LeCam regulariser to the discriminator
+    loss (trainer.FusedLeCam): the checkpoint gains one top-level key, 'lecam', and the epoch's info block
+    one line with the anchors and r_t = mean sign(D(real)).  Off (the default) nothing differs.  The reference has none.
 """
 import argparse
 import os
@@ -42,7 +45,7 @@ import torch.nn.functional as F  # noqa: E402
 
 import models  # noqa: E402  (the compat shim: mcgen_amd's module trees under the reference's names)
 import data as data_shim  # noqa: E402
-from _flags import pop_ema_flags, pop_loss_type_flags, pop_optimizer_flags  # noqa: E402
+from _flags import pop_ema_flags, pop_lecam_flags, pop_loss_type_flags, pop_optimizer_flags  # noqa: E402
 from config import cfg  # noqa: E402
 from data import fetch_dataset, make_data_loader  # noqa: E402
 from logger import Logger  # noqa: E402
@@ -53,6 +56,7 @@ def parse():
     optimizer_flags = pop_optimizer_flags()                  # --optimizer_name / --momentum (compat/_flags.py)
     ema_flags = pop_ema_flags()                              # --ema_decay / --ema_start: the averaged generator (off at 0)
     loss_flags = pop_loss_type_flags()                       # --loss_type {Hinge,BCE}
+    lecam_flags = pop_lecam_flags()                          # --lecam_lambda / --lecam_decay / --lecam_start (off at 0)
     ap = argparse.ArgumentParser(description='cfg')
     for k in cfg:                                            # train_gan.py:19-24: every cfg key is a flag
         if isinstance(cfg[k], (str, int, float)) or cfg[k] is None:
@@ -65,6 +69,7 @@ def parse():
     a = vars(ap.parse_args())
     extra = {k: a.pop(k) for k in ('engine', 'synthetic_size', 'output_dir', 'generate_per_mode')}
     extra.update(ema_flags)
+    extra.update(lecam_flags)
     for k in list(a):
         if k in cfg or k == 'control_name':
             cfg[k] = a[k]
@@ -106,13 +111,13 @@ def make_optimizer(model, lr, betas):                        # train_gan.py:222-
     raise ValueError('Not valid optimizer name')
 
 
-def make_trainer(model, lr, betas, world=1, ema_decay=0.0, ema_start=0):
-    """The fused counterpart of make_optimizer: GraphedGANTrainer builds cfg['optimizer_name'] for both networks, and the
-    averaged generator when ema_decay > 0."""
+def make_trainer(model, lr, betas, world=1, ema_decay=0.0, ema_start=0, lecam=None):
+    """The fused counterpart of make_optimizer: GraphedGANTrainer builds cfg['optimizer_name'] for both networks, the
+    averaged generator when ema_decay > 0, and the LeCam regulariser when `lecam` (pop_lecam_flags' dict) has lambda > 0."""
     from mcgen_amd.trainer import GraphedGANTrainer
     return GraphedGANTrainer(model, cfg['classes_size'], lr=lr, betas=betas, optimizer=cfg['optimizer_name'],
                              momentum=cfg['momentum'], weight_decay=cfg['weight_decay'], ema_decay=ema_decay, ema_start=ema_start,
-                             loss_type=cfg['loss_type'], dist_group=(torch.distributed.group.WORLD if world > 1 else None), world_size=world)
+                             loss_type=cfg['loss_type'], **(lecam or {}), dist_group=(torch.distributed.group.WORLD if world > 1 else None), world_size=world)
 
 
 def make_scheduler(optimizer):                               # train_gan.py:239-256 ('None' and the epoch-stepped ones)
@@ -251,19 +256,23 @@ def run():
         loader.set_shard(rank, world, seed)
     path = os.path.join(extra['output_dir'], 'model', f'{cfg["model_tag"]}_checkpoint.pt')
     if extra['engine'] == 'fused':
-        tr = make_trainer(model, 2e-4, (0.5, 0.999), world, extra['ema_decay'], extra['ema_start'])
+        tr = make_trainer(model, 2e-4, (0.5, 0.999), world, extra['ema_decay'], extra['ema_start'],
+                          {k: extra[k] for k in ('lecam_lambda', 'lecam_decay', 'lecam_start')} if extra['lecam_lambda'] else None)
         optimizer = {'generator': tr.opt_g, 'discriminator': tr.opt_d}
     else:
         if extra['ema_decay']:
             raise ValueError('Not valid engine: --ema_decay needs --engine fused')
+        if extra['lecam_lambda']:
+            raise ValueError('Not valid engine: --lecam_lambda needs --engine fused')
         tr = None
         optimizer = {'generator': make_optimizer(model.generator, 2e-4, (0.5, 0.999)),
                      'discriminator': make_optimizer(model.discriminator, 2e-4, (0.5, 0.999))}
     scheduler = {k: (FusedSchedule(o) if tr is not None else make_scheduler(o)) for k, o in optimizer.items()}
     ema = tr.ema if tr is not None else None                 # None: no averaged generator, the checkpoint keeps today's keys
+    lecam = tr.lecam if tr is not None else None             # None: no regulariser, log and checkpoint as they were
     last_epoch, logger = 1, None
     if int(cfg['resume_mode']) == 1 and os.path.exists(path):                  # train_gan.py:80-81,258-282
-        last_epoch, logger = resume(path, model, optimizer, scheduler, ema=ema)
+        last_epoch, logger = resume(path, model, optimizer, scheduler, ema=ema, lecam=lecam)
         if tr is not None:
             tr.geng.refresh_images(force=True)
         print(f'Resume from {last_epoch}')
@@ -287,8 +296,11 @@ def run():
         n_img = len(loader) * loader.batch_size                 # this rank's share of the epoch (the loader is sharded)
         logger.append({'Loss_D': last[0], 'Loss_G': last[1], 'Loss': abs(last[0] - last[1])}, 'train', n=n_img)   # train_gan.py:177-180
         rate = n_img * world / (time.time() - t0)               # samples consumed by all ranks / wall time
-        logger.append({'info': ['Model: {}'.format(cfg['model_tag']), 'Train Epoch: {}(100%)'.format(epoch),
-                                '{:.0f} images/s'.format(rate)]}, 'train', mean=False)
+        info = ['Model: {}'.format(cfg['model_tag']), 'Train Epoch: {}(100%)'.format(epoch), '{:.0f} images/s'.format(rate)]
+        if lecam is not None:                                # read here, at the log interval: no per-step synchronisation
+            (a_r, a_f), r_t = lecam.anchors(), lecam.stats()['r_t']
+            info.append('LeCam: a_R {:.4f} a_F {:.4f} r_t {:.3f}'.format(float(a_r), float(a_f), float(r_t)))
+        logger.append({'info': info}, 'train', mean=False)
         if rank == 0:
             logger.write('train', ['Loss', 'Loss_D', 'Loss_G'])
         if ema is not None:
@@ -300,7 +312,7 @@ def run():
             sch.step()
         logger.safe(False)
         if rank == 0:
-            save(make_checkpoint(model, optimizer, epoch + 1, cfg, scheduler=scheduler, logger=logger, ema=ema), path)   # train_gan.py:111-119
+            save(make_checkpoint(model, optimizer, epoch + 1, cfg, scheduler=scheduler, logger=logger, ema=ema, lecam=lecam), path)   # train_gan.py:111-119
             if scorer is not None:                                             # train_gan.py:119-122
                 cfg['pivot'], best = pivot_update(cfg['pivot'], logger.mean['test/{}'.format(cfg['pivot_metric'])])
                 if best:

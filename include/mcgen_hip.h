@@ -492,6 +492,41 @@ int mcgen_dtail_loss_fused(const void* x, int dtype, const float* code, const fl
 int mcgen_dtail_pair_wgrad_gan_loss(const float* dlogit, const float* pooled, const float* ratio, const float* logit, int N, int C,
                                     float* dw1, float* db1, float* dw2, float* db2, float* loss, int loss_type, void* stream);
 
+/* The LeCam regulariser of the discriminator loss (Tseng et al., "Regularizing GANs under Limited Data", CVPR 2021): it
+ * pulls D(real) towards a running mean of D(generated) and D(generated) towards a running mean of D(real).  The state
+ * lives on the device: the anchors a_real / a_fake (running means of the real / generated logits, initially 0), the
+ * count t of discriminator updates done (initially 0), and the statistics of the last update.  For update t with N real
+ * logits r_i and N generated logits f_i, active = lambda > 0 && t >= start, anchors as they stand BEFORE the update:
+ *   R      = mean (r_i - a_fake)^2 + mean (f_i - a_real)^2
+ *   loss   = base(loss_type) + (active ? lambda * R : 0)
+ *   dreal  = base_i + (active ? ((2 lambda) (r_i - a_fake)) fl(1 / N) : 0)       (dfake: f_i and a_real)
+ * in exactly this order: one subtraction, two products, one addition, none contracted; the anchors are constants of the
+ * differentiation.  An inactive term leaves the base derivative's and the base loss's bits.  Then the entry that owns
+ * the loss value writes m_real = mean r_i, m_fake = mean f_i, r_t = mean sign(r_i) (sign(0) = 0; ADA's overfitting
+ * indicator) and reg = R, moves the anchors -- t == 0: a = m, otherwise a = decay * a + (1 - decay) * m -- and adds 1
+ * to t.  The anchors move on every update, before `start` as well, so they are warm when the term switches on.
+ * Refused before any launch (state and outputs untouched): a null pointer, lambda < 0 or not finite, decay outside
+ * [0, 1), start < 0, and whatever the entry without the regulariser refuses. */
+typedef struct {
+    float a_real, a_fake;              /* the anchors */
+    float m_real, m_fake, r_t, reg;    /* of the last update: mean real / generated logit, mean sign(real), R */
+    int64_t t;                         /* discriminator updates done */
+} mcgen_lecam_state_t;
+/* mcgen_gan_loss_d with the regulariser: one block; reads the state, writes loss / dreal / dfake, then updates the state. */
+int mcgen_lecam_loss_d(const float* real, const float* fake, int N, int loss_type, mcgen_lecam_state_t* state_dev,
+                       float lambda, float decay, int start, float* loss, float* dreal, float* dfake, void* stream);
+/* mcgen_dtail_loss_fused, mode 0 (the paired discriminator pass, N even), with the regulariser's term in dlogit: thread 0
+ * of a sample's workgroup reads the anchors and t.  The state is only read; mcgen_dtail_pair_wgrad_lecam_loss, later in
+ * the same update, writes it.  dlogit is mcgen_lecam_loss_d's for the same logits and state, bit for bit. */
+int mcgen_dtail_lecam_fused(const void* x, int dtype, const float* code, const float* w, const float* b, const float* sigma,
+                            float* pooled, float* logit, float* dlogit, void* dx, int N, int HW, int C, int loss_type,
+                            const mcgen_lecam_state_t* state_dev, float lambda, int start, void* stream);
+/* mcgen_dtail_pair_wgrad_gan_loss with the regulariser: the extra block also adds lambda * R (old anchors) to the loss
+ * value and then updates the state, in mcgen_lecam_loss_d's order of sums (the same loss bits). */
+int mcgen_dtail_pair_wgrad_lecam_loss(const float* dlogit, const float* pooled, const float* ratio, const float* logit, int N, int C,
+                                      float* dw1, float* db1, float* dw2, float* db2, float* loss, int loss_type,
+                                      mcgen_lecam_state_t* state_dev, float lambda, float decay, int start, void* stream);
+
 /* dx = dy * (1 - y*y)      (nn.Tanh backward, mcgan.py:60) */
 int mcgen_tanh_bwd(const void* dy, const void* y, void* dx, int dtype, int64_t n, void* stream);
 

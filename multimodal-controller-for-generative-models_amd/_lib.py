@@ -35,6 +35,7 @@ AnBwd = HEADER.structs['mcgen_an_bwd_t']
 Pcs = HEADER.structs['mcgen_pcs_t']
 BnRun = HEADER.structs['mcgen_bn_run_t']
 SnLayer = HEADER.structs['mcgen_sn_layer_t']
+LecamState = HEADER.structs['mcgen_lecam_state_t']
 
 CONSTANTS = HEADER.constants            # every #define and enumerator: MCGEN_ROUTE_*, MCGEN_*_MAX, ...
 F32, BF16 = CONSTANTS['MCGEN_F32'], CONSTANTS['MCGEN_BF16']

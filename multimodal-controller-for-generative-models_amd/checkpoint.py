@@ -72,11 +72,13 @@ def _opt_state(opt):
     return opt.state_dict()
 
 
-def make_checkpoint(model, optimizer, epoch: int, cfg: Optional[dict] = None, scheduler=None, logger=None, ema=None) -> Dict[str, Any]:
+def make_checkpoint(model, optimizer, epoch: int, cfg: Optional[dict] = None, scheduler=None, logger=None, ema=None,
+                    lecam=None) -> Dict[str, Any]:
     """The dict train_gan.py:112-118 saves (epoch = number of finished epochs).  Tensors are moved to the CPU so the
     file loads anywhere, as the reference's map_location does on load.  `ema` (trainer.FusedEMA, or None): its state_dict
     goes under one more top-level key, 'generator_ema', which every loader of the reference's format ignores; without
-    it the dict has exactly the reference's keys."""
+    it the dict has exactly the reference's keys.  `lecam` (trainer.FusedLeCam, or None): likewise one more top-level key,
+    'lecam' (anchors, update count, hyper-parameters: plain numbers)."""
     def cpu(sd):
         if isinstance(sd, dict):
             return {k: cpu(v) for k, v in sd.items()}
@@ -88,6 +90,8 @@ def make_checkpoint(model, optimizer, epoch: int, cfg: Optional[dict] = None, sc
            'scheduler_dict': cpu(_opt_state(scheduler)) if scheduler is not None else None, 'logger': logger}
     if ema is not None:
         out['generator_ema'] = cpu(ema.state_dict())
+    if lecam is not None:
+        out['lecam'] = lecam.state_dict()
     return out
 
 
@@ -111,10 +115,11 @@ def save_checkpoint(path: str, model, optimizer, epoch: int, cfg: Optional[dict]
     save(make_checkpoint(model, optimizer, epoch, cfg, scheduler, logger), path)
 
 
-def resume(path: str, model, optimizer=None, scheduler=None, ema=None):
+def resume(path: str, model, optimizer=None, scheduler=None, ema=None, lecam=None):
     """train_gan.py:258-282: load model / optimizer / scheduler state; returns (last_epoch, logger).  Raises
     FileNotFoundError where the reference silently starts from scratch -- the caller decides.  `ema` (trainer.FusedEMA):
-    restored from 'generator_ema'; a file without the key starts the average over from the resumed parameters."""
+    restored from 'generator_ema'; a file without the key starts the average over from the resumed parameters.  `lecam`
+    (trainer.FusedLeCam): restored from 'lecam'; a file without the key starts with fresh anchors, and says so."""
     ck = load(path)
     model.load_state_dict(ck['model_dict'])
     if ema is not None:
@@ -123,6 +128,12 @@ def resume(path: str, model, optimizer=None, scheduler=None, ema=None):
         else:
             print('No averaged generator in {}: the average starts from the resumed parameters'.format(path))
             ema.reset()
+    if lecam is not None:
+        if ck.get('lecam') is not None:
+            lecam.load_state_dict(ck['lecam'])
+        else:
+            print('No LeCam state in {}: the anchors start fresh'.format(path))
+            lecam.reset()
     if optimizer is not None:
         if isinstance(optimizer, dict):
             for k, o in optimizer.items():

@@ -996,11 +996,48 @@ __device__ __forceinline__ float gan_sigmoid(float a) { return 1.f / (1.f + expf
 __device__ __forceinline__ float gan_softplus(float a) { return fmaxf(a, 0.f) + log1pf(expf(-fabsf(a))); }
 __device__ __forceinline__ float gan_dl_ones(float lg, float inv) { return -gan_sigmoid(-lg) * inv; }   // target 1
 __device__ __forceinline__ float gan_dl_zeros(float lg, float inv) { return gan_sigmoid(lg) * inv; }    // target 0
-template <typename T, int LOSS = MCGEN_GAN_LOSS_HINGE>
+// The LeCam regulariser's share of d(D loss)/d(logit) (mcgen_hip.h, mcgen_lecam_state_t): dl + ((2 lambda) (lg - anchor)) inv,
+// one subtraction, two products, one addition, never contracted into an fma -- the fused tail, the stand-alone kernel and
+// the float64 reference's bound all mean this sequence.  lecam_value: base + lambda (qr inv + qf inv), likewise.
+__device__ __forceinline__ float lecam_add(float dl, float lg, float anchor, float two_lambda, float inv) {
+#pragma clang fp contract(off)
+    const float d = lg - anchor;
+    const float p = two_lambda * d;
+    const float q = p * inv;
+    return dl + q;
+}
+__device__ __forceinline__ float lecam_sq(float acc, float lg, float anchor) {
+#pragma clang fp contract(off)
+    const float d = lg - anchor;
+    const float q = d * d;
+    return acc + q;
+}
+__device__ __forceinline__ float lecam_reg(float qr, float qf, float inv) {
+#pragma clang fp contract(off)
+    const float x = qr * inv, y = qf * inv;
+    return x + y;
+}
+__device__ __forceinline__ float lecam_value(float base, float lambda, float reg) {
+#pragma clang fp contract(off)
+    const float p = lambda * reg;
+    return base + p;
+}
+__device__ __forceinline__ float lecam_anchor(float a, float m, float decay, bool first) {
+#pragma clang fp contract(off)
+    if (first) return m;
+    const float x = decay * a, y = (1.f - decay) * m;
+    return x + y;
+}
+// LECAM (mode 0 only): thread 0 also reads the anchors and t and adds the regulariser's term before s_dl is published.
+// (The instantiations without LECAM compute what they computed; their kernel-argument block did grow by the three
+// defaulted trailing parameters, which every launch now passes and they never read.)
+// The state is READ here; the same update's tail-gradient launch (dtail_pair_w_kernel<LOSS, true>) writes it.
+template <typename T, int LOSS = MCGEN_GAN_LOSS_HINGE, bool LECAM = false>
 __global__ __launch_bounds__(256)
 void dtail_fused_kernel(const T* __restrict__ x, const float* __restrict__ code, const float* __restrict__ w,
                         const float* __restrict__ b, const float* __restrict__ sigma, float* pooled, float* logit,
-                        float* dlogit, T* __restrict__ dx, int N, int HW, int C, int mode) {
+                        float* dlogit, T* __restrict__ dx, int N, int HW, int C, int mode,
+                        const mcgen_lecam_state_t* lecam = nullptr, float lambda = 0.f, int start = 0) {
     extern __shared__ float acc[];                       // [pixel lanes][C]
     __shared__ float red[32];
     __shared__ float s_dl;
@@ -1042,6 +1079,11 @@ void dtail_fused_kernel(const T* __restrict__ x, const float* __restrict__ code,
             const int h = N / 2;
             dl = (n < h) ? ((1.f - lg) > 0.f ? -1.f / (float)h : 0.f) : ((1.f + lg) > 0.f ? 1.f / (float)h : 0.f);
         } else dl = -1.f / (float)N;
+        if (LECAM) {
+            const int h = N / 2;
+            if (lambda > 0.f && lecam->t >= (int64_t)start)
+                dl = lecam_add(dl, lg, (n < h) ? lecam->a_fake : lecam->a_real, 2.f * lambda, 1.f / (float)h);
+        }
         dlogit[n] = dl;
         s_dl = dl;
     }
@@ -1152,6 +1194,61 @@ __global__ void bce_g_kernel(const float* fake, int N, float* loss, float* dfake
     }
     a = block_sum(a, red);
     if (threadIdx.x == 0) loss[0] = a * inv;
+}
+// The discriminator loss with the LeCam regulariser over N real + N generated logits, by ONE block: the base loss's sums
+// in hinge_d_kernel's / bce_d_kernel's order, the regulariser's two sums of squares against the anchors as they stand,
+// and the sums behind the statistics; then thread 0 writes the loss value, the statistics, the moved anchors and t + 1.
+// Every thread reads the state at the top; thread 0 writes it behind the block_sums' barriers, so no thread of the block
+// sees a new value.  All sums are block_sum's fixed order (no float atomics); the state writes are thread 0's plain stores.
+// GRAD: also d loss / d logit per sample (the stand-alone entry; the fused tail formed it already on the paired path).
+// `base = a * inv + f * inv` is deliberately the expression hinge_d_kernel / bce_d_kernel / dtail_pair_w_kernel hold, under
+// the same (default) contraction: an inactive term must give THEIR loss bits, and those kernels are not touched here.  The
+// identity is the compiler's to keep, not the source's; tests/test_lecam_kernels_gpu.py compares the words.
+template <int LOSS, bool GRAD>
+__device__ __forceinline__ void lecam_d_block(const float* real, const float* fake, int N, float* red, float* loss,
+                                              float* dreal, float* dfake, mcgen_lecam_state_t* st,
+                                              float lambda, float decay, int start) {
+    const float a_real = st->a_real, a_fake = st->a_fake;
+    const int64_t t = st->t;
+    const bool active = lambda > 0.f && t >= (int64_t)start;
+    const float inv = 1.f / (float)N, two_lambda = 2.f * lambda;
+    float a = 0.f, f = 0.f, sr = 0.f, sf = 0.f, ss = 0.f, qr = 0.f, qf = 0.f;
+    for (int i = threadIdx.x; i < N; i += blockDim.x) {
+        const float r = real[i], g = fake[i];
+        if (LOSS == MCGEN_GAN_LOSS_BCE) { a += gan_softplus(-r); f += gan_softplus(g); }
+        else { a += fmaxf(1.f - r, 0.f); f += fmaxf(1.f + g, 0.f); }
+        sr += r; sf += g;
+        ss += (r > 0.f) ? 1.f : ((r < 0.f) ? -1.f : 0.f);
+        qr = lecam_sq(qr, r, a_fake); qf = lecam_sq(qf, g, a_real);
+        if (GRAD) {
+            float dr, dg;
+            if (LOSS == MCGEN_GAN_LOSS_BCE) { dr = gan_dl_ones(r, inv); dg = gan_dl_zeros(g, inv); }
+            else { dr = (1.f - r) > 0.f ? -inv : 0.f; dg = (1.f + g) > 0.f ? inv : 0.f; }
+            if (active) { dr = lecam_add(dr, r, a_fake, two_lambda, inv); dg = lecam_add(dg, g, a_real, two_lambda, inv); }
+            dreal[i] = dr; dfake[i] = dg;
+        }
+    }
+    a = block_sum(a, red); f = block_sum(f, red + 32);
+    sr = block_sum(sr, red); sf = block_sum(sf, red + 32);
+    ss = block_sum(ss, red);
+    qr = block_sum(qr, red + 32); qf = block_sum(qf, red);
+    if (threadIdx.x == 0) {
+        const float base = a * inv + f * inv;
+        const float reg = lecam_reg(qr, qf, inv);
+        loss[0] = active ? lecam_value(base, lambda, reg) : base;
+        const float m_real = sr * inv, m_fake = sf * inv;
+        st->m_real = m_real; st->m_fake = m_fake; st->r_t = ss * inv; st->reg = reg;
+        st->a_real = lecam_anchor(a_real, m_real, decay, t == 0);
+        st->a_fake = lecam_anchor(a_fake, m_fake, decay, t == 0);
+        st->t = t + 1;
+    }
+}
+template <int LOSS>
+__global__ __launch_bounds__(256)
+void lecam_d_kernel(const float* real, const float* fake, int N, float* loss, float* dreal, float* dfake,
+                    mcgen_lecam_state_t* st, float lambda, float decay, int start) {
+    __shared__ float red[64];
+    lecam_d_block<LOSS, true>(real, fake, N, red, loss, dreal, dfake, st, lambda, decay, start);
 }
 template <typename T>
 __global__ void tanh_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ y, T* __restrict__ dx, size_t n) {
@@ -1720,12 +1817,25 @@ extern "C" int mcgen_dtail_bwd(const float* dlogit, const void* x, int dtype, co
 
 // Paired discriminator pass: tail weight / bias gradients of the two halves of a 2N batch in one launch (blockIdx.y =
 // half); the second half's pooled features carry sigma_1 / sigma_2, which `ratio` divides out of its weight gradient.
-template <int LOSS>
+// LECAM: the extra block also owes the regulariser's value and the state update (lecam_d_block).  Ordering of the state
+// within one discriminator update: the tail launch (dtail_fused_kernel<.., true>) only READS the state and precedes this
+// launch on the stream -- the whole backward pass lies between them -- so it sees the anchors and t from before the
+// update; this launch is the only writer.  The next update's tail launch follows this one on the same stream, and in a
+// captured graph on the same chain of dependent nodes (its input is the discriminator this update's optimizer step
+// wrote, which consumed these gradients), so it sees the moved anchors and t + 1.
+// (Without LECAM the kernel computes what it computed; its kernel-argument block grew by the four defaulted parameters.)
+template <int LOSS, bool LECAM = false>
 __global__ __launch_bounds__(256)
 void dtail_pair_w_kernel(const float* __restrict__ dlogit, const float* __restrict__ pooled, const float* __restrict__ ratio,
                          float* dw1, float* db1, float* dw2, float* db2, int N, int C,
-                         const float* __restrict__ logit = nullptr, float* loss = nullptr) {
+                         const float* __restrict__ logit = nullptr, float* loss = nullptr,
+                         mcgen_lecam_state_t* lecam = nullptr, float lambda = 0.f, float decay = 0.f, int start = 0) {
     __shared__ float sh[4][64];
+    if (LECAM && blockIdx.x == gridDim.x - 1) {
+        if (blockIdx.y == 0)
+            lecam_d_block<LOSS, false>(logit, logit + N, N, &sh[0][0], loss, nullptr, nullptr, lecam, lambda, decay, start);
+        return;
+    }
     if (loss && blockIdx.x == gridDim.x - 1) {
         // the extra block of a launch that also owes the hinge loss (train_gan.py:154): hinge_d_kernel's sums, same order
         // (LOSS = MCGEN_GAN_LOSS_BCE, train_gan.py:149-152: bce_d_kernel's)
@@ -1850,6 +1960,56 @@ extern "C" int mcgen_dtail_pair_wgrad_gan_loss(const float* dlogit, const float*
         return mcgen_dtail_pair_wgrad_loss(dlogit, pooled, ratio, logit, N, C, dw1, db1, dw2, db2, loss, stream);
     hipLaunchKernelGGL(dtail_pair_w_kernel<MCGEN_GAN_LOSS_BCE>, dim3((C + 63) / 64 + 1, 2), dim3(256), 0, STREAM(stream), dlogit, pooled, ratio, dw1, db1, dw2, db2, N, C, logit, loss);
     MCGEN_LAUNCH_CHECK("dtail_pair_wgrad_gan_loss"); return 0;
+}
+
+// ---- the LeCam regulariser (mcgen_hip.h: mcgen_lecam_state_t) -------------------------------------------------------------
+#define LECAM_ARGS_OK(name, st, lambda, start) \
+    MCGEN_CHECK(st, name ": null state"); \
+    MCGEN_CHECK((lambda) >= 0.f && (lambda) <= 3.0e38f, name ": lambda must be finite and not negative"); \
+    MCGEN_CHECK((start) >= 0, name ": start must not be negative")
+extern "C" int mcgen_lecam_loss_d(const float* real, const float* fake, int N, int loss_type, mcgen_lecam_state_t* state_dev,
+                                  float lambda, float decay, int start, float* loss, float* dreal, float* dfake, void* stream) {
+    MCGEN_CHECK(GAN_LOSS_KNOWN(loss_type), "lecam_loss_d: unknown loss_type %d (MCGEN_GAN_LOSS_HINGE or MCGEN_GAN_LOSS_BCE)", loss_type);
+    MCGEN_CHECK(real && fake && loss && dreal && dfake, "lecam_loss_d: null pointer");
+    MCGEN_CHECK(N > 0, "lecam_loss_d: N must be positive");
+    LECAM_ARGS_OK("lecam_loss_d", state_dev, lambda, start);
+    MCGEN_CHECK(decay >= 0.f && decay < 1.f, "lecam_loss_d: decay in [0, 1)");
+    if (loss_type == MCGEN_GAN_LOSS_HINGE)
+        hipLaunchKernelGGL(lecam_d_kernel<MCGEN_GAN_LOSS_HINGE>, dim3(1), dim3(256), 0, STREAM(stream), real, fake, N, loss, dreal, dfake, state_dev, lambda, decay, start);
+    else
+        hipLaunchKernelGGL(lecam_d_kernel<MCGEN_GAN_LOSS_BCE>, dim3(1), dim3(256), 0, STREAM(stream), real, fake, N, loss, dreal, dfake, state_dev, lambda, decay, start);
+    MCGEN_LAUNCH_CHECK("lecam_loss_d"); return 0;
+}
+extern "C" int mcgen_dtail_lecam_fused(const void* x, int dtype, const float* code, const float* w, const float* b, const float* sigma,
+                                       float* pooled, float* logit, float* dlogit, void* dx, int N, int HW, int C, int loss_type,
+                                       const mcgen_lecam_state_t* state_dev, float lambda, int start, void* stream) {
+    MCGEN_CHECK(GAN_LOSS_KNOWN(loss_type), "dtail_lecam_fused: unknown loss_type %d (MCGEN_GAN_LOSS_HINGE or MCGEN_GAN_LOSS_BCE)", loss_type);
+    MCGEN_CHECK(x && w && b && sigma && pooled && logit && dlogit && dx, "dtail_lecam_fused: null pointer");
+    MCGEN_CHECK(N > 0 && N % 2 == 0 && HW > 0, "dtail_lecam_fused: a paired batch (N even and positive), HW positive");
+    MCGEN_CHECK(C > 0 && C % 8 == 0 && C / 8 <= 256, "dtail_lecam_fused: C must be a multiple of 8, at most 2048");
+    LECAM_ARGS_OK("dtail_lecam_fused", state_dev, lambda, start);
+    const int pl = 256 / (C / 8);
+    const size_t lds = (size_t)pl * C * sizeof(float);
+#define LECAM_TAIL(T, LOSS) hipLaunchKernelGGL((dtail_fused_kernel<T, LOSS, true>), dim3(N), dim3(256), lds, STREAM(stream), \
+        (const T*)x, code, w, b, sigma, pooled, logit, dlogit, (T*)dx, N, HW, C, 0, state_dev, lambda, start)
+    if (loss_type == MCGEN_GAN_LOSS_HINGE) { DISPATCH_T(dtype, LECAM_TAIL(float, MCGEN_GAN_LOSS_HINGE), LECAM_TAIL(bf16_t, MCGEN_GAN_LOSS_HINGE)); }
+    else { DISPATCH_T(dtype, LECAM_TAIL(float, MCGEN_GAN_LOSS_BCE), LECAM_TAIL(bf16_t, MCGEN_GAN_LOSS_BCE)); }
+#undef LECAM_TAIL
+    MCGEN_LAUNCH_CHECK("dtail_lecam_fused"); return 0;
+}
+extern "C" int mcgen_dtail_pair_wgrad_lecam_loss(const float* dlogit, const float* pooled, const float* ratio, const float* logit, int N, int C,
+                                                 float* dw1, float* db1, float* dw2, float* db2, float* loss, int loss_type,
+                                                 mcgen_lecam_state_t* state_dev, float lambda, float decay, int start, void* stream) {
+    MCGEN_CHECK(GAN_LOSS_KNOWN(loss_type), "dtail_pair_wgrad_lecam_loss: unknown loss_type %d (MCGEN_GAN_LOSS_HINGE or MCGEN_GAN_LOSS_BCE)", loss_type);
+    MCGEN_CHECK(dlogit && pooled && ratio && logit && dw1 && db1 && dw2 && db2 && loss, "dtail_pair_wgrad_lecam_loss: null pointer");
+    MCGEN_CHECK(N > 0 && C > 0, "dtail_pair_wgrad_lecam_loss: N and C must be positive");
+    LECAM_ARGS_OK("dtail_pair_wgrad_lecam_loss", state_dev, lambda, start);
+    MCGEN_CHECK(decay >= 0.f && decay < 1.f, "dtail_pair_wgrad_lecam_loss: decay in [0, 1)");
+    if (loss_type == MCGEN_GAN_LOSS_HINGE)
+        hipLaunchKernelGGL((dtail_pair_w_kernel<MCGEN_GAN_LOSS_HINGE, true>), dim3((C + 63) / 64 + 1, 2), dim3(256), 0, STREAM(stream), dlogit, pooled, ratio, dw1, db1, dw2, db2, N, C, logit, loss, state_dev, lambda, decay, start);
+    else
+        hipLaunchKernelGGL((dtail_pair_w_kernel<MCGEN_GAN_LOSS_BCE, true>), dim3((C + 63) / 64 + 1, 2), dim3(256), 0, STREAM(stream), dlogit, pooled, ratio, dw1, db1, dw2, db2, N, C, logit, loss, state_dev, lambda, decay, start);
+    MCGEN_LAUNCH_CHECK("dtail_pair_wgrad_lecam_loss"); return 0;
 }
 extern "C" int mcgen_tanh_bwd(const void* dy, const void* y, void* dx, int dtype, int64_t n, void* stream) {
     MCGEN_CHECK(dy && y && dx && n > 0, "tanh_bwd: bad arguments");

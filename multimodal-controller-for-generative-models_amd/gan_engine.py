@@ -799,7 +799,8 @@ class DiscriminatorEngine:
         return self._codes.run_any(ind2)
 
     def forward_pair(self, real_nchw: Tensor, fake_nchw: Tensor, indicator: Tensor, ind2: Optional[Tensor] = None,
-                     x2: Optional[Nhwc] = None, codes=None, tail_loss: Optional[str] = None, loss_type: str = 'Hinge'):
+                     x2: Optional[Nhwc] = None, codes=None, tail_loss: Optional[str] = None, loss_type: str = 'Hinge',
+                     lecam=None):
         """D(real) and D(fake) of one discriminator update (train_gan.py:144-150) as ONE pass over the 2N batch.
         The two forwards of the reference differ only in the spectral-norm state (each runs its own power iteration,
         which depends on the weights alone): conv(x; W / sigma_2) = (sigma_1 / sigma_2) * conv(x; W / sigma_1), so the
@@ -809,7 +810,11 @@ class DiscriminatorEngine:
         `codes` (optional): `pair_codes(ind2)`, computed once for several updates on the same labels.
         `tail_loss` 'd_pair': the tail's launch also forms d(D loss)/d(logit) of the 2N batch for `loss_type` ('Hinge' |
         'BCE') and the tail's input gradient (ctx['tail']); `backward_iter` writes that loss's value into ctx['loss']
-        (train_gan.py:148-154)."""
+        (train_gan.py:148-154).
+        `lecam` (a trainer.FusedLeCam with lambda > 0, or None): with the fused tail, d(D loss)/d(logit) carries the LeCam
+        regulariser's term from the holder's anchors (ops.dtail_lecam_fused) and `backward_iter`'s tail-gradient launch adds
+        its value to ctx['loss'] and moves the anchors -- the same two launches.  Without the fused tail the caller forms
+        the loss with ops.lecam_loss_d."""
         n = x2.shape[0] // 2 if x2 is not None else real_nchw.shape[0]
         (sigma1, uv1), (sigma2, uv2) = self._power_iters(2, True)
         ratio = self._sn_ratio if self._sn_ratio is not None else sigma1 / sigma2
@@ -834,9 +839,10 @@ class DiscriminatorEngine:
             ctx['codes_job'] = (self._codes_pair, lab[0], lab[1], ratio, n, lambda outs: scaled.update(zip(uses, outs)))
         else:
             scaled.update(zip(uses, self._codes_pair.run_any(ind2, ratio, n)))     # all scaled codes of the pass: one launch
-        return self._forward_body(x, ctx, lambda mc_i, sn_idx: scaled[(mc_i, sn_idx)], tail_loss, loss_type)
+        return self._forward_body(x, ctx, lambda mc_i, sn_idx: scaled[(mc_i, sn_idx)], tail_loss, loss_type, lecam)
 
-    def _forward_body(self, x_nchw: Tensor, ctx, code_of, tail_loss: Optional[str] = None, loss_type: str = 'Hinge'):
+    def _forward_body(self, x_nchw: Tensor, ctx, code_of, tail_loss: Optional[str] = None, loss_type: str = 'Hinge',
+                      lecam=None):
         dt = self.dtype
         n = x_nchw.shape[0]
         sigma = ctx['sigma']
@@ -894,8 +900,14 @@ class DiscriminatorEngine:
         if tail_loss is not None and ops.dtail_hinge_ok(x):
             if (tail_loss == 'd_pair') != (ctx['pair'] is not None):
                 raise McgenError("tail_loss: 'd_pair' goes with forward_pair, 'g' with forward")
-            logit, pooled_feat, dlogit, dxt = ops.dtail_loss_fused(x, codet, tl.m.weight_orig.detach().view(-1), tl.m.bias,
-                                                                   sigma[tl.idx:tl.idx + 1], tail_loss, loss_type)
+            if lecam is not None and tail_loss == 'd_pair':
+                logit, pooled_feat, dlogit, dxt = ops.dtail_lecam_fused(x, codet, tl.m.weight_orig.detach().view(-1), tl.m.bias,
+                                                                        sigma[tl.idx:tl.idx + 1], loss_type, lecam.state,
+                                                                        lecam.lam, lecam.start)
+                ctx['lecam'] = lecam                 # (backward_iter's tail-gradient launch owes the state update)
+            else:
+                logit, pooled_feat, dlogit, dxt = ops.dtail_loss_fused(x, codet, tl.m.weight_orig.detach().view(-1), tl.m.bias,
+                                                                       sigma[tl.idx:tl.idx + 1], tail_loss, loss_type)
             ctx['tail'] = (dlogit, dxt)
             ctx['loss_type'] = loss_type             # (backward_iter's tail-gradient launch writes the matching loss value)
             if tail_loss == 'd_pair':
@@ -1030,11 +1042,15 @@ class DiscriminatorEngine:
             # tail weight / bias gradients per half; the fake half's pooled features carry sigma_1 / sigma_2
             (_, g_a), (_, g_b) = passes
             with_loss = pre_dy is not None and 'loss' in ctx
+            lecam = ctx.get('lecam')
+            if lecam is not None and not with_loss:
+                raise McgenError('the LeCam term is in the fused tail\'s dlogit: backward_iter must be given ctx[\'tail\'][0]')
             ops.dtail_pair_wgrad(dlogit, ctx['pooled'], pair['ratio'][tl.idx:tl.idx + 1],
                                  self.flat_p.view_of(g_a, wl).view(-1), self.flat_p.view_of(g_a, bl).view(-1),
                                  self.flat_p.view_of(g_b, wl).view(-1), self.flat_p.view_of(g_b, bl).view(-1),
                                  logit=ctx['logit'] if with_loss else None, loss=ctx['loss'] if with_loss else None,
-                                 loss_type=ctx.get('loss_type', 'Hinge'))
+                                 loss_type=ctx.get('loss_type', 'Hinge'),
+                                 lecam=None if lecam is None else (lecam.state, lecam.lam, lecam.decay, lecam.start))
             return dy
 
         def block_bwd(b, bc, dy):

@@ -952,14 +952,70 @@ def dtail_loss_fused(x: Tensor, code: Optional[Tensor], w: Tensor, b: Tensor, si
     return both[0], pooled, both[1], dx
 
 
+def lecam_state_layout():
+    """mcgen_lecam_state_t as a tensor: -> (int64 words of the struct, {float field: float32 index}, int64 index of t),
+    read off the header's struct, so that a holder keeps the state as ONE int64 tensor with float32 / int64 views."""
+    st = _lib.LecamState
+    floats = {k: getattr(st, k).offset // 4 for k in ('a_real', 'a_fake', 'm_real', 'm_fake', 'r_t', 'reg')}
+    return C.sizeof(st) // 8, floats, st.t.offset // 8
+
+
+def _lecam_state(state: Tensor) -> int:
+    """The device address of a mcgen_lecam_state_t held as an int64 tensor (`lecam_state_layout`)."""
+    if state is None or state.dtype != torch.int64 or state.numel() * 8 != C.sizeof(_lib.LecamState):
+        raise _lib.McgenError('LeCam state: an int64 device tensor of sizeof(mcgen_lecam_state_t) bytes')
+    return _p(state)
+
+
+def dtail_lecam_fused(x: Tensor, code: Optional[Tensor], w: Tensor, b: Tensor, sigma: Tensor, loss_type: str,
+                      state: Tensor, lam: float, start: int):
+    """`dtail_loss_fused`, mode 'd_pair', with the LeCam regulariser's term in dlogit (mcgen_dtail_lecam_fused): the launch
+    reads the anchors and the update count from `state` and leaves them alone -- `dtail_pair_wgrad(..., lecam=...)` of the
+    same update writes them.  -> (logit [N], pooled [N, C], dlogit [N], dx like x)"""
+    n, c = x.shape[0], x.shape[-1]
+    hw = x.numel() // (n * c)
+    pooled = torch.empty((n, c), dtype=torch.float32, device=x.device)
+    both = torch.empty((2, n), dtype=torch.float32, device=x.device)
+    dx = torch.empty_like(x)
+    check(_lib.load().mcgen_dtail_lecam_fused(_p(x), _dt(x.dtype), _f32(code), _f32(w), _f32(b), _f32(sigma), _f32(pooled),
+                                              both[0].data_ptr(), both[1].data_ptr(), _p(dx), n, hw, c, gan_loss_id(loss_type),
+                                              _lecam_state(state), float(lam), int(start), _stream()), 'dtail_lecam_fused')
+    return both[0], pooled, both[1], dx
+
+
+def lecam_loss_d(real: Tensor, fake: Tensor, loss_type: str, state: Tensor, lam: float, decay: float, start: int,
+                 both: bool = False):
+    """`gan_loss_d` with the LeCam regulariser (mcgen_lecam_loss_d): (loss, d loss / d real, d loss / d fake) from the
+    anchors as `state` holds them, then the launch moves the anchors, writes the update's statistics and counts the update."""
+    n = real.numel()
+    out = torch.empty(1 + 2 * n, dtype=torch.float32, device=real.device)
+    check(_lib.load().mcgen_lecam_loss_d(_f32(real), _f32(fake), n, gan_loss_id(loss_type), _lecam_state(state), float(lam),
+                                         float(decay), int(start), out.data_ptr(), out[1:1 + n].data_ptr(), out[1 + n:].data_ptr(),
+                                         _stream()), 'lecam_loss_d')
+    if both:
+        return out[0], out[1:1 + n], out[1 + n:], out[1:]
+    return out[0], out[1:1 + n], out[1 + n:]
+
+
 def dtail_pair_wgrad(dlogit: Tensor, pooled: Tensor, ratio: Tensor, dw1: Tensor, db1: Tensor, dw2: Tensor, db2: Tensor,
-                     logit: Optional[Tensor] = None, loss: Optional[Tensor] = None, loss_type: str = 'Hinge'):
+                     logit: Optional[Tensor] = None, loss: Optional[Tensor] = None, loss_type: str = 'Hinge', lecam=None):
     """Tail weight / bias gradients of the two halves of a paired discriminator pass (dw2 divided by ratio[0]); with
-    `logit` [2N] and `loss` [1] the launch also writes the discriminator's loss of `loss_type` (train_gan.py:148-154)."""
+    `logit` [2N] and `loss` [1] the launch also writes the discriminator's loss of `loss_type` (train_gan.py:148-154).
+    `lecam` = (state, lambda, decay, start): the loss value includes the LeCam regulariser and the launch updates `state`
+    (mcgen_dtail_pair_wgrad_lecam_loss); it needs `logit` and `loss`."""
     n2, c = pooled.shape
     for t in (dw1, db1, dw2, db2):
         if not t.is_contiguous() or t.dtype != torch.float32:
             raise _lib.McgenError('dtail_pair_wgrad: outputs must be contiguous fp32')
+    if lecam is not None:
+        if loss is None or logit is None:
+            raise _lib.McgenError('dtail_pair_wgrad: the LeCam state is updated by the launch that writes the loss value')
+        state, lam, decay, start = lecam
+        check(_lib.load().mcgen_dtail_pair_wgrad_lecam_loss(_f32(dlogit), _f32(pooled), _f32(ratio), _f32(logit.contiguous()), n2 // 2, c,
+                                                            _f32(dw1), _f32(db1), _f32(dw2), _f32(db2), _f32(loss),
+                                                            gan_loss_id(loss_type), _lecam_state(state), float(lam), float(decay),
+                                                            int(start), _stream()), 'dtail_pair_wgrad_lecam_loss')
+        return
     if loss is not None:
         check(_lib.load().mcgen_dtail_pair_wgrad_gan_loss(_f32(dlogit), _f32(pooled), _f32(ratio), _f32(logit.contiguous()), n2 // 2, c,
                                                           _f32(dw1), _f32(db1), _f32(dw2), _f32(db2), _f32(loss),

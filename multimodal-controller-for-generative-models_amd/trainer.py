@@ -420,6 +420,68 @@ class FusedEMA:
         self._step_buf.zero_()
 
 
+class FusedLeCam:
+    """The device state of the LeCam regulariser of the discriminator loss (include/mcgen_hip.h, mcgen_lecam_state_t):
+    the anchors a_R / a_F (running means of the real / generated logits), the count t of discriminator updates and the
+    last update's statistics, as ONE int64 tensor the kernels address, with float32 / int64 views over it.  The launches
+    that form the discriminator loss read and move it (ops.dtail_lecam_fused + ops.dtail_pair_wgrad(lecam=...) on the
+    paired path, ops.lecam_loss_d elsewhere): nothing here launches anything, and t lives on the device, so a captured
+    update stays valid.  `lam` > 0: the term lam * R is on from update `start`; the anchors move from update 0."""
+
+    def __init__(self, device, lam: float, decay: float = 0.99, start: int = 0):
+        self.lam, self.decay, self.start = self.check_hyper(lam, decay, start)
+        words, self._f, self._t = ops.lecam_state_layout()
+        self.state = torch.zeros(words, dtype=torch.int64, device=device)
+        self._floats = self.state.view(torch.float32)
+        self.step_count = self.state[self._t:self._t + 1]
+
+    @staticmethod
+    def check_hyper(lam, decay, start):
+        lam, decay, start = float(lam), float(decay), int(start)
+        if not (0.0 <= lam < float('inf')) or not 0.0 <= decay < 1.0 or start < 0:
+            raise ValueError('Not valid LeCam regulariser: lambda >= 0 and finite, decay in [0, 1) and start >= 0')
+        return lam, decay, start
+
+    def hyper(self):
+        """(lambda, decay, start): kernel arguments of the loss launches, baked into a captured graph (FusedEMA.hyper)."""
+        return (self.lam, self.decay, self.start)
+
+    def state_tensors(self):
+        return [self.state]
+
+    def anchors(self):
+        """(a_R, a_F) as device scalars: views, they follow the updates."""
+        return self._floats[self._f['a_real']], self._floats[self._f['a_fake']]
+
+    def stats(self):
+        """Of the last discriminator update, device scalars: the mean real / generated logit, r_t = mean sign(D(real))
+        (ADA's overfitting indicator) and the regulariser's value R (before lambda)."""
+        f = self._floats
+        return {'m_R': f[self._f['m_real']], 'm_F': f[self._f['m_fake']], 'r_t': f[self._f['r_t']], 'R': f[self._f['reg']]}
+
+    def state_dict(self):
+        a_r, a_f = self.anchors()
+        return {'lambda': self.lam, 'decay': self.decay, 'start': self.start, 'a_R': float(a_r), 'a_F': float(a_f),
+                'step': int(self.step_count), 'stats': {k: float(v) for k, v in self.stats().items()}}
+
+    def load_state_dict(self, sd):
+        """Takes the anchors, the count and the statistics; the hyper-parameters stay the constructor's (they are the
+        flags of THIS run, and a captured graph holds them) -- where the dict's differ, a line says so."""
+        theirs = tuple(sd.get(k) for k in ('lambda', 'decay', 'start'))
+        if all(v is not None for v in theirs) and (float(theirs[0]), float(theirs[1]), int(theirs[2])) != self.hyper():
+            print('LeCam state was accumulated with (lambda, decay, start) = {}; this run goes on with {}'.format(theirs, self.hyper()))
+        host = torch.zeros(self.state.numel(), dtype=torch.int64)
+        f = host.view(torch.float32)
+        f[self._f['a_real']], f[self._f['a_fake']] = float(sd['a_R']), float(sd['a_F'])
+        for k, field in (('m_R', 'm_real'), ('m_F', 'm_fake'), ('r_t', 'r_t'), ('R', 'reg')):
+            f[self._f[field]] = float(sd.get('stats', {}).get(k, 0.0))
+        host[self._t] = int(sd['step'])
+        self.state.copy_(host)
+
+    def reset(self):
+        self.state.zero_()
+
+
 def _graph(fn, pool=None):
     """`fn()` captured into a new HIP graph (in the memory pool of an earlier one, if given)."""
     g = torch.cuda.CUDAGraph()
@@ -455,7 +517,14 @@ class GANTrainer:
     def __init__(self, model, classes: int, lr=2e-4, betas=(0.5, 0.999), d_iters: int = 5, g_iters: int = 1,
                  dist_group=None, world_size: int = 1, grad_wire_dtype: Optional[torch.dtype] = None,
                  optimizer: str = 'Adam', momentum: float = 0.0, weight_decay: float = 0.0,
-                 ema_decay: float = 0.0, ema_start: int = 0, loss_type: str = 'Hinge'):
+                 ema_decay: float = 0.0, ema_start: int = 0, loss_type: str = 'Hinge',
+                 lecam_lambda: float = 0.0, lecam_decay: float = 0.99, lecam_start: int = 0):
+        # the LeCam regulariser of the D loss (FusedLeCam; off at 0: then no launch, argument or result differs).  Checked
+        # before anything touches a device.
+        lecam_hyper = FusedLeCam.check_hyper(lecam_lambda, lecam_decay, lecam_start)
+        if lecam_hyper[0] > 0 and world_size > 1:
+            raise ValueError('Not valid LeCam regulariser: lecam_lambda > 0 runs on one GPU -- each rank would keep anchors of '
+                             'its own shard of the batch; anchors shared between ranks are not implemented')
         self.model = model
         # cfg['loss_type'] of train_gan.py:55,148-156,168-174; fixed here: a captured graph bakes its launches in
         ops.gan_loss_id(loss_type)                        # (raises the reference's ValueError('Not valid loss type'))
@@ -482,6 +551,9 @@ class GANTrainer:
         self._pieces = (_CGANPieces if self._cgan else _MCGANPieces)(self)      # the model's parts of the step (_step)
         # the averaged generator (opt-in): updated right behind every generator optimizer step (g_apply).  A multi-rank run
         # needs no exchange for it: every rank averages the same parameters.
+        self.lecam = None
+        if lecam_hyper[0] > 0:
+            self.lecam = FusedLeCam(self.grad_d.device, *lecam_hyper)
         self.ema = None
         if ema_decay:
             gen = model.generator
@@ -501,7 +573,17 @@ class GANTrainer:
     def _hyper(self):
         """What the captured launches bake in (see FusedAdam.hyper, FusedEMA.hyper)."""
         key = (self.opt_g.hyper(), self.opt_d.hyper(), self.loss_type)
-        return key if self.ema is None else key + (self.ema.hyper(),)
+        if self.ema is not None:
+            key += (self.ema.hyper(),)
+        return key if self.lecam is None else key + (('lecam',) + self.lecam.hyper(),)      # (last: train_iteration looks there)
+
+    def _loss_d(self, real, fake, both=False):
+        """The stand-alone D loss of the legs without the fused tail (and of CGAN's two passes): ops.gan_loss_d, or with the
+        LeCam regulariser on ops.lecam_loss_d, which also moves the holder's state -- one launch either way."""
+        if self.lecam is None:
+            return ops.gan_loss_d(real, fake, self.loss_type, both=both)
+        lc = self.lecam
+        return ops.lecam_loss_d(real, fake, self.loss_type, lc.state, lc.lam, lc.decay, lc.start, both=both)
 
     # ---- data-parallel gradient exchange: two buckets per network, started under the backward pass -------------
     # The engines' backward passes hand out each network's flat gradient in two contiguous buckets: the LATE layers
@@ -622,7 +704,7 @@ class GANTrainer:
             # D(real) and D(fake) as one pass over the 2N batch (DiscriminatorEngine.forward_pair): the spectral-norm
             # power iterations of the two reference forwards depend on the weights alone and run first, in order
             logits, ctx = self.deng.forward_pair(img, fake, ind, ind2, x2=x2, codes=codes, tail_loss='d_pair' if _FUSE_TAIL else None,
-                                                 loss_type=self.loss_type)
+                                                 loss_type=self.loss_type, lecam=self.lecam)
             n = ind.shape[0]
             lg = logits.view(-1)
             if 'tail' in ctx:
@@ -630,7 +712,7 @@ class GANTrainer:
                 # backward pass's tail-gradient launch (two launches where there were four)
                 self.loss_d, dboth = ctx['loss'][0], ctx['tail'][0]
             else:
-                self.loss_d, _, _, dboth = ops.gan_loss_d(lg[:n], lg[n:], self.loss_type, both=True)      # d(real) and d(fake) side by side
+                self.loss_d, _, _, dboth = self._loss_d(lg[:n], lg[n:], both=True)      # d(real) and d(fake) side by side
             # `fuse` (single rank): the raw per-half gradients stay as they are -- d_apply turns them into the update in one
             # fused launch per layer table (spectral-norm fix + Adam) and self.grad_d is not written
             yield from self.deng.backward_iter(ctx, dboth, self.grad_d, False, False, split=self.world > 1,
@@ -638,7 +720,7 @@ class GANTrainer:
             return
         d_real, ctx_r = self.deng.forward(img, ind, True)
         d_fake, ctx_f = self.deng.forward(fake, ind, True)
-        self.loss_d, dreal, dfake = ops.gan_loss_d(d_real.view(-1), d_fake.view(-1), self.loss_type)
+        self.loss_d, dreal, dfake = self._loss_d(d_real.view(-1), d_fake.view(-1))
         self.deng.backward(ctx_r, dreal, self.grad_d, False, False)
         yield from self.deng.backward_iter(ctx_f, dfake, self.grad_d, True, False, split=self.world > 1)   # final once the second pass added
 
@@ -803,7 +885,7 @@ class _CGANPieces:
         n = label.shape[0]
         d_real, ctx_r = t.deng.forward(inputs['real'], None, True, label=label)
         d_fake, ctx_f = t.deng.forward(Nhwc(fakes.t[j * n:(j + 1) * n], fakes.c), None, True, label=label)
-        t.loss_d, dreal, dfake = ops.gan_loss_d(d_real.view(-1), d_fake.view(-1), t.loss_type)
+        t.loss_d, dreal, dfake = t._loss_d(d_real.view(-1), d_fake.view(-1))
         # (the fake pass first: its transposed weight images are the current ones; the sum is the same either way)
         t.deng.backward(ctx_f, dfake, t.grad_d, False, False)
         t.deng.backward(ctx_r, dreal, t.grad_d, True, False)
@@ -845,6 +927,8 @@ class GraphedGANTrainer(GANTrainer):
         ts += [b for b in self.model.generator.buffers() if b.dtype != torch.int64 or b.dim() == 0]
         if self.ema is not None:
             ts += self.ema.state_tensors()
+        if self.lecam is not None:
+            ts += self.lecam.state_tensors()
         seen, out = set(), []
         for t in ts:                                  # (codebooks are buffers too: constant, copied all the same; aliases once)
             if t.data_ptr() not in seen:
@@ -865,8 +949,9 @@ class GraphedGANTrainer(GANTrainer):
         self.geng.refresh_images(force=True)          # G's weight images follow its parameters (D's are rebuilt per pass)
 
     def _stateful(self):
-        """The optimizers, and the averaged generator when there is one: what moves with a step besides the model."""
-        return (self.opt_g, self.opt_d) + ((self.ema,) if self.ema is not None else ())
+        """The optimizers, and the averaged generator and the LeCam state when there are any: what moves with a step besides
+        the model."""
+        return (self.opt_g, self.opt_d) + tuple(o for o in (self.ema, self.lecam) if o is not None)
 
     def _settle(self):
         """What follows a restored state_dict: the flat buffers, G's weight images, the codebooks' caches."""
@@ -957,6 +1042,11 @@ class GraphedGANTrainer(GANTrainer):
         if self._graphs is None:
             return super().train_iteration(img, label, zs)
         if self._hyper_key != self._hyper():
+            if self.lecam is not None and self._hyper_key[-1] != self._hyper()[-1]:
+                # the regulariser's numbers do not come back with a resumed optimizer state: a change is an attribute write,
+                # and capturing again would change the loss mid-run without a word
+                raise ValueError('Not valid LeCam regulariser: lambda, decay and start are arguments of the captured launches and '
+                                 f'were {self._hyper_key[-1][1:]} at capture(), now {self.lecam.hyper()}; build a new trainer to change them')
             # betas / eps / weight decay changed since the capture (a resumed optimizer state): the apply graphs hold the
             # old values as kernel arguments -- capture again (state is snapshotted and restored around it).  The learning
             # rate is read from device memory when the kernels run: a scheduler step needs no re-capture.
