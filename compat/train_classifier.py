@@ -20,7 +20,7 @@ class ClassifierDriver(Driver):
         self.tr.capture(input['img'], input['label'])
 
     def fused_step(self, input):                      # train_classifier.py:106-110 as one replayed step
-        # a short final batch runs the trainer's eager step (ClassifierTrainer.train_iteration)
+        # a short final batch runs the eager step at its own size (_FlatTrainer._dispatch, shared by all single-network trainers)
         return self.tr.train_iteration(input['img'], input['label'])
 
 

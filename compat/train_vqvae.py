@@ -16,7 +16,8 @@ class VQVAEDriver(Driver):
         self.tr.capture(input['img'])
 
     def fused_step(self, input):                      # train_vqvae.py:104-108 as one replayed step
-        # a short final batch runs the trainer's eager step (VQVAETrainer.train_iteration), the captured graph keeps its size
+        # a short final batch runs the eager step at its own size and the captured graph keeps its statics: the trainers'
+        # shared dispatch (_FlatTrainer._dispatch) decides by shapes and refuses anything but another batch size
         return self.tr.train_iteration(input['img'])
 
 

@@ -22,7 +22,7 @@ import torch.nn.functional as F
 from . import ops
 from .engine_base import _t1x1
 from .ops import Seg
-from .vae_engine import VAEEngine
+from .vae_engine import VAEEngine, check_train_batch
 
 Tensor = torch.Tensor
 
@@ -111,6 +111,8 @@ class CVAEEngine(VAEEngine):
     def forward(self, img: Tensor, label: Tensor, train: bool, eps: Optional[Tensor] = None, tape=None, want_grad: bool = False):
         """-> dict(loss, mu, logvar, img) with img back in (-1, 1) as NCHW fp32 (cvae.py:131-142)."""
         m = self.m
+        if train:
+            check_train_batch(img.shape[0])
         if train and eps is None:
             eps = torch.randn(img.shape[0], m.latent_size, device=img.device)
         zrow, mu, logvar, kld = self.encode(img, label, train, eps, tape)

@@ -10,6 +10,7 @@ import torch.nn as nn
 
 from ..config import cfg
 from ..cvae_engine import CVAEEngine
+from ..vae_engine import check_train_batch
 from .utils import FusedNet, check_labels, init_param, live_modes
 
 
@@ -101,6 +102,8 @@ class CVAE(FusedNet):
     def forward(self, input):
         """{'img' in (-1,1), 'label'[, 'eps']} -> {'loss', 'mu', 'logvar', 'img'} (cvae.py:131-142); `eps` injects the
         reparameterisation noise (parity runs), otherwise it is drawn here.  Evaluation mode takes z = mu."""
+        if self.training:
+            check_train_batch(input['img'].shape[0])           # one sample: refused before any launch, as the reference does
         eng = self._engine()
         label = self._label(input['label'])
         eps = input.get('eps')

@@ -10,6 +10,7 @@ import torch.nn as nn
 from ..config import cfg
 from ..modules import MultimodalController, Wrapper
 from ..vae_engine import VAEEngine
+from ..vae_engine import check_train_batch
 from .utils import FusedNet, init_param
 
 
@@ -109,6 +110,8 @@ class MCVAE(FusedNet):
     def forward(self, input):
         """{'img' in (-1,1), 'label'[, 'eps']} -> {'loss', 'mu', 'logvar', 'img'} (mcvae.py:133-144); `eps` injects
         the reparameterisation noise (parity runs), otherwise it is drawn here."""
+        if self.training:
+            check_train_batch(input['img'].shape[0])           # one sample: refused before any launch, as the reference does
         eng = self._engine()
         label = self._label(input['label'])
         eps = input.get('eps')

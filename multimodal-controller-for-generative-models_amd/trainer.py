@@ -30,6 +30,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .gan_engine import FlatState, Nhwc, _bump
+from .vae_engine import check_train_batch
 
 # 'thread_local': other threads of the process (the RCCL watchdog of a multi-rank run polls events) may keep
 # making HIP calls while this thread captures; only this thread's illegal calls abort the capture.
@@ -1038,9 +1039,15 @@ class GraphedGANTrainer(GANTrainer):
         return GANTrainer.train_iteration(self, img, label)
 
     def train_iteration(self, img, label, zs=None):
-        """Replays the captured step; `zs` (d_iters + g_iters latent batches) replaces the in-graph latent draws."""
+        """Replays the captured step; `zs` (d_iters + g_iters latent batches) replaces the in-graph latent draws.  The
+        paired and grouped passes are sized at capture: a batch of another shape than the captured one is refused before
+        the statics are touched (the driver drops the loader's short final batch)."""
         if self._graphs is None:
             return super().train_iteration(img, label, zs)
+        if tuple(img.shape) != tuple(self.s_img.shape) or tuple(label.shape) != tuple(self.s_label.shape):
+            raise ValueError(f'Not valid batch: the captured step takes images {tuple(self.s_img.shape)} and labels '
+                             f'{tuple(self.s_label.shape)}, got {tuple(img.shape)} and {tuple(label.shape)}; a GraphedGANTrainer '
+                             'runs whole batches only (drop_last)')
         if self._hyper_key != self._hyper():
             if self.lecam is not None and self._hyper_key[-1] != self._hyper()[-1]:
                 # the regulariser's numbers do not come back with a resumed optimizer state: a change is an attribute write,
@@ -1086,11 +1093,44 @@ class GraphedGANTrainer(GANTrainer):
         return self.loss_d, self.loss_g
 
 
+def batch_route(static_shapes, input_shapes) -> str:
+    """Where a batch of `input_shapes` goes on a trainer whose captured statics have `static_shapes` (None: nothing is
+    captured): 'replay' when every shape equals its static's, 'eager' when the inputs differ from the statics in the leading
+    (batch) dimension only and agree on it among themselves (the loader's short final batch), ValueError for anything
+    else -- another resolution, inputs that disagree on N, an empty batch.  A function of shapes alone: it runs before any
+    copy or launch, and a copy_ into the statics would raise late (sizes that differ) or broadcast silently (N = 1)."""
+    given = [tuple(int(x) for x in v) for v in input_shapes]
+    if not given or any(len(v) == 0 for v in given):
+        raise ValueError(f'Not valid batch: every input needs a leading batch dimension, got shapes {given}')
+    ns = sorted({v[0] for v in given})
+    if len(ns) != 1:
+        raise ValueError(f'Not valid batch: the inputs disagree on the batch size, got shapes {given}')
+    if ns[0] < 1:
+        raise ValueError(f'Not valid batch: empty batch, got shapes {given}')
+    if static_shapes is None:
+        return 'eager'
+    statics = [tuple(int(x) for x in s) for s in static_shapes]
+    if len(statics) != len(given):
+        raise ValueError(f'Not valid batch: the captured step takes {len(statics)} inputs, got {len(given)}')
+    if given == statics:
+        return 'replay'
+    for s, v in zip(statics, given):
+        if v[1:] != s[1:]:
+            raise ValueError(f'Not valid batch: input of shape {v} differs from the captured {s} in more than the batch '
+                             'dimension')
+    return 'eager'
+
+
 class _FlatTrainer:
     """Loop body shared by train_glow.py:108-121 and train_pixelcnn.py:108-121: zero_grad, forward, backward,
     clip_grad_norm_(parameters, 1), Adam(lr 3e-4) -- parameters and gradients each in one flat fp32 buffer, so the
     clip and the optimizer are one launch each and a data-parallel run all-reduces one bucket.  `capture` records
-    forward+backward and clip+Adam as two HIP graphs; the all-reduce of a multi-rank run sits between the replays."""
+    forward+backward and clip+Adam as two HIP graphs; the all-reduce of a multi-rank run sits between the replays.
+
+    Every subclass's `train_iteration` goes through `_dispatch`, which decides by shapes alone (`batch_route`): a batch that
+    matches the captured statics replays; a batch of another size (the loader's short final batch, down to one sample)
+    runs the eager step at its own size and leaves the graphs and their statics alone; any other mismatch raises
+    ValueError before anything is copied or launched."""
 
     def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), weight_decay=0.0, max_norm=1.0, dist_group=None, world_size=1,
                  optimizer='Adam', momentum=0.0):
@@ -1116,6 +1156,24 @@ class _FlatTrainer:
 
     def _refresh(self):                     # in-graph refresh of per-step random inputs
         pass
+
+    def _draw(self, *inputs):               # the per-step random input at the batch's own size (None: the step has none)
+        return None
+
+    def _check(self, *inputs):              # what the model refuses about a batch, before any launch
+        pass
+
+    def _dispatch(self, *inputs, rand=None):
+        """One train step on `inputs` (+ `rand`, the injected per-step random tensor): replay or eager, see the class."""
+        given = list(inputs) + ([rand] if rand is not None else [])
+        statics = [s.shape for s in self.statics[:len(given)]] if self._graphs else None
+        route = batch_route(statics, [t.shape for t in given])
+        self._check(*inputs)
+        if route == 'replay':
+            return self._replay(*inputs, rand=rand)
+        if rand is None:
+            rand = self._draw(*inputs)
+        return self._eager(*inputs, *(() if rand is None else (rand,)))
 
     def _apply(self):
         self.grad_norm = ops.clip_grad_norm_(self.gflat, self.max_norm)
@@ -1208,10 +1266,11 @@ class GlowTrainer(_FlatTrainer):
         eng.assume_initialized = True
         self._capture((img.clone(), label.clone(), torch.rand_like(img)), warmup)
 
+    def _draw(self, img, label):
+        return torch.rand_like(img)
+
     def train_iteration(self, img, label, noise=None):
-        if self._graphs:
-            return self._replay(img, label, rand=noise)
-        return self._eager(img, label, torch.rand_like(img) if noise is None else noise)
+        return self._dispatch(img, label, rand=noise)
 
 
 class PixelCNNTrainer(_FlatTrainer):
@@ -1234,14 +1293,13 @@ class PixelCNNTrainer(_FlatTrainer):
         self._capture((codes.clone(), label.clone()), warmup)
 
     def train_iteration(self, codes, label):
-        if self._graphs:
-            return self._replay(codes, label)
-        return self._eager(codes, label)
+        return self._dispatch(codes, label)
 
 
 class VAETrainer(_FlatTrainer):
     """train_vae.py:98-126 on the HIP path (config 1 of the reference runs this model on the CPU; this is the same
-    loop body on the GPU kernels).  MCVAE or the CVAE baseline (one GPU)."""
+    loop body on the GPU kernels).  MCVAE or the CVAE baseline (one GPU).  A batch of one sample is refused, as the
+    reference's BatchNorm1d refuses it in training mode (`check_train_batch`)."""
 
     def __init__(self, model, *a, world_size=1, **k):
         if world_size > 1 and hasattr(model.encoder, 'embedding'):
@@ -1263,19 +1321,21 @@ class VAETrainer(_FlatTrainer):
         eps = torch.randn(img.shape[0], self.model.latent_size, device=img.device)
         self._capture((img.clone(), label.clone(), eps), warmup)
 
+    def _draw(self, img, label):
+        return torch.randn(img.shape[0], self.model.latent_size, device=img.device)
+
+    def _check(self, img, label):
+        check_train_batch(img.shape[0])
+
     def train_iteration(self, img, label, eps=None):
-        if self._graphs:
-            return self._replay(img, label, rand=eps)
-        if eps is None:
-            eps = torch.randn(img.shape[0], self.model.latent_size, device=img.device)
-        return self._eager(img, label, eps)
+        return self._dispatch(img, label, rand=eps)
 
 
 class VQVAETrainer(_FlatTrainer):
     """train_vqvae.py:99-112 on the HIP path: zero_grad, forward (the quantiser's EMA buffers move as in the reference),
     backward, clip_grad_norm_(1), Adam(lr 3e-4).  No per-step random input.  The capture warm-up restores the whole
     state_dict, the codebook buffers (embedding, cluster_size, embedding_mean) included, so capturing does not advance
-    training.  A batch of another size than the captured one (the loader's short final batch) runs the eager step."""
+    training.  A batch of another size than the captured one runs the eager step (`_FlatTrainer._dispatch`)."""
 
     def __init__(self, model, *a, world_size=1, **k):
         if world_size > 1:
@@ -1295,9 +1355,7 @@ class VQVAETrainer(_FlatTrainer):
         self._capture((img.clone(),), warmup)
 
     def train_iteration(self, img):
-        if self._graphs and tuple(img.shape) == tuple(self.statics[0].shape):
-            return self._replay(img)
-        return self._eager(img)
+        return self._dispatch(img)
 
 
 class ClassifierTrainer(_FlatTrainer):
@@ -1305,7 +1363,7 @@ class ClassifierTrainer(_FlatTrainer):
     move as in the reference), backward, clip_grad_norm_(1), Adam (lr 1e-2 in the driver).  No per-step random input.
     The learning rate lives in device memory (FusedAdam), so a MultiStepLR step (`set_lr`) needs no re-capture.  The
     capture warm-up restores the whole state_dict, the BatchNorm buffers included, so capturing does not advance
-    training.  A batch of another size than the captured one (the loader's short final batch) runs the eager step."""
+    training.  A batch of another size than the captured one runs the eager step (`_FlatTrainer._dispatch`)."""
 
     def __init__(self, model, *a, world_size=1, **k):
         if world_size > 1:
@@ -1329,6 +1387,4 @@ class ClassifierTrainer(_FlatTrainer):
         self._capture((img.clone(), label.clone()), warmup)
 
     def train_iteration(self, img, label):
-        if self._graphs and tuple(img.shape) == tuple(self.statics[0].shape):
-            return self._replay(img, label)
-        return self._eager(img, label)
+        return self._dispatch(img, label)

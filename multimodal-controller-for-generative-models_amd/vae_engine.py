@@ -26,6 +26,14 @@ from .ops import Seg, pad8
 Tensor = torch.Tensor
 
 
+def check_train_batch(n: int):
+    """A training-mode step of MCVAE / CVAE on one sample is refused: the decoder's BatchNorm1d (mcvae.py:79, cvae.py:78)
+    would normalise a single value per channel, which the reference's nn.BatchNorm1d raises on.  Called before any launch."""
+    if int(n) < 2:
+        raise ValueError(f'Not valid batch: training mode needs more than 1 sample (the decoder normalises over the batch '
+                         f'alone, one value per channel), got {int(n)}; evaluation mode takes a single sample')
+
+
 class ConvAEEngine(EngineBase):
     """The strided-down, residual and transposed-up blocks MCVAE and VQ-VAE share.  `mc` / `mc3` / `mc6` are the
     blocks' MultimodalControllers (their codes gate the BatchNorm outputs), None for VQ-VAE's plain blocks."""
@@ -247,6 +255,8 @@ class VAEEngine(ConvAEEngine):
     def forward(self, img: Tensor, label: Tensor, train: bool, eps: Optional[Tensor] = None, tape=None, want_grad: bool = False):
         """-> dict(loss, mu, logvar, img) with img back in (-1, 1) as NCHW fp32 (mcvae.py:133-144)."""
         m = self.m
+        if train:
+            check_train_batch(img.shape[0])
         img01 = (img + 1) / 2
         if train and eps is None:
             eps = torch.randn(img.shape[0], m.latent_size, device=img.device)

@@ -36,9 +36,11 @@ def mc_mask(x: Tensor, indicator: Tensor, codebook: Tensor) -> Tensor:
     """MultimodalController.forward (modules/modules.py:71-76).
 
     ``code = indicator @ codebook`` broadcast over the trailing dims; the code
-    is a constant for autograd (``code.detach()``).
+    is a constant for autograd (``code.detach()``).  The one-hot indicator
+    and the 0/1 code follow the dtype of the state they meet (a float64 state
+    gives float64 all the way; exact either way).
     """
-    code = indicator.matmul(codebook).detach()
+    code = indicator.to(codebook.dtype).matmul(codebook).detach().to(x.dtype)
     return x * code.reshape(*code.shape, *([1] * (x.dim() - 2)))
 
 

@@ -1,4 +1,5 @@
-"""CPU restatement (plain fp32 torch ops) of the reference MCGlow (models/mcglow.py), affine coupling +
+"""CPU restatement (plain torch ops, in the dtype of the state and inputs given: fp32 as the reference runs, or
+float64 as a high-precision reference) of the reference MCGlow (models/mcglow.py), affine coupling +
 LU-parameterised invertible 1x1 convolution (the configuration process_control selects, utils.py:183-184).
 
 TEST INFRASTRUCTURE ONLY -- see ``oracle/__init__.py``.  The dequantisation noise (mcglow.py:299,

@@ -1,4 +1,5 @@
-"""CPU restatement (plain fp32 torch ops) of the reference MCGatedPixelCNN (models/mcpixelcnn.py).
+"""CPU restatement (plain torch ops, in the dtype of the state given: fp32 as the reference runs, or float64 as a
+high-precision reference) of the reference MCGatedPixelCNN (models/mcpixelcnn.py).
 
 TEST INFRASTRUCTURE ONLY -- see ``oracle/__init__.py``."""
 from __future__ import annotations

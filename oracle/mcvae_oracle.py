@@ -1,4 +1,5 @@
-"""CPU restatement (plain fp32 torch ops) of the reference MCVAE (models/mcvae.py).
+"""CPU restatement (plain torch ops, in the dtype of the state and inputs given: fp32 as the reference runs, or
+float64 as a high-precision reference) of the reference MCVAE (models/mcvae.py).
 
 TEST INFRASTRUCTURE ONLY -- see ``oracle/__init__.py``.  Pure functions over the reference's
 ``state_dict`` keys; the reparameterisation noise is an explicit input (the reference draws it inside

@@ -1,6 +1,7 @@
 """compat/test_vae.py, test_vqvae.py, test_pixelcnn.py, test_classifier.py, test_glow.py and test_generated.py as a reference
-user runs them, after one short epoch of the matching train driver on the synthetic on-device dataset (192 images, batch 64).
-Each test driver runs at --batch 80, so the last batch has 32 rows, once with --metrics device (mcgen_amd.evaluate) and once
+user runs them, after one short epoch of the matching train driver on the synthetic on-device dataset (200 images, batch 64: the
+epoch ends in a short batch of 8, which a captured trainer runs eagerly).  Each test driver runs at --batch 80, so the last
+batch has 40 rows, once with --metrics device (mcgen_amd.evaluate) and once
 with --metrics host (the per-batch `Metric` loop) under the same seed: the `logger.mean['test/*']` saved to
 output/result/<tag>.pt agree to 1e-5 relative (float32 torch formulas against float64 sums, test_eval_ref_cpu.py).  Every
 subprocess has its own timeout and its return code is asserted before the next one starts."""
@@ -22,7 +23,7 @@ for p in (DRV,):
 RTOL = 1e-5
 
 # IS and FID of a generated .npy with mcgen_amd.metrics, as compat/test_generated.py sets them up: COIL100's cfg, the classifier
-# checkpoint, the 192 synthetic training images as the real set; prints one JSON line
+# checkpoint, the 200 synthetic training images as the real set; prints one JSON line
 _EXPECTED = '''
 import json, sys
 sys.path.insert(0, {root!r})
@@ -38,7 +39,7 @@ assert generated.shape == (200, 3, 32, 32), generated.shape
 img = torch.tensor(generated / 255 * 2 - 1).cuda()
 assert not torch.isnan(img).any()
 model = M.feature_network('COIL100', checkpoint={ckpt!r}, device='cuda')
-real, _ = synthetic_uint8_dataset(192, [3, 32, 32], 100, seed=0, device='cuda')
+real, _ = synthetic_uint8_dataset(200, [3, 32, 32], 100, seed=0, device='cuda')
 real = [{{'img': normalize_uint8(chunk)}} for chunk in real.split(512)]
 print(json.dumps({{'is': M.inception_score(img, 'COIL100', model=model), 'fid': M.fid(img, 'COIL100', real=real, model=model)}}))
 '''
@@ -46,7 +47,7 @@ print(json.dumps({{'is': M.inception_score(img, 'COIL100', model=model), 'fid': 
 
 def _run(args, cwd, data, ok=True, timeout=600):
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1')
-    common = ['--data_name', data, '--log_interval', '0.5', '--synthetic_size', '192']
+    common = ['--data_name', data, '--log_interval', '0.5', '--synthetic_size', '200']
     r = subprocess.run([sys.executable, os.path.join(DRV, args[0])] + args[1:] + common, cwd=cwd, env=env, capture_output=True,
                        text=True, timeout=timeout)
     assert (r.returncode == 0) == ok, r.stdout[-3000:] + r.stderr[-3000:]
@@ -91,25 +92,25 @@ def _grids(cwd, tag, shape):
 def test_test_vae(tmp_path):
     who, tag = ['--model_name', 'cvae', '--control_name', 'None'], '0_CIFAR10_label_cvae'
     _train('train_vae.py', who, tmp_path, 'CIFAR10')
-    _device_against_host('test_vae.py', who, tag, ['Loss', 'BCE'], tmp_path, 'CIFAR10', 193)       # 80 + 80 + 32, then n = 1
-    _grids(tmp_path, tag, (32, 3, 32, 32))
+    _device_against_host('test_vae.py', who, tag, ['Loss', 'BCE'], tmp_path, 'CIFAR10', 201)       # 80 + 80 + 40, then n = 1
+    _grids(tmp_path, tag, (40, 3, 32, 32))
 
 
 def test_test_vqvae_and_test_pixelcnn(tmp_path):
     ae, ae_tag = ['--model_name', 'vqvae', '--control_name', 'None'], '0_CIFAR10_label_vqvae'
     _train('train_vqvae.py', ae, tmp_path, 'CIFAR10')
-    _device_against_host('test_vqvae.py', ae, ae_tag, ['Loss', 'MSE'], tmp_path, 'CIFAR10', 193)
-    _grids(tmp_path, ae_tag, (32, 3, 32, 32))
+    _device_against_host('test_vqvae.py', ae, ae_tag, ['Loss', 'MSE'], tmp_path, 'CIFAR10', 201)
+    _grids(tmp_path, ae_tag, (40, 3, 32, 32))
     who, tag = ['--model_name', 'mcpixelcnn', '--control_name', '0.5'], '0_CIFAR10_label_mcpixelcnn_0.5'
     _train('train_pixelcnn.py', who, tmp_path, 'CIFAR10')
-    _device_against_host('test_pixelcnn.py', who, tag, ['Loss', 'NLL'], tmp_path, 'CIFAR10', 193)
+    _device_against_host('test_pixelcnn.py', who, tag, ['Loss', 'NLL'], tmp_path, 'CIFAR10', 201)
     assert not (tmp_path / 'output' / 'vis' / f'input_{tag}.npy').exists()         # test_pixelcnn.py writes no grids
 
 
 def test_test_classifier(tmp_path):
     who, tag = ['--model_name', 'classifier', '--control_name', 'None'], '0_COIL100_label_classifier'
     _train('train_classifier.py', who, tmp_path, 'COIL100')
-    got = _device_against_host('test_classifier.py', who, tag, ['Loss', 'Accuracy'], tmp_path, 'COIL100', 192)   # no trailing append
+    got = _device_against_host('test_classifier.py', who, tag, ['Loss', 'Accuracy'], tmp_path, 'COIL100', 200)   # no trailing append
     assert 0.0 <= got['Accuracy'] <= 100.0
 
 
@@ -123,8 +124,8 @@ def test_test_glow(tmp_path):
     who, tag = ['--model_name', 'cglow', '--control_name', 'None'], '0_MNIST_label_cglow'
     _train('train_glow.py', who, tmp_path, 'MNIST', epochs=8)
     assert (tmp_path / 'output' / 'model' / f'{tag}_best.pt').exists()
-    _device_against_host('test_glow.py', who, tag, ['Loss'], tmp_path, 'MNIST', 193)
-    _grids(tmp_path, tag, (32, 1, 32, 32))                                         # the output is model.reverse(z) of the last batch
+    _device_against_host('test_glow.py', who, tag, ['Loss'], tmp_path, 'MNIST', 201)
+    _grids(tmp_path, tag, (40, 1, 32, 32))                                         # the output is model.reverse(z) of the last batch
 
 
 def test_test_generated(tmp_path):

@@ -271,7 +271,9 @@ def test_train_vqvae_driver_feeds_train_pixelcnn(tmp_path):
                 '--num_epochs', '2', '--resume_mode', '1'] + common, tmp_path)
     assert 'Resume from 2' in out
     assert _load_ck(ck)['epoch'] == 3
-    # (train_pixelcnn's own short-final-batch handling is a separate matter: give it whole batches)
+    # 200 images at batch 64: the epoch ends in a batch of 8, which the captured PixelCNNTrainer runs eagerly
     out = _run([os.path.join(drv, 'train_pixelcnn.py'), '--model_name', 'mcpixelcnn', '--control_name', '0.5',
-                '--num_epochs', '1'] + common + ['--synthetic_size', '192'], tmp_path)
+                '--num_epochs', '1'] + common + ['--log_interval', '0.2'], tmp_path)        # (0.2: every one of the 4 batches is logged)
     assert 'Not exists model tag: 0_CIFAR10_label_vqvae' not in out
+    pk = _load_ck(tmp_path / 'output' / 'model' / '0_CIFAR10_label_mcpixelcnn_0.5_checkpoint.pt')
+    assert pk['logger'].counter['train/Loss'] == 200                        # the logged train counter saw every image

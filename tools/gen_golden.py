@@ -1486,6 +1486,128 @@ def fx_dbi():
 FIXTURES.update(surgery_cgan=fx_surgery_cgan, surgery_cvae=fx_surgery_cvae, surgery_cglow=fx_surgery_cglow,
                 surgery_cpixelcnn=fx_surgery_cpixelcnn, dbi=fx_dbi)
 
+
+# ---- short batches: the first n samples of a small fixture's batch, the reference in float64 and in float32 -----------------
+class _GivenNoise:
+    """torch.rand_like / torch.randn_like return `noise` (cast to the asking tensor's dtype): the fixture's recorded draw."""
+
+    def __init__(self, noise):
+        self.noise = noise
+
+    def __enter__(self):
+        self._randn_like, self._rand_like = torch.randn_like, torch.rand_like
+        torch.randn_like = torch.rand_like = lambda t, **k: self.noise.to(t.dtype)
+        return self
+
+    def __exit__(self, *a):
+        torch.randn_like, torch.rand_like = self._randn_like, self._rand_like
+
+
+class _FloatFollows:
+    """The reference writes `.float()` on its one-hot indicators; while a float64 model runs, `.float()` gives `dtype`."""
+
+    def __init__(self, dtype):
+        self.dtype = dtype
+
+    def __enter__(self):
+        self._float = torch.Tensor.float
+        torch.Tensor.float = lambda t, *a, **k: t.to(self.dtype)
+        return self
+
+    def __exit__(self, *a):
+        torch.Tensor.float = self._float
+
+
+def _short_record(arrays, n, full, run):
+    """`run(dtype) -> (loss, {name: gradient}, extras)` of one training-mode forward + backward of the reference on the
+    first n samples.  Stored under n<n>/: the float64 loss and the float32 one, the float64 gradients -- whole when `full`,
+    else per parameter their norm, sum and max |g| (the digest form of vqvae_train_full_digest.npz) -- the same from the
+    float32 run, and per parameter max |g32 - g64|: the reference's own rounding, which the short-batch bounds rest on."""
+    l64, g64, extra = run(torch.float64)
+    l32, g32, _ = run(torch.float32)
+    assert l64.dtype == torch.float64 and l32.dtype == torch.float32 and set(g64) == set(g32)
+    names = sorted(g64)
+    p = f'n{n}/'
+    arrays[p + 'loss'] = np.array(l64.item()); arrays[p + 'loss_fp32'] = np.array(l32.item(), dtype=np.float32)
+    arrays[p + 'grad_names'] = np.array(names)
+    for tag, g in (('', g64), ('_fp32', g32)):
+        assert all(g[k].dtype == (torch.float32 if tag else torch.float64) for k in names)
+        if full:
+            for k in names:
+                arrays[p + f'grad{tag}/' + k] = g[k].numpy().copy()
+        else:
+            arrays[p + 'grad_norms' + tag] = np.array([g[k].double().norm().item() for k in names])
+            arrays[p + 'grad_sums' + tag] = np.array([g[k].double().sum().item() for k in names])
+            arrays[p + 'grad_maxabs' + tag] = np.array([g[k].double().abs().max().item() for k in names])
+    arrays[p + 'grad_numel'] = np.array([g64[k].numel() for k in names], dtype=np.int64)
+    arrays[p + 'fp32_err'] = np.array([(g32[k].double() - g64[k]).abs().max().item() for k in names])
+    for k, v in extra.items():
+        arrays[p + k] = v
+    print(f'  n={n}: loss {l64.item():.9f}  fp32 off by {abs(l32.item() - l64.item()):.2e}  worst gradient fp32 error / max|g| '
+          f'{max(float((g32[k].double() - g64[k]).abs().max() / g64[k].abs().max().clamp_min(1e-30)) for k in names):.2e}')
+
+
+def fx_vqvae_train_short():
+    """The VQ-VAE training forward + backward (train_vqvae.py:103-105) from vqvae_train_small.npz's state on the first
+    n = 1, 3 and 7 samples of its batch of 8: a loader's short final batch.  n = 3 whole, 1 and 7 as digests; with each the
+    code map and the arg-min margin of the float64 run (the float32 run must pick the same codes)."""
+    import models
+    d = gu.load_npz('vqvae_train_small.npz')
+    _set_vqvae_cfg([16, 16], 8, 64)
+    img = torch.from_numpy(d['img'])
+    arrays = {}
+    for n in (1, 3, 7):
+        codes = []
+
+        def run(dtype):
+            torch.manual_seed(0)
+            model = models.vqvae()
+            model.load_state_dict(gu.state_from_npz(d))
+            model = model.to(dtype); model.train(True)
+            seen = {}
+            h = model.quantizer.register_forward_pre_hook(lambda mod, inp: seen.update(x=inp[0].detach().clone(), emb=mod.embedding.clone()))
+            out = model({'img': img[:n].to(dtype).clone()})
+            h.remove()
+            out['loss'].backward()
+            codes.append(out['code'].clone())
+            extra = {'code': out['code'].numpy().copy(), 'dist_margin': _vq_margin(seen['x'], seen['emb']).numpy()}
+            return out['loss'].detach(), {k: p.grad.detach().clone() for k, p in model.named_parameters()}, extra
+        _short_record(arrays, n, n == 3, run)
+        assert torch.equal(codes[0], codes[1]), 'float32 and float64 disagree on a code: the error measured is no rounding error'
+    save('vqvae_train_short.npz', **arrays)
+
+
+def fx_cglow_short():
+    """The CGlow training forward + backward (train_glow.py:110-112) from cglow_small.npz's initialised state (its sd/ with
+    sd_init/ over it) on the first n = 1 and 3 samples of its batch of 4, with the first n rows of its recorded
+    dequantisation noise (noise/0/0).  n = 3 (= B - 1) whole, n = 1 as a digest.  Parameters the reference gives no
+    gradient (the split blocks' embeddings) are absent from grad_names, as in cglow_small.npz."""
+    import models
+    import cglow_ref
+    d = gu.load_npz('cglow_small.npz')
+    _, init, _ = cglow_ref.states(d)
+    cfg['model_name'] = 'cglow'; cfg['device'] = 'cpu'; cfg['classes_size'] = 12
+    cfg['data_shape'] = [1, 32, 32]
+    cfg['glow'] = dict(cglow_ref.GLOW_CFG)
+    img, lab, noise = torch.from_numpy(d['img']), torch.from_numpy(d['label']), torch.from_numpy(d['noise/0/0'])
+    arrays = {}
+    for n in (1, 3):
+        def run(dtype):
+            torch.manual_seed(0); np.random.seed(0)
+            model = models.cglow()
+            model.load_state_dict(init)
+            model = model.to(dtype); model.train(True)
+            with _GivenNoise(noise[:n]), _FloatFollows(dtype):
+                out = model({'img': img[:n].to(dtype).clone(), 'label': lab[:n]})
+                out['loss'].backward()
+            grads = {k: p.grad.detach().clone() for k, p in model.named_parameters() if p.grad is not None}
+            return out['loss'].detach(), grads, {}
+        _short_record(arrays, n, n == 3, run)
+    save('cglow_short.npz', **arrays)
+
+
+FIXTURES.update(vqvae_train_short=fx_vqvae_train_short, cglow_short=fx_cglow_short)
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--only', default=None)
